@@ -14,7 +14,14 @@ independent, so there is no data-path collective; with N > 1 each step ends with
 per-rank result table (gain[k], row4col[k*M], nf per matrix -- SURVEY 8(e)) that assembles the global table, overlapped
 with the next step's kernel.
 
-Prints ONE JSON line (rank 0):
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, one JSON line (rank 0) with metric, value,
+unit, higher_is_better, dtype, ms_per_step (wall time of one timed step, the slowest rank's), kernel_ms (HIP events) and the
+workload.  `--dump-outputs DIR` also writes what the last timed step computed as DIR/<name>.npy: for the dense configs nf, gain,
+row4col, col4row of rank 0's matrices (all of them where they fit in 64 MB, else a fixed seeded sample, see matrix_index), for c5
+probs and nf of every frame.  The inputs are generated from fixed seeds, so two builds can be compared output for output.
+
+`--full` adds everything else, to the same line:
+  parity_prune_vs_noprune, launch = the timed tables against an untimed no-prune launch; the relay launches counted;
   roofline.achieved   = algorithmic bytes per launch (SURVEY 8(d) B_alg, with P counted by the engine itself in its
                         no-prune mode and cross-checked against the reference on the cpu_baseline sample) / average
                         kernel duration measured with HIP events on the launch stream; roofline.traffic = HBM bytes per
@@ -27,7 +34,8 @@ Prints ONE JSON line (rank 0):
                         tables included -- SURVEY 8(d)'s metric definition; never `value`);
   configs             = the other BASELINE configs measured in the same run: c2 (1024 x 16x16, k=50), c3 (4096 x
                         32x32, k=200), c5 (1000 streamed 30x10 KITTI-like frames through the fused association kernel:
-                        batched throughput AND one-frame-per-call latency, weights checked against the reference).
+                        batched throughput AND one-frame-per-call latency, weights checked against the reference);
+  collective          = (N > 1) the same steps without the exchange first, its exposed time; the cross-rank table checks.
 `--config c2|c3|c5` makes that configuration the headline of the line instead.
 """
 from __future__ import annotations
@@ -204,6 +212,32 @@ def tables_parity(m, ref, ns=None):
     return {"nf": nf_ok, "gain_bits": g_ok, "row4col": r_ok, "col4row": c_ok, "matrices": int(ns), "all": nf_ok and g_ok and r_ok and c_ok}
 
 
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_BYTES = 60_000_000  # all the .npy files of one dump together stay below 64 MB
+
+
+def dense_outputs(m):
+    """The tables of the last timed step as float arrays (slots past nf zeroed): every matrix of the batch where they fit in
+    DUMP_BYTES, else a fixed seeded sample of matrices (ascending; their indices in matrix_index)."""
+    B, N, M, k = m["B"], m["N"], m["M"], m["k"]
+    per = 8 + 8 * k + 4 * k * (M + N) + 8  # nf, gain, row4col, col4row, matrix_index of one matrix
+    n = min(B, DUMP_BYTES // per)
+    idx = np.arange(B) if n == B else np.sort(np.random.default_rng(0).choice(B, n, replace=False))
+    nf = m["nf"][idx]
+    filled = np.arange(k)[None, :] < nf[:, None]
+    return {"nf": nf.astype(np.float64), "gain": np.where(filled, m["g"][idx], 0.0),
+            "row4col": np.where(filled[:, :, None], m["r4c"][idx], 0).astype(np.float32),
+            "col4row": np.where(filled[:, :, None], m["c4r"][idx], 0).astype(np.float32),
+            "matrix_index": idx.astype(np.float64)}
+
+
+def dump_outputs(d, arrays):
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 # ------------------------------------------------------------------------------------------------ dense configs
 class Exchange:
     """The one collective of a step: ONE all-gather of this rank's packed slice into the global table, asynchronous,
@@ -248,8 +282,11 @@ def all_reduce_(torch, dist, backend, t, op):
     return t
 
 
-def run_dense(eng, torch, dist, cfg, B, steps, warmup, rank, world, dev, tstream, use_dist, first, backend="nccl", no_gather_leg=False):
-    """C2 / C3 / C4: B dense matrices resident in HBM, one launch per step.  Returns the measurements of this rank."""
+def run_dense(eng, torch, dist, cfg, B, steps, warmup, rank, world, dev, tstream, use_dist, first, backend="nccl", no_gather_leg=False,
+              checks=True, tables=True):
+    """C2 / C3 / C4: B dense matrices resident in HBM, one launch per step.  Returns the measurements of this rank.
+    checks=False (a plain bench run): no untimed no-prune launch (pushed / parity_self / balg are None), no leg without the
+    exchange, no cross-rank checks -- only the warm-up and the timed steps.  tables=False: row4col / col4row stay on the device."""
     from probabilisticsemslam_amd import workloads as wl
     _, N, M, k, seed = wl.DENSE_CONFIGS[cfg]
     costs = wl.dense_batch(B, N, M, seed, first=first)  # rank-private slice of the one seeded stream
@@ -282,12 +319,14 @@ def run_dense(eng, torch, dist, cfg, B, steps, warmup, rank, world, dev, tstream
                 s[off_n: off_n + B * 4].view(torch.int32))
     eng.reserve(B, N, k)
     torch.cuda.synchronize()  # the allocations / fills above ran on the default stream
-    # untimed: the reference's push count P per matrix (no-prune mode), for the algorithmic byte count
-    eng.kbest_dev(d_cost, B, N, M, k, d_r4c[0], d_c4r, d_gain[0], d_nf[0], d_pushed=d_pushed, prune=False, stream=stream, tables_i8=i8)
-    torch.cuda.synchronize()
-    pushed = d_pushed.cpu().numpy()
-    nf_ref = d_nf[0].cpu().numpy().copy()
-    g_ref = d_gain[0].cpu().numpy().copy()
+    pushed = nf_ref = g_ref = None
+    if checks:
+        # untimed: the reference's push count P per matrix (no-prune mode), for the algorithmic byte count
+        eng.kbest_dev(d_cost, B, N, M, k, d_r4c[0], d_c4r, d_gain[0], d_nf[0], d_pushed=d_pushed, prune=False, stream=stream, tables_i8=i8)
+        torch.cuda.synchronize()
+        pushed = d_pushed.cpu().numpy()
+        nf_ref = d_nf[0].cpu().numpy().copy()
+        g_ref = d_gain[0].cpu().numpy().copy()
     pending = [None] * nbuf
 
     def step(i, ev=None, gather=True):
@@ -330,20 +369,20 @@ def run_dense(eng, torch, dist, cfg, B, steps, warmup, rank, world, dev, tstream
     # the same K steps WITHOUT the exchange first (N > 1 only; untimed as far as `value` goes): the collective's exposed time is
     # the difference of the two legs
     dt_nog = kern_nog = None
-    if use_dist and not no_gather_leg:
+    if use_dist and checks and not no_gather_leg:
         dt_nog, kern_nog = timed(False)
     dt, kern_ms = timed(True)
     last = (steps - 1) % nbuf
     nf = d_nf[last].cpu().numpy()
     g = d_gain[last].cpu().numpy()
-    r4c = d_r4c[last].cpu().numpy().astype(np.int32)
-    c4r = d_c4r.cpu().numpy().astype(np.int32)
+    r4c = d_r4c[last].cpu().numpy().astype(np.int32) if tables else None
+    c4r = d_c4r.cpu().numpy().astype(np.int32) if tables else None
     # the timed (pruning) path must reproduce the no-prune run bit for bit
-    parity_self = bool((nf == nf_ref).all() and (g.view(np.int64) == g_ref.view(np.int64)).all())
-    if use_dist:  # every rank must hold the same global table, and its own slice of it must be what it solved
+    parity_self = bool((nf == nf_ref).all() and (g.view(np.int64) == g_ref.view(np.int64)).all()) if checks else None
+    if use_dist and checks:  # every rank must hold the same global table, and its own slice of it must be what it solved
         mine = g_view(last, rank)
         assert torch.equal(mine[0], d_gain[last]) and torch.equal(mine[1], d_r4c[last]) and torch.equal(mine[2], d_nf[last])
-    if use_dist and world > 1:
+    if use_dist and checks and world > 1:
         parts = [g_view(last, r) for r in range(world)]
         chk = torch.stack([sum(p[0].sum() for p in parts), sum(p[1].double().sum() for p in parts),
                            sum(p[2].double().sum() for p in parts)])
@@ -374,7 +413,8 @@ def run_dense(eng, torch, dist, cfg, B, steps, warmup, rank, world, dev, tstream
                 "exposed_ms": None if dt_nog is None else 1e3 * (dt - dt_nog) / steps,
                 "kernel_ms_without_the_gather": kern_nog}
     return dict(costs=costs, N=N, M=M, k=k, seed=seed, B=B, dt=dt, kern_ms=kern_ms, nf=nf, g=g, r4c=r4c, c4r=c4r, pushed=pushed,
-                parity_self=parity_self, found=int(nf.sum()), balg=algorithmic_bytes(N, M, k, nf, pushed), collective=coll)
+                parity_self=parity_self, found=int(nf.sum()), balg=None if pushed is None else algorithmic_bytes(N, M, k, nf, pushed),
+                collective=coll)
 
 
 def host_inclusive_dense(eng, costs, N, M, k):
@@ -746,9 +786,10 @@ def run_c5(eng, torch, steps, warmup, dev, tstream, no_cpu, F=1000, k=200, nL=20
     nf = d_nf.cpu().numpy()
     probs = d_probs.cpu().numpy().reshape(F, nM, nL + 1)
     assert (nf >= 0).all(), "a frame did not fit the fused kernel"
-    if kernel_only:  # under the profiler: only the timed launches
+    outputs = {"probs": probs, "nf": nf.astype(np.float64)}  # what the last timed launch handed back (--dump-outputs)
+    if kernel_only:  # a plain run, or under the profiler: only the timed launches
         return {"workload": f"{F} streamed frames (kernel only)", "frames": F, "steps": steps, "ms_per_step": 1e3 * dt / steps,
-                "kernel_ms": kern_ms, "value": float(nf.sum()) * steps / dt, "unit": "assignments/s"}
+                "kernel_ms": kern_ms, "value": float(nf.sum()) * steps / dt, "unit": "assignments/s", "outputs": outputs}
     # -- the host-pointer entry: all frames in one call, and the reference's call pattern, one frame per call
     lib, ctx = eng.lib, eng.ctx
     p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
@@ -866,7 +907,7 @@ def run_c5(eng, torch, steps, warmup, dev, tstream, no_cpu, F=1000, k=200, nL=20
            "one_frame_per_call_floor": floor_us,
            "one_frame_per_call_small": small,
            "mean_rows_kept": float(D.mean()), "mean_pushed_per_frame": float(pushed.mean()),
-           "roofline": roofline_block("c5", F, balg, kern_ms)}
+           "roofline": roofline_block("c5", F, balg, kern_ms), "outputs": outputs}
     iss = issue_block("c5")
     if iss:
         out["issue"] = iss
@@ -948,7 +989,14 @@ def main():
     ap.add_argument("--no-extra", action="store_true", help="skip the `configs` block (c2, c3, c5 in the same run)")
     ap.add_argument("--no-host", action="store_true", help="skip value_host_inclusive (under the profiler: only the timed launches)")
     ap.add_argument("--kernel-only", action="store_true", help="c5 under the profiler: only the timed launches of the fused kernel")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: parity, roofline / issue, host-inclusive, CPU baselines, the `configs` block "
+                         "(--no-cpu / --no-extra / --no-host / --cpu-sample trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, < 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # (KBEST_BENCH_SELF_LAUNCH=1 takes the launcher path with one rank too: how it is exercised on a 1-GPU box)
     if (args.gpus > 1 or os.environ.get("KBEST_BENCH_SELF_LAUNCH") == "1") and "WORLD_SIZE" not in os.environ:
@@ -1002,7 +1050,10 @@ def main():
     if args.config == "c5":
         if world != 1:
             raise SystemExit("--config c5 is a single-GPU stream (frames are independent: run one stream per GPU)")
-        e = run_c5(eng, torch, args.steps, args.warmup, dev, tstream, args.no_cpu, kernel_only=args.kernel_only)
+        e = run_c5(eng, torch, args.steps, args.warmup, dev, tstream, args.no_cpu, kernel_only=args.kernel_only or not args.full)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, e["outputs"])
+        del e["outputs"]
         out = {"metric": "k-best assignments/sec (batched NxN cost matrices, k=200)", "value": e["value"], "unit": "assignments/s",
                "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": e["ms_per_step"], "higher_is_better": True,
                "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
@@ -1020,11 +1071,13 @@ def main():
             B = args.batch or Bc
         relays_before = eng.relay_launches()
         m = run_dense(eng, torch, dist if use_dist else None, args.config, B, args.steps, args.warmup, rank, world, dev, tstream,
-                      use_dist, rank * B, backend=backend)
+                      use_dist, rank * B, backend=backend, checks=args.full, tables=args.full or bool(args.dump_outputs))
         relayed = eng.relay_launches() - relays_before  # (of this rank's launches: the no-prune run, the warm-ups, the timed steps)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, dense_outputs(m))
         coll = m["collective"]
         t = torch.tensor([m["dt"], m["kern_ms"], (coll or {}).get("exposed_ms") or 0.0], dtype=torch.float64, device=dev)
-        tot = torch.tensor([m["found"], m["balg"]], dtype=torch.float64, device=dev)
+        tot = torch.tensor([m["found"], m["balg"] or 0], dtype=torch.float64, device=dev)
         if use_dist:
             all_reduce_(torch, dist, backend, t, dist.ReduceOp.MAX)
             all_reduce_(torch, dist, backend, tot, dist.ReduceOp.SUM)
@@ -1048,21 +1101,24 @@ def main():
                            "collective": coll["what"] if use_dist else "none (one GPU)"},
                 "problems_per_s": B * world * args.steps / dt_max,
                 "kernel_ms": kern_ms_max,
-                "parity_prune_vs_noprune": m["parity_self"],
-                "launch": {"relay_launches": relayed, "of": (args.steps + args.warmup) * (2 if coll and coll.get("exposed_ms") is not None else 1),
-                           "what": "launches of the 64-row kernel that ran as a relay: every matrix enumerated by three workgroups in turn, its LDS "
-                                   "handed on through HBM (DESIGN.md section 2 point 12; KBEST_RELAY=0 launches it plainly)"},
-                "roofline": roofline_block(args.config, B, balg_all / world, kern_ms_max,
-                                           {"mean_pushed_per_matrix": float(m["pushed"].mean())}),
             }
-            if coll:
-                out["collective"] = coll
-            iss = issue_block(args.config)
-            if iss:
-                out["issue"] = iss
-            if world == 1 and not args.no_host:
+            if args.full:
+                out.update({
+                    "parity_prune_vs_noprune": m["parity_self"],
+                    "launch": {"relay_launches": relayed, "of": (args.steps + args.warmup) * (2 if coll and coll.get("exposed_ms") is not None else 1),
+                               "what": "launches of the 64-row kernel that ran as a relay: every matrix enumerated by three workgroups in turn, its LDS "
+                                       "handed on through HBM (DESIGN.md section 2 point 12; KBEST_RELAY=0 launches it plainly)"},
+                    "roofline": roofline_block(args.config, B, balg_all / world, kern_ms_max,
+                                               {"mean_pushed_per_matrix": float(m["pushed"].mean())}),
+                })
+                if coll:
+                    out["collective"] = coll
+                iss = issue_block(args.config)
+                if iss:
+                    out["issue"] = iss
+            if args.full and world == 1 and not args.no_host:
                 out["value_host_inclusive"] = host_inclusive_dense(eng, m["costs"], N, M, k)
-            if world == 1 and not args.no_cpu:
+            if args.full and world == 1 and not args.no_cpu:
                 sample = args.cpu_sample or cpu_samples[args.config]
                 cb, ref, p_cpu = cpu_dense(m["costs"], N, M, k, sample)
                 ns = min(sample, B)
@@ -1085,12 +1141,13 @@ def main():
                     cb["parity_sample"] = f"all {tpa['matrices']} matrices of the timed launch (nf, gain bits, row4col, col4row) against the reference's tables from the all-core run"
                     out["cpu_baseline_all_cores"] = ca
                     out["speedup_vs_cpu_all_cores"] = out["value"] / ca["value"]
-            if world == 1 and not args.no_extra and args.config == "c4" and args.batch is None:
+            if args.full and world == 1 and not args.no_extra and args.config == "c4" and args.batch is None:
                 # the other BASELINE configs, measured in the same run (fewer steps each: the default run stays short)
                 extra = {}
                 for cfg in ("c2", "c3"):
                     extra[cfg] = dense_entry(eng, torch, cfg, 5, 1, dev, tstream, cpu_samples[cfg], args.no_cpu)
                 extra["c5"] = run_c5(eng, torch, 5, 1, dev, tstream, args.no_cpu)
+                del extra["c5"]["outputs"]
                 try:  # (not a BASELINE config: the general-size kernel's profile case, 512 x 128x128 -- its roofline line)
                     extra["w128"] = dense_entry(eng, torch, "w128", 3, 1, dev, tstream, None, True)
                 except Exception as ex:

@@ -45,7 +45,7 @@ def test_bench_world2_over_gloo_on_one_gpu(scaling, launcher):
     gloo (RCCL refuses two ranks on one GPU).  Launched exactly as the driver does (`python -m torch.distributed.run ...`), and once
     through bench.py's own launcher.  SURVEY 8(e)."""
     port = _free_port()
-    args = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--scaling", scaling]
+    args = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--scaling", scaling]
     if launcher == "driver":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.join(ROOT, "bench.py")] + args

@@ -4,7 +4,7 @@ out=$(pwd)/gpurun_out/ab_c5
 mkdir -p $out
 for r in 1 2; do
   for lib in "$@"; do
-    ( KBEST_LIB=$lib timeout 300 python3 bench.py --config c5 --steps 20 --warmup 3 --no-cpu ) > $out/b.txt 2>&1
+    ( KBEST_LIB=$lib timeout 300 python3 bench.py --full --config c5 --steps 20 --warmup 3 --no-cpu ) > $out/b.txt 2>&1
     python3 - <<PY
 import json
 d=None

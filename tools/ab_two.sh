@@ -4,7 +4,7 @@ out=$(pwd)/gpurun_out/ab_two
 mkdir -p $out
 for r in 1 2; do
   for v in $vals; do
-    ( env $var=$v timeout 400 python3 bench.py --config c4 --steps 5 --warmup 2 --no-cpu ) > $out/b.txt 2>&1
+    ( env $var=$v timeout 400 python3 bench.py --full --config c4 --steps 5 --warmup 2 --no-cpu ) > $out/b.txt 2>&1
     python3 - <<PY
 import json
 d=json.loads([l for l in open("$out/b.txt") if l.startswith("{")][-1])

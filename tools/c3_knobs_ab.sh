@@ -1,4 +1,4 @@
-run() { env "$@" timeout 200 python bench.py --config c3 --steps 5 --warmup 2 --no-cpu --no-extra --no-host 2>/dev/null | python -c "import sys,json; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$*', 'kernel_ms', round(j['kernel_ms'],3), 'relays', j['launch']['relay_launches'])"; }
+run() { env "$@" timeout 200 python bench.py --full --config c3 --steps 5 --warmup 2 --no-cpu --no-extra --no-host 2>/dev/null | python -c "import sys,json; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$*', 'kernel_ms', round(j['kernel_ms'],3), 'relays', j['launch']['relay_launches'])"; }
 for r in 1 2; do
 run A=1
 run KBEST_NWAVES=8

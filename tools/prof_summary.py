@@ -1,6 +1,6 @@
 """Summarise the rocprofv3 CSVs written by tools/prof.sh: per-kernel durations, PMC means, HBM traffic.
-The bench run under the profiler makes 1 untimed no-prune dispatch (push counting), W warm-up dispatches and K timed
-ones; only the last K dispatches of the k-best kernel are the measured workload, so means are taken over those."""
+The bench run under the profiler makes W warm-up dispatches and K timed ones (with --full, 1 untimed no-prune dispatch
+in front of them: push counting); only the last K dispatches of the k-best kernel are the measured workload, so means are taken over those."""
 import csv
 import glob
 import json
