@@ -205,12 +205,14 @@ int kbest_batch_f64_dev(kbest_ctx *ctx, const kbest_opts *opts, int B, int maxRo
  * reference-order kernel and its slots of d_row4col / d_col4row / d_gain are replaced (KBEST_TIE_REFERENCE: the reference's own answer);
  * with KBEST_FLAG_CANONICAL_TIES every problem flagged KBEST_TIE_BOUNDARY has its gain level at slot k completed under the engine's rule
  * (the problem again with k + 64 / 256 / 1 024 / KBEST_TIE_CAP solutions; the first k of the canonically ordered table written over the
- * problem's slots; KBEST_TIE_RESOLVED, or KBEST_TIE_UNRESOLVED where the level is larger than the cap).  A batch without flagged
- * problems costs one small copy.
+ * problem's slots; KBEST_TIE_RESOLVED, or KBEST_TIE_UNRESOLVED where the level is larger than the cap).  d_nf: the launch's nf
+ * (may be NULL); a re-run problem's entry takes the re-run's count -- with a cutoff, gains that are equal in exact arithmetic but
+ * round apart can make the reference keep another number of solutions than the first pass.  A batch without flagged problems costs
+ * one small copy.
  */
 int kbest_resolve_ties_dev(kbest_ctx *ctx, const kbest_opts *opts, int B, int maxRow, int maxCol, const int32_t *d_nRow,
                            const int32_t *d_nCol, const double *d_cost, const int64_t *d_costOff, int k, int32_t *d_row4col,
-                           int32_t *d_col4row, double *d_gain, int32_t *d_tie_flags, void *stream);
+                           int32_t *d_col4row, double *d_gain, int32_t *d_tie_flags, int32_t *d_nf, void *stream);
 
 /*
  * Same with host buffers (copies in, runs, copies out, synchronises; col4row may be NULL = not wanted).  Uniform square batches
@@ -279,6 +281,8 @@ int kbest_set_profile_buffer(kbest_ctx *ctx, void *d_buf);
  *                  (nL+nM) x nM column-major
  *   probs          packed, problem b at probOff[b] doubles: [nM][nL+1] row-major
  *                  (the reference's vector<vector<double>>)
+ *   nf[b]          the solutions the k-best found (at most k); nM == 1, where the reference
+ *                  enumerates nothing (:554-570): the entries it weighs, x < 42
  * Host buffers.
  */
 int kbest_weights_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM,
@@ -371,6 +375,7 @@ long long kbest_relay_launches(kbest_ctx *ctx);  /* (-1: null context) */
 #define KBEST_ROUTE_WIDE 8    /* the general-size kernel: any size, any k                               */
 #define KBEST_ROUTE_RELAY 16  /* ... as a relay of several workgroups per matrix                        */
 #define KBEST_ROUTE_EXACT 64  /* the reference-order kernel (KBEST_FLAG_REFERENCE_ORDER; > 1 024 rows)   */
+#define KBEST_ROUTE_SPLIT 128 /* the 64-row kernel with several workgroups per matrix and the merge      */
 #define KBEST_ROUTE_EXTRA 32  /* the launch enumerated the solution behind the k-th (exact ties checked) */
 int kbest_last_route(kbest_ctx *ctx);
 

@@ -1281,6 +1281,7 @@ static int batch_dev_impl(kbest_ctx *ctx, const kbest_opts *opts, int B, int max
         hipError_t e = kb::launch_kbest(p, B * S, shp.nWaves, s);
         if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "kbest kernel launch", e);
         if (S > 1) {  // the global k best of every matrix from its shares' lists
+            ctx->lastRoute |= KBEST_ROUTE_SPLIT;
             kb::MergeParams mp;
             memset(&mp, 0, sizeof(mp));
             mp.gain = reinterpret_cast<const unsigned char *>(sb + sl.offGain);
@@ -1855,7 +1856,7 @@ int kbest_batch_f64(kbest_ctx *ctx, const kbest_opts *opts, int B, int maxRow, i
     std::vector<int32_t> fl((size_t)B);
     HIP_TRY(ctx, hipMemcpy(fl.data(), dFlags.as<int32_t>(), (size_t)B * 4, hipMemcpyDeviceToHost));
     if (!(opts->flags & KBEST_FLAG_NO_TIE_RESOLVE))
-        kb_complete_tie_levels(ctx, opts, B, maxRow, maxCol, nRow, nCol, cost, costOff, k, row4col, col4row, gain, fl.data(), nullptr);
+        kb_complete_tie_levels(ctx, opts, B, maxRow, maxCol, nRow, nCol, cost, costOff, k, row4col, col4row, gain, nf, fl.data(), nullptr);
     for (int b = 0; b < B; b++) {
         if ((fl[b] & KBEST_TIE_BOUNDARY) && !(fl[b] & KBEST_TIE_RESOLVED)) fl[b] |= KBEST_TIE_UNRESOLVED;
         if ((fl[b] & KBEST_TIE_UNORDERED) && !(fl[b] & KBEST_TIE_RESOLVED)) {
@@ -1887,14 +1888,15 @@ int kbest_batch_f64(kbest_ctx *ctx, const kbest_opts *opts, int B, int maxRow, i
 // (fl[b] & KBEST_TIE_BOUNDARY without KBEST_TIE_RESOLVED): those problems again,
 // alone, with k + 64, then k + 256, k + 1 024, then k + KBEST_TIE_CAP solutions -- whichever kernel takes that k; the table comes back in the
 // canonical order -- until the level ends inside the table; the first k of the ordered table then replace the problem's slots in the
-// caller's HOST tables (row4col / col4row: int32, or int8 with KBEST_FLAG_TABLES_I8; col4row may be null) and the problem is flagged
+// caller's HOST tables (row4col / col4row: int32, or int8 with KBEST_FLAG_TABLES_I8; col4row may be null; nf, where not null, takes the
+// re-run's count) and the problem is flagged
 // KBEST_TIE_RESOLVED.  Nothing of a problem is touched before its re-run has validated; a re-run that fails (beyond a kernel's
 // limits, out of memory) or a level of more than KBEST_TIE_CAP members beyond k leaves the first pass' tables and the flags as they
 // are (the caller marks such a problem KBEST_TIE_UNRESOLVED).  changed (optional): the problems whose tables were replaced.
 // cost / costOff / nRow / nCol: as kbest_batch_f64's (host).
 void kb_complete_tie_levels(kbest_ctx *ctx, const kbest_opts *opts, int B, int maxRow, int maxCol, const int32_t *nRow, const int32_t *nCol,
-                            const double *cost, const int64_t *costOff, int k, void *row4col, void *col4row, double *gain, int32_t *fl,
-                            std::vector<int> *changed)
+                            const double *cost, const int64_t *costOff, int k, void *row4col, void *col4row, double *gain, int32_t *nf,
+                            int32_t *fl, std::vector<int> *changed)
 {
     static const int steps[4] = {64, 256, 1024, KBEST_TIE_CAP};
     const bool i8 = (opts->flags & KBEST_FLAG_TABLES_I8) != 0;
@@ -1939,6 +1941,9 @@ void kb_complete_tie_levels(kbest_ctx *ctx, const kbest_opts *opts, int B, int m
             if (col4row)
                 memcpy(static_cast<char *>(col4row) + (size_t)b * k * maxRow * esz, sC.data() + (size_t)i * k * maxRow * esz, (size_t)k * maxRow * esz);
             memcpy(gain + (size_t)b * k, sGain.data() + (size_t)i * k, (size_t)k * 8);
+            // the count too: with a cutoff, gains that are equal in exact arithmetic but round apart in the shifted sums (cutHyp) and
+            // in the unshifted ones (the break) let a tree split in another order keep another number of solutions
+            if (nf) nf[b] = sNf[i];
             fl[b] = (fl[b] & KBEST_TIE_INSIDE) | KBEST_TIE_REFERENCE;
             if (changed) changed->push_back(b);
         }
@@ -2008,10 +2013,10 @@ extern "C" {
 // The asynchronous entries report a tie at slot k, they cannot complete it.  This SYNCHRONOUS helper does, for the tables of an
 // earlier kbest_batch_f64_dev call that are still on the device: it waits for `stream`, reads the flags, completes the flagged gain
 // levels (kb_complete_tie_levels: the flagged problems again with k + 64 / 256 / 1 024 solutions) and patches those problems' slots
-// of the device tables and flags in place.
+// of the device tables, d_nf (where given) and the flags in place.
 int kbest_resolve_ties_dev(kbest_ctx *ctx, const kbest_opts *opts, int B, int maxRow, int maxCol, const int32_t *d_nRow,
                            const int32_t *d_nCol, const double *d_cost, const int64_t *d_costOff, int k, int32_t *d_row4col,
-                           int32_t *d_col4row, double *d_gain, int32_t *d_tie_flags, void *stream)
+                           int32_t *d_col4row, double *d_gain, int32_t *d_tie_flags, int32_t *d_nf, void *stream)
 {
     if (!ctx) return KBEST_ERR_BAD_ARG;
     if (!opts || B < 0 || k < 1 || maxCol < 1 || maxRow < maxCol || !d_cost || !d_row4col || !d_gain || !d_tie_flags ||
@@ -2054,11 +2059,15 @@ int kbest_resolve_ties_dev(kbest_ctx *ctx, const kbest_opts *opts, int B, int ma
         const size_t src = d_costOff ? (size_t)hOff[b] : (size_t)b * per;
         HIP_TRY(ctx, hipMemcpy(sCost.data() + (size_t)i * per, d_cost + src, (size_t)sRow[i] * sCol[i] * 8, hipMemcpyDeviceToHost));
     }
+    // the launch's counts of those problems: a re-run on the reference-order kernel may keep another number of solutions
+    std::vector<int32_t> sNf(d_nf ? n : 0);
+    for (int i = 0; i < (int)sNf.size(); i++) HIP_TRY(ctx, hipMemcpy(&sNf[i], d_nf + idx[i], 4, hipMemcpyDeviceToHost));
     std::vector<int> changed;
     kb_complete_tie_levels(ctx, opts, n, maxRow, maxCol, sRow.data(), sCol.data(), sCost.data(), sOff.data(), k, sR.data(), d_col4row ? sC.data() : nullptr,
-                           sGain.data(), sFl.data(), &changed);
+                           sGain.data(), d_nf ? sNf.data() : nullptr, sFl.data(), &changed);
     for (int i : changed) {
         const int b = idx[i];
+        if (d_nf) HIP_TRY(ctx, hipMemcpy(d_nf + b, &sNf[i], 4, hipMemcpyHostToDevice));
         HIP_TRY(ctx, hipMemcpy(reinterpret_cast<char *>(d_row4col) + (size_t)b * k * maxCol * esz, sR.data() + (size_t)i * k * maxCol * esz, (size_t)k * maxCol * esz, hipMemcpyHostToDevice));
         if (d_col4row)
             HIP_TRY(ctx, hipMemcpy(reinterpret_cast<char *>(d_col4row) + (size_t)b * k * maxRow * esz, sC.data() + (size_t)i * k * maxRow * esz, (size_t)k * maxRow * esz, hipMemcpyHostToDevice));

@@ -85,7 +85,7 @@ struct WeightParams {
     const long long *costOff;
     const double *gain;       // [B][k]
     const int *row4col;       // [B][k][maxCol]
-    const int *nf;            // [B]
+    int *nf;                  // [B] (nM == 1: set to the entries weighed)
     double *probs;
     const long long *probOff;
     int k, maxCol;
@@ -543,8 +543,8 @@ hipError_t launch_to_probs(double *x, long long n, hipStream_t stream);
 #ifdef __cplusplus
 #include <vector>
 void kb_complete_tie_levels(kbest_ctx *ctx, const kbest_opts *opts, int B, int maxRow, int maxCol, const int32_t *nRow, const int32_t *nCol,
-                            const double *cost, const int64_t *costOff, int k, void *row4col, void *col4row, double *gain, int32_t *fl,
-                            std::vector<int> *changed);
+                            const double *cost, const int64_t *costOff, int k, void *row4col, void *col4row, double *gain, int32_t *nf,
+                            int32_t *fl, std::vector<int> *changed);
 #endif
 int kbest_batch_f64_keep(kbest_ctx *ctx, const kbest_opts *opts, int B, int maxRow, int maxCol, const int32_t *nRow,
                          const int32_t *nCol, const double *cost, const int64_t *costOff, int k, int32_t *row4col,

@@ -1796,13 +1796,18 @@ __global__ void __launch_bounds__(256) weights_kernel(WeightParams p)
         const double *cost = p.cost + p.costOff[b];
         if (tid == 0) {
             double norm = 0.0;
+            int cnt = 0;
             for (int i = 0; i <= nL; i++)
-                if (cost[i] < GATE) norm += exp(-cost[i]);
+                if (cost[i] < GATE) { norm += exp(-cost[i]); cnt++; }
             norm = 1.0 / norm;
             for (int i = 0; i <= nL; i++) {
                 const double q = (cost[i] < GATE) ? exp(-cost[i]) : 0.0;
                 probs[(i >= nL) ? nLo : (ridx ? ridx[i] : i)] = q * norm;
             }
+            // nf: the entries weighed, at most k -- what the fused kernels report (kbest_small.hip, kbest_bnb.hip) -- not the count
+            // of the enumeration, which keeps the entries up to best + 42 inclusive
+            const int kw = p.kUse > 0 ? p.kUse : p.k;
+            if (p.nf[b] >= 0) p.nf[b] = cnt < kw ? cnt : kw;
         }
         return;
     }

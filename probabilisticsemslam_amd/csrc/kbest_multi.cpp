@@ -538,7 +538,7 @@ int kbest_batch_f64_multi_ex(kbest_multi *m, const kbest_opts *opts, int mode, i
                 std::vector<int> changed;
                 kb_complete_tie_levels(d.ctx, opts, nb, maxRow, maxCol, nRow ? nRow + b0 : nullptr, nCol ? nCol + b0 : nullptr, cost + (size_t)b0 * per,
                                        nullptr, k, row4col + (size_t)b0 * k * maxCol, col4row ? col4row + (size_t)b0 * k * maxRow : nullptr,
-                                       gain + (size_t)b0 * k, fl, &changed);
+                                       gain + (size_t)b0 * k, nf + b0, fl, &changed);
                 std::vector<signed char> r8((size_t)k * maxCol);
                 for (int i : changed) {
                     const int32_t *src = row4col + ((size_t)b0 + i) * k * maxCol;
@@ -550,6 +550,7 @@ int kbest_batch_f64_multi_ex(kbest_multi *m, const kbest_opts *opts, int mode, i
                         W_HIP(d, hipMemcpy(dst, src, (size_t)k * maxCol * 4, hipMemcpyHostToDevice));
                     }
                     W_HIP(d, hipMemcpy(mine + sl.offGain + (size_t)i * k * 8, gain + ((size_t)b0 + i) * k, (size_t)k * 8, hipMemcpyHostToDevice));
+                    W_HIP(d, hipMemcpy(mine + sl.offNf + (size_t)i * 4, nf + b0 + i, 4, hipMemcpyHostToDevice));
                 }
             }
             for (int i = 0; i < nb; i++)

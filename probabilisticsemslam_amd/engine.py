@@ -24,6 +24,7 @@ KBEST_TIE_INSIDE, KBEST_TIE_BOUNDARY, KBEST_TIE_RESOLVED, KBEST_TIE_REFERENCE = 
 KBEST_TIE_UNCHECKED, KBEST_TIE_UNORDERED, KBEST_TIE_UNRESOLVED = 1 << 28, 1 << 29, 1 << 30
 KBEST_ROUTE_LANE, KBEST_ROUTE_SMALL, KBEST_ROUTE_FAST, KBEST_ROUTE_WIDE, KBEST_ROUTE_RELAY, KBEST_ROUTE_EXTRA = 1, 2, 4, 8, 16, 32
 KBEST_ROUTE_EXACT = 64
+KBEST_ROUTE_SPLIT = 128  # (KBEST_SPLIT: several workgroups per matrix of the 64-row kernel, then the merge)
 KBEST_TIE_CAP = 4096
 KBEST_MAX_DIM = 64        # rows handled by the LDS-resident kernel
 KBEST_MAX_DIM_WIDE = 1024  # rows of the general-size kernel (beyond KBEST_MAX_DIM)
@@ -132,7 +133,7 @@ def load_library():
     if hasattr(lib, "kbest_last_route"):
         lib.kbest_last_route.argtypes = [vp]
         lib.kbest_resolve_ties_dev.argtypes = [vp, C.POINTER(KBestOpts), C.c_int, C.c_int, C.c_int, i32p, i32p, dp, i64p, C.c_int, i32p, i32p, dp,
-                                               i32p, vp]
+                                               i32p, i32p, vp]
         lib.kbest_multi_last_tie_flags.argtypes = [vp, i32p, C.c_int]
     if hasattr(lib, "kbest_last_tie_flags"):
         lib.kbest_last_tie_flags.argtypes = [vp, i32p, C.c_int]
@@ -398,18 +399,19 @@ class KBestEngine:
 
 
     def resolve_ties_dev(self, d_cost, B, N, M, k, d_row4col, d_col4row, d_gain, d_tie_flags, maximize=False, cutoff=None, stream=None,
-                         d_nRow=None, d_nCol=None, d_costOff=None, tables_i8=False, reference_ties=False, canonical_ties=False):
+                         d_nRow=None, d_nCol=None, d_costOff=None, tables_i8=False, reference_ties=False, canonical_ties=False, d_nf=None):
         """kbest_resolve_ties_dev: the synchronous second call behind kbest_dev -- completes the gain levels that straddle slot k
         in the device tables (same arguments as the launch).  By default (reference_ties: the accepted no-op flag) every problem flagged
         with a tie is replaced by the reference-order kernel's tables; canonical_ties: KBEST_FLAG_CANONICAL_TIES -- the engine's own
-        rule instead (levels that straddle slot k completed in steps)."""
+        rule instead (levels that straddle slot k completed in steps).  d_nf: the launch's nf tensor -- a re-run problem's entry takes
+        the re-run's count (without it the launch's count stays, which a cutoff on gains that round apart can make stale)."""
         o = self._opts(maximize, cutoff, (KBEST_FLAG_TABLES_I8 if tables_i8 else 0) | (KBEST_FLAG_REFERENCE_TIES if reference_ties else 0) |
                        (KBEST_FLAG_CANONICAL_TIES if canonical_ties else 0))
 
         def dp(t):
             return None if t is None else C.c_void_p(t.data_ptr())
         self._check(self.lib.kbest_resolve_ties_dev(self.ctx, C.byref(o), B, N, M, dp(d_nRow), dp(d_nCol), dp(d_cost), dp(d_costOff), k,
-                                                    dp(d_row4col), dp(d_col4row), dp(d_gain), dp(d_tie_flags),
+                                                    dp(d_row4col), dp(d_col4row), dp(d_gain), dp(d_tie_flags), dp(d_nf),
                                                     C.c_void_p(stream) if stream else None))
 
     def merge_topk_dev(self, B, n_shard, k, M, d_gain, d_row4col, d_nf, shard_stride_bytes, d_out_gain, d_out_row4col, d_out_nf,

@@ -50,7 +50,7 @@ while time.time() - t0 < budget:
     if ref:
         eng.lib.kbest_reserve_exact(eng.ctx, B, maxN, maxM, k)
     eng.kbest_dev(d_cost, B, maxN, maxM, k, d_r, d_c, d_g, d_n, stream=st, d_tie_flags=d_f, tables_i8=i8, **kw, **shp)
-    eng.resolve_ties_dev(d_cost, B, maxN, maxM, k, d_r, d_c, d_g, d_f, stream=st, tables_i8=i8, canonical_ties=not ref, **kw, **shp)
+    eng.resolve_ties_dev(d_cost, B, maxN, maxM, k, d_r, d_c, d_g, d_f, stream=st, tables_i8=i8, canonical_ties=not ref, d_nf=d_n, **kw, **shp)
     torch.cuda.synchronize()
     nf, r4c, c4r, g, fl = d_n.cpu().numpy(), d_r.cpu().numpy().astype(np.int32), d_c.cpu().numpy().astype(np.int32), d_g.cpu().numpy(), d_f.cpu().numpy()
     desc = (seed, ncall, B, maxN, maxM, k, i8, ragged, integer, ref, kw)

@@ -308,3 +308,89 @@ def canonical_assignment_prob(cond, nL, nM, k, cap=4096):
     cutoff 42 (canonical_kbest), then the reference's accumulation.  Returns (probs, nf, boundary, resolved)."""
     n, r4c, g, boundary, resolved = canonical_kbest(cond, nL + nM, nM, k, cutoff=42.0, cap=cap, run_cap=4096)
     return weights_from_solutions(r4c, g, nL, nM), n, boundary, resolved
+
+
+# ---------------------------------------------------------------- high-precision weights (tests of the probabilities)
+
+HP_PREC = 160  # bits of the accumulation and the division below (113 would do: nothing here loses more than a few)
+
+
+def hp_weights_from_solutions(row4col, gain, nL, nM, gate=True):
+    """assignmentProb's weights (assignment.cpp:616-648) over a given list of solutions, in high precision: the solutions kept
+    and the exponents best - g exactly as the reference decides and computes them in float64 (the gate best + 42 > g strict;
+    gate=False: bruteForceProb, every solution), exp, accumulation and division in mpmath at HP_PREC bits.  Returns an
+    [nM, nL + 1] object array of mpmath numbers (exact zeros where no kept solution puts a weight)."""
+    import mpmath
+    r = np.asarray(row4col, dtype=np.int64).reshape(-1, nM)
+    g = np.asarray(gain, dtype=np.float64).reshape(-1)
+    with mpmath.workprec(HP_PREC):
+        zero = mpmath.mpf(0)
+        probs = np.array([[zero] * (nL + 1) for _ in range(nM)], dtype=object)
+        total = zero
+        best = g[0] if len(g) else 0.0
+        for s in range(len(g)):
+            if gate and not (best + 42.0 > g[s]):
+                continue
+            w = mpmath.exp(mpmath.mpf(float(best - g[s])))
+            total += w
+            for c in range(nM):
+                row = int(r[s, c])
+                probs[c, row if row < nL else nL] += w
+        if total != 0:
+            for c in range(nM):
+                for j in range(nL + 1):
+                    probs[c, j] = probs[c, j] / total
+    return probs
+
+
+def hp_single_column(col, nL):
+    """assignmentProb / bruteForceProb with nM == 1 (assignment.cpp:554-570) in high precision: exp(-x) over the entries
+    x < 42 (compared in float64), normalised.  Returns a [1, nL + 1] object array."""
+    import mpmath
+    x = np.asarray(col, dtype=np.float64).reshape(-1)
+    with mpmath.workprec(HP_PREC):
+        w = [mpmath.exp(-mpmath.mpf(float(x[i]))) if x[i] < 42.0 else mpmath.mpf(0) for i in range(nL + 1)]
+        total = sum(w, mpmath.mpf(0))
+        return np.array([[wi / total if total != 0 else wi for wi in w]], dtype=object)
+
+
+def hp_assignment_prob(cond, nL, nM, k, canonical=False):
+    """High-precision assignmentProb of a conditioned block: the k best within the cutoff 42 in the reference's order
+    (orc_kbest) or in the engine's order of exact ties (canonical_kbest), then hp_weights_from_solutions.  (probs, nf)."""
+    if nM == 1:
+        return hp_single_column(cond, nL), None
+    if canonical:
+        nf, r4c, g, _, _ = canonical_kbest(cond, nL + nM, nM, k, cutoff=42.0, run_cap=4096)
+    else:
+        nf, r4c, _, g = orc_kbest(cond, nL + nM, nM, k, cutoff=42.0)
+    return hp_weights_from_solutions(r4c[:nf], g[:nf], nL, nM), nf
+
+
+def hp_brute_force_prob(cond, nL, nM):
+    """High-precision bruteForceProb of a conditioned block: every solution the reference enumerates (kBest2D up to its upper
+    bound on their number, no cutoff, no gate).  (probs, nf)."""
+    if nM == 1:
+        return hp_single_column(cond, nL), None
+    _, _, upper = brute_force_prob(cond, nL, nM)
+    nf, r4c, _, g = orc_kbest(cond, nL + nM, nM, upper)
+    return hp_weights_from_solutions(r4c[:nf], g[:nf], nL, nM, gate=False), nf
+
+
+def hp_mismatch(p, hp, nf):
+    """None if every float64 probability p is within (2 nf + 8) 2^-53 of the high-precision value, relative, and exactly 0
+    wherever that value is 0; else a description of the first entry that is not.  nf: solutions weighed (None: one column)."""
+    import mpmath
+    p = np.asarray(p, dtype=np.float64)
+    if p.shape != hp.shape:
+        return f"shape {p.shape} != {hp.shape}"
+    n = hp.size if nf is None else int(nf)
+    with mpmath.workprec(HP_PREC):
+        tol = mpmath.mpf(2 * n + 8) * mpmath.mpf(2) ** -53
+        for idx in np.ndindex(hp.shape):
+            want, got = hp[idx], float(p[idx])
+            if want == 0:
+                if got != 0.0:
+                    return f"{idx}: {got!r} where the exact value is 0"
+            elif not abs(mpmath.mpf(got) - want) <= tol * want:
+                return f"{idx}: {got!r} against {mpmath.nstr(want, 20)} (rel {mpmath.nstr(abs(mpmath.mpf(got) - want) / want, 3)}, nf {n})"
+    return None
