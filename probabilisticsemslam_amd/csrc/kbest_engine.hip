@@ -139,8 +139,9 @@ constexpr int OPT_TSEL = 4;  // tickets that can be selected in one round (the f
 // atoms are a few thousand KNOWN assignments: the (k-1)-th smallest of their costs, plus the optimum, bounds the k-th
 // best gain from above -- 1.7-3.5x the true gap on 64x64, k = 200 -- while the pool has no threshold at all yet
 // (round 1 would otherwise complete every child of 8 hypotheses) and only a loose one for some rounds after.
-// The (k-1)-th smallest is bracketed by bisection on the value: every thread keeps its share of the combinations in
-// registers and counts those <= x; the upper end of the bracket is a valid bound whatever the precision.
+// The (k-1)-th smallest is bracketed on the value: every thread keeps its share of the combinations in registers and counts
+// those <= x (doubling steps, then one histogram pass over the bracket); the upper end of the bracket is a valid bound
+// whatever the precision.
 // A separate function on purpose: its registers must not count against the round loop's.
 constexpr int T0_SCRATCH = 160;  // u64 words of LDS scratch: sorted costs [64], masks [64], one counter per bisection step [32 x i32]
 constexpr int T0_EXTRA = 160;    // atoms learnt in round 1 (HBM, behind the root's)
@@ -154,16 +155,46 @@ __host__ __device__ inline int t0_area_bytes(int D) { return 8 * (2 * D + 2 + 2 
 // the optimum, so the counting argument is the same: 1.2-1.8x the true gap instead of 1.7-3.5x.
 // `scratchWords`: u64 words of LDS available (the fresh list's gains); candidates beyond it are dropped (fewer known
 // assignments: a looser bound, still a bound).
-template <int NW>
-__device__ __attribute__((noinline)) void apriori_threshold(u64 *scratch, const u64 *atoms, double *t0Out, int D, int k,
-                                                            int phase, int scratchWords)
+// The triples of 16 and the quadruples of 8 as lists (4 / 3 bits per member, ascending), so that a thread holds combinations and not
+// the empty places of a 16^3 / 8^4 grid (six in seven of the grid's places were empty: 19 values per thread at 12 waves, now 5)
+struct T0Combos { unsigned short tri[560], quad[70]; };
+constexpr T0Combos t0_combos()
 {
-    constexpr int NT = NW * 64, SLOTS = (4096 + NT - 1) / NT;  // NW >= 8: at most 8 grid slots per thread and kind
+    T0Combos t{};
+    int n = 0;
+    for (int i = 0; i < 16; i++)
+        for (int j = i + 1; j < 16; j++)
+            for (int l = j + 1; l < 16; l++) t.tri[n++] = (unsigned short)(i | (j << 4) | (l << 8));
+    n = 0;
+    for (int i = 0; i < 8; i++)
+        for (int j = i + 1; j < 8; j++)
+            for (int l = j + 1; l < 8; l++)
+                for (int q = l + 1; q < 8; q++) t.quad[n++] = (unsigned short)(i | (j << 3) | (l << 6) | (q << 9));
+    return t;
+}
+__constant__ const T0Combos T0_COMBOS = t0_combos();
+// (LDS pointers are passed as such: through generic ones a function that is not inlined reads and writes LDS with FLAT instructions)
+typedef __attribute__((address_space(3))) u64 lds_u64;
+typedef __attribute__((address_space(3))) double lds_f64;
+typedef __attribute__((address_space(3))) int lds_i32;
+__device__ __forceinline__ int lds_add(lds_i32 *p, int x) { return __hip_atomic_fetch_add(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+constexpr int T0_RANKS = 256;  // phase 1: candidates ranked at most (their rank sums lie under the sorted atoms: 128 words)
+template <int NW>
+__device__ __attribute__((noinline)) void apriori_threshold(lds_u64 *scratch, const u64 *atoms, lds_f64 *t0Out, int D, int k, int phase,
+                                                            int scratchWords)
+{
+    // the known assignments, dealt to the threads: 2 016 pairs (in a list of 2 048 places), 560 triples, 64 singles + 70 quadruples
+    constexpr int NT = NW * 64, PSL = (2048 + NT - 1) / NT, TSL = (560 + NT - 1) / NT, QSL = (134 + NT - 1) / NT;
+    constexpr int NV = PSL + TSL + QSL;                                       // NW >= 8: at most 7 per thread
+    constexpr int NBITS = NV < 8 ? 3 : (NV < 16 ? 4 : (NV < 32 ? 5 : 6));     // bits of a thread's count
+    static_assert(NT >= T0_RANKS || NW < 8, "one candidate per thread in the rank pass");
     const double INF = d_inf();
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    double *sd = reinterpret_cast<double *>(scratch);  // atoms sorted by cost
-    u64 *sm = scratch + 64;                            // their row masks
-    int *cnt = reinterpret_cast<int *>(scratch + 128);
+    lds_f64 *sd = reinterpret_cast<lds_f64 *>(scratch);  // atoms sorted by cost
+    lds_u64 *sm = scratch + 64;                          // their row masks
+    lds_i32 *cnt = reinterpret_cast<lds_i32 *>(scratch + 128);
+    lds_i32 *rk = reinterpret_cast<lds_i32 *>(scratch);  // phase 1: the candidates' ranks, summed over the waves (under sd / sm, before they are filled)
+    lds_i32 *hist = reinterpret_cast<lds_i32 *>(scratch);  // the refinement's histogram (over sd / sm, once every thread holds its sums)
     const double gRoot = __longlong_as_double((long long)atoms[2 * D]);
     if (phase == 0) {
         if (wave == 0) {
@@ -179,39 +210,58 @@ __device__ __attribute__((noinline)) void apriori_threshold(u64 *scratch, const 
         }
     } else {
         // candidates: every atom that can still matter (cost below the current threshold's gap), compacted into LDS
-        double *cd = reinterpret_cast<double *>(scratch + T0_SCRATCH);
-        const int candCap = (scratchWords - T0_SCRATCH) / 2;
-        u64 *cm = scratch + T0_SCRATCH + candCap;
-        int *ncand = reinterpret_cast<int *>(scratch + 144);
+        lds_f64 *cd = reinterpret_cast<lds_f64 *>(scratch + T0_SCRATCH);
+        int candCap = (scratchWords - T0_SCRATCH) / 2;
+        candCap = candCap > T0_RANKS ? T0_RANKS : candCap;
+        lds_u64 *cm = scratch + T0_SCRATCH + candCap;
+        lds_i32 *ncand = reinterpret_cast<lds_i32 *>(scratch + 144);
         const double capGap = *t0Out - gRoot;  // (+inf when there is no threshold yet)
         // (the counter is bumped by L2 atomics; a plain load that hit a line cached before them could only read a SMALLER
         //  count -- fewer atoms, a looser bound, still a bound; the atoms themselves are plain stores of this workgroup's
         //  waves, coherent through the CU's vector L1)
         int nExtra = (int)(unsigned)atoms[2 * D + 1];
         nExtra = nExtra > T0_EXTRA ? T0_EXTRA : nExtra;
-        if (tid < 64) { sd[tid] = INF; sm[tid] = 0ull; }
+        for (int i = tid; i < T0_RANKS; i += NT) rk[i] = 0;
         if (tid == 0) *ncand = 0;
         __syncthreads();
         for (int i = tid; i < D + nExtra; i += NT) {
             const int w = i < D ? 2 * i : 2 * D + 2 + 2 * (i - D);
             const double dl = __longlong_as_double((long long)atoms[w]);
             if (dl < INF && dl <= capGap) {
-                const int pos = atomicAdd(ncand, 1);
+                const int pos = lds_add(ncand, 1);
                 if (pos < candCap) { cd[pos] = dl; cm[pos] = atoms[w + 1]; }
             }
         }
         __syncthreads();
         int nc = *ncand;
-        nc = nc > candCap ? candCap : nc;
-        for (int i = tid; i < nc; i += NT) {  // the 64 cheapest, sorted (ties by position)
-            const double dl = cd[i];
-            int rank = 0;
-            for (int j = 0; j < nc; j++) {
-                const double dj = cd[j];
-                rank += (dj < dl || (dj == dl && j < i)) ? 1 : 0;
+        nc = __builtin_amdgcn_readfirstlane(nc > candCap ? candCap : nc);
+        // the 64 cheapest, sorted (ties by position).  Rank of candidate i = the candidates in front of it, counted by several
+        // waves at once: wave w takes the candidates 64 g .. 64 g + 63 (g = w mod G, one per lane) against one share of the
+        // others, and the shares are summed in LDS (one wave walking all of them was the longest part of this call).
+        const int G = (nc + 63) >> 6;  // <= candCap / 64 + 1 <= NW / 2
+        if (G > 0) {
+            const int g = wave % G, part = wave / G, parts = NW / G;
+            const int chunk = (nc + parts - 1) / parts;
+            const int i = g * 64 + lane;
+            if (part < parts && i < nc) {
+                const double dl = cd[i];
+                const int j1 = (part + 1) * chunk < nc ? (part + 1) * chunk : nc;
+                int rank = 0;
+                for (int j = part * chunk; j < j1; j++) {
+                    const double dj = cd[j];
+                    rank += (dj < dl || (dj == dl && j < i)) ? 1 : 0;
+                }
+                if (rank) lds_add(&rk[i], rank);
             }
-            if (rank < 64) { sd[rank] = dl; sm[rank] = cm[i]; }
         }
+        __syncthreads();
+        int rank = 64;
+        double dl = INF;
+        u64 ml = 0ull;
+        if (tid < nc) { rank = rk[tid]; dl = cd[tid]; ml = cm[tid]; }
+        __syncthreads();  // every rank is read: sd / sm take the ranks' place
+        if (rank < 64) { sd[rank] = dl; sm[rank] = ml; }
+        if (tid >= nc && tid < 64) { sd[tid] = INF; sm[tid] = 0ull; }  // (the ranks are a permutation: places nc .. 63 are the empty ones)
     }
     if (tid < 32) cnt[tid] = 0;
     __syncthreads();
@@ -221,66 +271,124 @@ __device__ __attribute__((noinline)) void apriori_threshold(u64 *scratch, const 
     // DOWN: a combination is counted only if it really is <= x, so the count can only be too small and the x at which it
     // reaches k - 1 is still an upper bound of the (k-1)-th smallest (half the registers of fp64 values: the function fits the
     // caller-saved registers and needs no stack).
-    float val[3 * SLOTS + 1];
-    val[3 * SLOTS] = __double2float_ru(tid < 64 ? sd[tid] : INF);  // singles
+    float val[NV];
 #pragma unroll
-    for (int e = 0; e < SLOTS; e++) {
+    for (int e = 0; e < PSL; e++) {  // pairs of all atoms: row q of the list holds the pairs (q, .) and, behind them, the pairs (62 - q, .)
+        const int idx = tid + e * NT, q = idx >> 6, c = idx & 63;
+        const bool own = c < 63 - q;
+        const int i = own ? q : 62 - q, j = own ? q + 1 + c : c;
+        double x = INF;
+        if ((q < 31 || (q == 31 && own)) && j < nA && (sm[i] & sm[j]) == 0ull) x = sd[i] + sd[j];
+        val[e] = __double2float_ru(x);
+    }
+#pragma unroll
+    for (int e = 0; e < TSL; e++) {  // triples of the 16 cheapest
         const int idx = tid + e * NT;
-        {   // pairs of all atoms
-            const int i = idx >> 6, j = idx & 63;
-            double x = INF;
-            if (idx < 4096 && i < j && j < nA && (sm[i] & sm[j]) == 0ull) x = sd[i] + sd[j];
-            val[e] = __double2float_ru(x);
-        }
-        {   // triples of the 16 cheapest
-            const int i = idx >> 8, j = (idx >> 4) & 15, l = idx & 15;
-            double x = INF;
-            if (idx < 4096 && i < j && j < l && l < nA) {
+        double x = INF;
+        if (idx < 560) {
+            const int t = T0_COMBOS.tri[idx], i = t & 15, j = (t >> 4) & 15, l = t >> 8;
+            if (l < nA) {
                 const u64 mi = sm[i], mj = sm[j], ml = sm[l];
                 if (((mi & mj) | (mi & ml) | (mj & ml)) == 0ull) x = (sd[i] + sd[j]) + sd[l];
             }
-            val[SLOTS + e] = __double2float_ru(x);
         }
-        {   // quadruples of the 8 cheapest
-            const int i = idx >> 9, j = (idx >> 6) & 7, l = (idx >> 3) & 7, q = idx & 7;
-            double x = INF;
-            if (idx < 4096 && i < j && j < l && l < q && q < nA) {
+        val[PSL + e] = __double2float_ru(x);
+    }
+#pragma unroll
+    for (int e = 0; e < QSL; e++) {  // singles, and quadruples of the 8 cheapest
+        const int idx = tid + e * NT;
+        double x = INF;
+        if (idx < 64) x = sd[idx];
+        else if (idx < 64 + 70) {
+            const int t = T0_COMBOS.quad[idx - 64], i = t & 7, j = (t >> 3) & 7, l = (t >> 6) & 7, q = t >> 9;
+            if (q < nA) {
                 const u64 mi = sm[i], mj = sm[j], ml = sm[l], mq = sm[q];
                 if (((mi & mj) | (mi & ml) | (mi & mq) | (mj & ml) | (mj & mq) | (ml & mq)) == 0ull)
                     x = ((sd[i] + sd[j]) + sd[l]) + sd[q];
             }
-            val[2 * SLOTS + e] = __double2float_ru(x);
         }
+        val[PSL + TSL + e] = __double2float_ru(x);
     }
     auto total_le = [&](double x, int step) -> int {  // block-wide number of combinations <= x (one barrier); never too large
         const float xf = __double2float_rd(x);
         int n = 0;
 #pragma unroll
-        for (int e = 0; e <= 3 * SLOTS; e++) n += (val[e] <= xf) ? 1 : 0;
+        for (int e = 0; e < NV; e++) n += (val[e] <= xf) ? 1 : 0;
         int w = 0;
 #pragma unroll
-        for (int bit = 0; bit < 5; bit++) w += __popcll(__ballot((n >> bit) & 1)) << bit;  // n <= 25
-        if (lane == 0 && w) atomicAdd(&cnt[step], w);
+        for (int bit = 0; bit < NBITS; bit++) w += __popcll(__ballot((n >> bit) & 1)) << bit;
+        if (lane == 0 && w) lds_add(&cnt[step], w);
         __syncthreads();
         return __builtin_amdgcn_readfirstlane(cnt[step]);
     };
     // bracket: the answer is of the order of the cheapest atoms' sums -- start at twice the 16th cheapest atom and double
-    // until k - 1 combinations are below (every single and every pair is <= twice the dearest atom), then 8 bisections
+    // until k - 1 combinations are below (every single and every pair is <= twice the dearest atom)
     const double top = 2.0 * sd[nA - 1];
     double hi = 2.0 * sd[nA > 16 ? 15 : nA - 1], lo = 0.0;
-    int step = 0;
+    int step = 0, nLo = 0;  // nLo: combinations counted at or below lo
     for (;;) {
         if (hi > top) hi = top;
-        if (total_le(hi, step++) >= k - 1) break;
+        const int n = total_le(hi, step++);
+        if (n >= k - 1) break;
         if (hi >= top || step >= 12) return;  // fewer than k - 1 known assignments: no threshold (uniform)
         lo = hi;
+        nLo = n;
         hi = 2.0 * hi;
     }
-    for (int it = 0; it < 8; it++) {
-        const double mid = 0.5 * (lo + hi);
-        if (total_le(mid, step++) >= k - 1) hi = mid; else lo = mid;
+    // refinement, in ONE pass and one barrier where eight bisections took eight: every sum in (lo, hi] is dropped into one of
+    // 256 equal bins of the bracket (a histogram in LDS, over the sorted atoms, which every thread is done with behind the
+    // bracket's first barrier), and wave 0 walks the bins to the one where the count reaches k - 1.  The bin of a sum s is
+    // b(s) = trunc(fl(fl(s - lo') * r)) in fp32, lo' = lo rounded down and r = fl(256 / (hi' - lo')): each operation is monotone
+    // and has a relative error of at most 2^-24, so b(s) <= b implies s < lo' + (b + 1) / r * (1 + 2^-22), and that value -- taken
+    // with 2^-21, in fp64 -- bounds every sum counted up to bin b.  (Sums above hi' are not counted, as in the bracket; a
+    // bracket too narrow for fp32 is left as it is.)
+    const float lof = __double2float_rd(lo), hif = __double2float_rd(hi);
+    const float r = 256.0f / (hif - lof);
+    if (!(hif - lof >= 1e-30f)) {  // (uniform)
+        if (tid == 0 && gRoot + hi < *t0Out) *t0Out = gRoot + hi;
+        return;
     }
-    if (tid == 0 && gRoot + hi < *t0Out) *t0Out = gRoot + hi;
+    for (int i = tid; i < 256; i += NT) hist[i] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < NV; e++) {
+        const float s = val[e];
+        if (s > lof && s <= hif) lds_add(&hist[(int)fminf((s - lof) * r, 255.0f)], 1);
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    // wave 0: lane l holds bins 4 l .. 4 l + 3; inclusive prefix sums over the lanes, then the first bin at which nLo + prefix >= k - 1
+    // (there is one: the bracket's upper end counted k - 1 and every sum it counted has a bin)
+    const int hx = hist[4 * lane], hy = hist[4 * lane + 1], hz = hist[4 * lane + 2], hw = hist[4 * lane + 3];
+    const int own = (hx + hy) + (hz + hw);
+    int inc = own;
+    inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xF, 0xF, true);  // row_shr:1
+    inc += __builtin_amdgcn_update_dpp(0, inc, 0x112, 0xF, 0xF, true);  // row_shr:2
+    inc += __builtin_amdgcn_update_dpp(0, inc, 0x114, 0xF, 0xF, true);  // row_shr:4
+    inc += __builtin_amdgcn_update_dpp(0, inc, 0x118, 0xF, 0xF, true);  // row_shr:8
+    inc += __builtin_amdgcn_update_dpp(0, inc, 0x142, 0xA, 0xF, false);  // row_bcast:15 -> rows 1, 3
+    inc += __builtin_amdgcn_update_dpp(0, inc, 0x143, 0xC, 0xF, false);  // row_bcast:31 -> rows 2, 3
+    const int need = k - 1 - nLo;  // >= 1
+    const u64 reached = __ballot(inc >= need);
+    double bound = hi;
+    if (reached) {
+        const int l = __builtin_ctzll(reached);
+        int c = __builtin_amdgcn_readlane(inc - own, l) + __builtin_amdgcn_readlane(hx, l);  // sums up to lane l's first bin
+        int bin = 4 * l;
+        if (c < need) {
+            c += __builtin_amdgcn_readlane(hy, l);
+            bin++;
+            if (c < need) {
+                c += __builtin_amdgcn_readlane(hz, l);
+                bin += (c < need) ? 2 : 1;
+            }
+        }
+        if (bin < 255) {
+            const double up = (double)lof + ((double)(bin + 1) * (1.0 / (double)r)) * (1.0 + 0x1p-21);
+            bound = up < hi ? up : hi;
+        }
+    }
+    if (tid == 0 && gRoot + bound < *t0Out) *t0Out = gRoot + bound;
 }
 
 // pool entry: gain (fp64), meta (u32: column | parent state << 8 | flags), own state slot (u16)
@@ -872,15 +980,15 @@ __global__ void __launch_bounds__(NW * 64, min_waves_per_simd(NW)) kbest_kernel(
         KB_T(tRound);
         KB_ACC(7, 1);  // [7] rounds
         if ((t0On && roundNo == 1) || (t1On && roundNo == 2)) {
-            apriori_threshold<NW>(lbKey, atoms, &ctrl->t0, D, k, roundNo - 1, spec * 64);
+            apriori_threshold<NW>((lds_u64 *)lbKey, atoms, (lds_f64 *)&ctrl->t0, D, k, roundNo - 1, spec * 64);
 #ifdef KB_T0_DEBUG
             __syncthreads();
             if (tid == 0 && b < 4) printf("T0DBG b=%d round=%d t0gap=%.6f poolT=%.6f nOld=%d extra=%d\n", b, roundNo, ctrl->t0 - __longlong_as_double((long long)atoms[2 * D]),
                                           (ctrl->nq - ctrl->head >= k - ctrl->emitted) ? PG[ctrl->head + k - ctrl->emitted - 1] - __longlong_as_double((long long)atoms[2 * D]) : -1.0, ctrl->nq - ctrl->head, (int)atoms[2 * D + 1]);
 #endif
             // Every wave must have LEFT the function before its scratch is re-armed: the waves return one by one (behind the
-            // function's last barrier each still reads the sorted atoms / the counters, through FLAT loads -- the function is
-            // not inlined and takes generic pointers), and a wave that re-armed the minima under a slower one's reads gave
+            // function's last barrier wave 0 still reads the histogram, and before round 7 every wave read the counters there),
+            // and a wave that re-armed the minima under a slower one's reads gave
             // that wave another view of them.  Found in round 5 by the soak of 2-column frames at k = 1 025 (the first k
             // beyond the fused kernel once every launch enumerates k + 1): one problem in ten thousand came back with nf = 2;
             // with this barrier none in 560 000 (tests/test_gpu_round5.py::test_apriori_threshold_scratch_is_not_rearmed_early).
@@ -888,6 +996,9 @@ __global__ void __launch_bounds__(NW * 64, min_waves_per_simd(NW)) kbest_kernel(
             for (int i = tid; i < spec * 64; i += NT) lbKey[i] = ~0ull;  // re-arm the filter minima
             __syncthreads();
         }
+#ifdef KB_PROFILE_T0
+        KB_T(tThr);
+#endif
         // control values come out of LDS in VGPRs: readfirstlane makes them provably wave-uniform, so every
         // loop below is scalar-controlled.  They are only rewritten in D, behind a barrier.
         const int nsel = uni32(ctrl->nsel);
@@ -941,7 +1052,11 @@ __global__ void __launch_bounds__(NW * 64, min_waves_per_simd(NW)) kbest_kernel(
         // (the optimistic bounds of this round's nodes were set when they were selected: opt->bAbs[w], struct Opt)
         const bool optAny = optOn && uni32(opt->anyFinite) != 0;
         KB_T(tF0);
-        KB_ACC(14, tF0 - tRound);  // [14] round prologue (control reads)
+#ifdef KB_PROFILE_T0
+        KB_ACC(14, tThr - tRound);  // (make PROFILE=1 VARIANT=.. EXTRA=-DKB_PROFILE_T0: [14] is the a-priori threshold block alone)
+#else
+        KB_ACC(14, tF0 - tRound);  // [14] round prologue: the a-priori threshold (rounds 1 and 2) + the control reads
+#endif
         int myNode = -1, myParts = 1;  // the node whose filter this wave took part in
         {
             // all NW waves take part: node = wave % nsel, and the waves of one node split its columns j.
@@ -1421,11 +1536,9 @@ __global__ void __launch_bounds__(NW * 64, min_waves_per_simd(NW)) kbest_kernel(
         if (budget > spec) budget = spec;
         if (budget < 1) budget = 1;
         int mySel = -1, mySid = 0, nselNew = 0, nLazy = 0;
-        constexpr int MS = (NW >= 16) ? 16 : (NW >= 12 ? 12 : 8);  // candidates split per round at most
-        int sIdx[MS], sSid[MS];
-#pragma unroll
-        for (int w = 0; w < MS; w++) { sIdx[w] = -1; sSid[w] = 0; }
-        // wave 0 walks the whole selection (it writes the control block); wave w only as far as its own, the w-th
+        int sidFirst = 0;  // state slot of the first selected CANDIDATE (the selection rank behind the tickets'), 0 when there is none
+        // wave 0 walks the whole selection (one lane of it writes ctrl->selIdx / selSid as it goes: the next round reads them behind
+        // this phase's barrier); wave w only as far as its own, the w-th
         const int walk = (wave == 0 || budget <= wave) ? budget : wave + 1;
         int firstOpen = -1;  // pool index of the first candidate that has not been split
         // the candidates: selection ranks rank0, rank0 + 1, ... go to the first open entries of the pool, in pool order
@@ -1444,10 +1557,8 @@ __global__ void __launch_bounds__(NW * 64, min_waves_per_simd(NW)) kbest_kernel(
                     const bool lazy = (lazyM >> bitpos) & 1ull;
                     const int sidv = lazy ? sidBase + nLazy : __builtin_amdgcn_readlane((int)ps, bitpos);
                     if (nselNew == wave) { mySel = base + bitpos; mySid = sidv; }
-                    if (wave == 0) {
-#pragma unroll
-                        for (int w = 0; w < MS; w++) if (w == nselNew) { sIdx[w] = base + bitpos; sSid[w] = sidv; }
-                    }
+                    if (nselNew == rank0) sidFirst = sidv;
+                    if (wave == 0 && lane == 0) { ctrl->selIdx[nselNew] = (short)(base + bitpos); ctrl->selSid[nselNew] = (unsigned short)sidv; }
                     nLazy += lazy ? 1 : 0;
                     nselNew++;
                     m &= m - 1;
@@ -1468,14 +1579,10 @@ __global__ void __launch_bounds__(NW * 64, min_waves_per_simd(NW)) kbest_kernel(
             tSel = tSel > budget ? budget : tSel;
             if (tSel > 0) {
                 mySel = -1;
-#pragma unroll
-                for (int w = 0; w < MS; w++) { sIdx[w] = -1; sSid[w] = 0; }
-                walk_candidates(tSel);
+                sidFirst = 0;
+                walk_candidates(tSel);  // (rewrites the entries from tSel on)
                 if (wave < tSel) { mySel = -1; mySid = uni32((int)opt->TS[wave]); }
-                if (wave == 0) {
-#pragma unroll
-                    for (int w = 0; w < MS; w++) if (w < tSel) { sIdx[w] = -1; sSid[w] = uni32((int)opt->TS[w]); }
-                }
+                if (wave == 0 && lane < tSel) { ctrl->selIdx[lane] = -1; ctrl->selSid[lane] = opt->TS[lane]; }
             }
         }
         const bool myTicket = wave < tSel;
@@ -1536,9 +1643,6 @@ __global__ void __launch_bounds__(NW * 64, min_waves_per_simd(NW)) kbest_kernel(
             int e = emitted, h = 0, stop = 0;
             const double cdel = ctrl->cdelta, g0u = ctrl->gain0u;
             const double tMin = nTl > 0 ? opt->TK[0] : INF;  // emission stops at the smallest ticket key (struct Opt)
-            int sidFirst = sSid[0];                          // state slot of the first selected CANDIDATE (rank tSel)
-#pragma unroll
-            for (int w = 1; w < MS; w++) sidFirst = (w == tSel) ? sSid[w] : sidFirst;
             bool more = true;
             for (int base = 0; more && base < nq && e < k; base += 64) {
                 const int i = base + lane;
@@ -1593,8 +1697,6 @@ __global__ void __launch_bounds__(NW * 64, min_waves_per_simd(NW)) kbest_kernel(
                 ctrl->outTicket = 0;
                 ctrl->nq = nq;
                 ctrl->head = h;
-#pragma unroll
-                for (int w = 0; w < MS; w++) { ctrl->selIdx[w] = (short)sIdx[w]; ctrl->selSid[w] = (unsigned short)sSid[w]; }
                 if (stop) ctrl->stop = 1;
                 else if (RELAY && e >= ctrl->relayCut) ctrl->stop = 4;  // relay: this piece's share is out -- the round ends as usual, the loop with it
             }
