@@ -22,6 +22,8 @@
  *        getAssignmentProbs chain behind it
  *   kbest_bb_match_batch_f64
  *        batched form of  asgnBB (assignment.cpp:724-797; k = 1, maximize)
+ *   kbest_permanent_probs_batch_f64 / kbest_permanent_probs_batch_f64_dev
+ *        batched form of  permanentProb (assignment.h:13, assignment.cpp:145-290), exact for every permOpt
  *
  * Conventions kept from the reference: cost matrices are column-major
  * C[row + col*numRow] with numRow >= numCol (shortestPathCPP.hpp:185-190);
@@ -347,6 +349,41 @@ int kbest_assoc_probs_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawRow, int ma
                                     const int64_t *d_costOff, int k, int condition, double *d_probs,
                                     const int64_t *d_probOff, int32_t *d_nf, void *stream);
 int kbest_reserve_assoc(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, int k);
+
+/*
+ * Batched permanentProb (assignment.h:13, assignment.cpp:145-290) for every permOpt: the EXACT association probabilities, as
+ * ratios of matrix permanents (kbest_perm.hip: sums over column subsets, every term non-negative; the reference's permOpt 0,
+ * Huber's sampling estimate, is answered exactly as well).  Layout of kbest_weights_batch_f64: frame b is an (nL+nM) x nM
+ * column-major block at costOff[b], probs [nM][nL+1] at probOff[b]; rows r >= nL are folded into slot nL.
+ * condition = 1: raw blocks, conditionCosts -> permanentProb -> scatter back (getAssignmentProbs with usePerm,
+ * assignment.cpp:57-74; landmarks conditionCosts drops get exactly 0.0).  perm (may be NULL): perm[b] = the permanent of the
+ * frame's toProbs matrix (after conditioning when asked for), i.e. the normaliser.  A frame whose permanent is 0 (a column
+ * without a finite entry, fewer usable rows than columns) comes back with all probabilities 0 and perm[b] = 0, not NaN.
+ * Limits: 1 <= nM <= KBEST_PERM_MAX_COLS (a product of one entry per column is at least exp(-42 * 16), still a normal double;
+ * beyond, the sums would lose small terms silently: KBEST_ERR_UNSUPPORTED), nL + nM <= KBEST_MAX_DIM_WIDE.  A frame's result
+ * does not depend on the batch it travels in, bit for bit.  Host buffers; stages, reserves and runs kbest_permanent_probs_batch_f64_dev.
+ */
+#define KBEST_PERM_MAX_COLS 16
+int kbest_permanent_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,
+                                    const int64_t *costOff, int condition, double *probs, const int64_t *probOff,
+                                    double *perm);
+/* The same on device buffers, asynchronous on `stream` (NULL: the context's): one launch, no allocation.  maxRawRow / maxCol:
+ * upper bounds of nL + nM / nM over the batch (a frame beyond them gets perm = 0 and its probs are left alone).  Needs
+ * kbest_reserve_permanent first (KBEST_ERR_NOT_RESERVED): frames whose subset layers do not fit LDS keep them in a work space
+ * in HBM, (maxRawRow + 2) * 2^maxCol * 8 bytes per frame IN FLIGHT (64 rows x 16 columns: 34 MB).  The launch has as many
+ * workgroups as the chip holds at a time and as frames fit the reserved work space (at most KBEST_PERM_WORK_CAP bytes, at least one frame) and each of them
+ * takes frame after frame: a large batch is processed in chunks of that many frames without a workgroup ever waiting for another. */
+#define KBEST_PERM_WORK_CAP ((size_t)1 << 30)
+int kbest_permanent_probs_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, const int32_t *d_nL,
+                                        const int32_t *d_nM, const double *d_cost, const int64_t *d_costOff,
+                                        int condition, double *d_probs, const int64_t *d_probOff, double *d_perm,
+                                        void *stream);
+int kbest_reserve_permanent(kbest_ctx *ctx, int B, int maxRawRow, int maxCol);
+/* Diagnostic, for tests: another cap of the permanent work space (bytes; 0: KBEST_PERM_WORK_CAP again).  A lower cap means
+ * fewer frames in flight -- smaller chunks -- and the same results bit for bit. */
+int kbest_set_permanent_work_cap(kbest_ctx *ctx, size_t bytes);
+/* Diagnostic, for tests: workgroups -- frames in flight -- of the context's last permanent launch (-1: null context). */
+int kbest_last_permanent_grid(kbest_ctx *ctx);
 /* on = 1: the HOST-buffer association entries of this context (kbest_weights / assoc_probs / bruteforce / quadric_assoc) enumerate
  * their k best in the REFERENCE's own order of operations (the reference-order kernel, as KBEST_FLAG_REFERENCE_ORDER does for
  * kbest_batch_f64): where exactly equal gains straddle slot k the assignments that are weighed are the ones the reference's

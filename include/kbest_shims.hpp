@@ -12,6 +12,7 @@
 //   toProbs        assignment.h:19               (callers: assignment.cpp:164)
 //   assignmentProb assignment.h:11               (callers: assignment.cpp:66, comparison.cpp:194-222)
 //   conditionCosts assignment.h:26               (callers: assignment.cpp:58, comparison.cpp:161)
+//   permanentProb  assignment.h:13               (callers: assignment.cpp:64, comparison.cpp:225, 233)
 //
 // MurtyHyp / ScratchSpace keep the reference's public member names, types and
 // declaration order (shortestPathCPP.hpp:22-65, 73-142) so that objects built
@@ -113,6 +114,12 @@ void toProbs(std::vector<double> &costMatrix);
 // assignment.h:26 (assignment.cpp:439-525)
 std::vector<double> conditionCosts(const std::vector<double> &costs, size_t nRows, size_t nCols,
                                    std::vector<ptrdiff_t> &rowIdxOut);
+
+// assignment.h:13 (assignment.cpp:145-290): the exact association probabilities as ratios of permanents, [nM][nL+1].  By value, as
+// the reference declares it.  permOpt 0 (Huber's sampling estimate), 1 (exact) and 2 (long double) all return the exact marginals
+// (kbest_permanent_probs_batch_f64: sums over column subsets, nM <= 16); any other value throws std::runtime_error
+// (assignment.cpp:344, 406).
+std::vector<std::vector<double>> permanentProb(std::vector<double> costMatrix, size_t nL, size_t nM, int permOpt);
 
 // Not in the reference: the engine context behind the functions above (created on first use, GPU 0), for the entries of
 // kbest_c.h that take one -- e.g. kbest_last_tie_flags after a call.

@@ -139,6 +139,9 @@ struct kbest_ctx {
     DevBufRaw splitBuf;       // per-share result tables + shared thresholds of the split
     DevBufRaw tieBuf;         // [B] fp64: gain of the solution behind the tables (exact ties, kbest_ties.h)
     DevBufRaw exactBuf;       // work space of the reference-order kernel (kbest_exact.hip)
+    DevBufRaw permBuf;        // work space of the permanent kernel (kbest_perm.hip): the subset layers that do not fit LDS
+    size_t permCap = KBEST_PERM_WORK_CAP;  // ... and its cap (kbest_set_permanent_work_cap)
+    int permLastGrid = 0;     // workgroups (frames in flight) of the last permanent launch (kbest_last_permanent_grid)
     DevBufRaw relayBuf;       // relay launches of the 64-row kernel: [B] LDS images (kbest_engine.hip)
     DevBufRaw relayFlags;     // ... and three words per matrix: claimed / done / gone (zeroed when the buffer is made, put back to zero by every launch)
     long long relayLaunches = 0;  // relay launches made (kbest_relay_launches)
@@ -486,6 +489,7 @@ int kbest_destroy(kbest_ctx *ctx)
     if (ctx->tieBuf.p) (void)hipFree(ctx->tieBuf.p);
     if (ctx->relayBuf.p) (void)hipFree(ctx->relayBuf.p);
     if (ctx->exactBuf.p) (void)hipFree(ctx->exactBuf.p);
+    if (ctx->permBuf.p) (void)hipFree(ctx->permBuf.p);
     if (ctx->relayFlags.p) (void)hipFree(ctx->relayFlags.p);
     if (ctx->lastEvent) (void)hipEventDestroy(ctx->lastEvent);
     for (auto &a : ctx->aux)
@@ -2612,6 +2616,162 @@ extern "C" int kbest_reserve_assoc(kbest_ctx *ctx, int B, int maxRawRow, int max
         return fail(ctx, KBEST_ERR_UNSUPPORTED, "kbest_reserve_assoc: frames beyond the fused association kernel");
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     return ensure_states(ctx, small_states_need_upto(ctx, B, capRow, maxCol, k, true), true);
+}
+
+// ---- permanentProb (kbest_perm.hip) ------------------------------------------------------------------------------------------
+// Workgroups of a launch = frames in flight: as many as the batch has, as the chip holds at a time (the kernel's 105 VGPRs give
+// 4 waves per SIMD, 16 per CU; its LDS the rest), and as have a slice of the work space under the cap (at least one).
+static int perm_grid(const kbest_ctx *ctx, const kb::PermPlan &pl, int B, size_t bytes)
+{
+    long long g = B;
+    int perCU = 16 / (pl.threads / 64);
+    if (pl.lds > 0 && perCU > ctx->ldsPerCU / pl.lds) perCU = ctx->ldsPerCU / pl.lds;
+    if (perCU < 1) perCU = 1;
+    const long long resident = (long long)ctx->nCU * perCU;
+    if (g > resident) g = resident;
+    if (pl.slotDoubles > 0) {
+        const size_t cap = bytes < ctx->permCap ? bytes : ctx->permCap;
+        long long fit = (long long)(cap / ((size_t)pl.slotDoubles * 8));
+        if (fit < 1) fit = 1;
+        if (g > fit) g = fit;
+    }
+    return (int)g;
+}
+
+static int perm_check_shape(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, const char *who)
+{
+    if (B < 0 || maxCol < 1 || maxRawRow < maxCol) return fail(ctx, KBEST_ERR_BAD_ARG, (std::string(who) + ": bad argument").c_str());
+    if (maxCol > KBEST_PERM_MAX_COLS)
+        return fail(ctx, KBEST_ERR_UNSUPPORTED, (std::string(who) + ": more than KBEST_PERM_MAX_COLS = 16 measurements in a frame (the exact "
+                                                 "sums over column subsets stop there: products of 17 gated entries leave the normal doubles)").c_str());
+    if (maxRawRow > KBEST_MAX_DIM_WIDE)
+        return fail(ctx, KBEST_ERR_UNSUPPORTED, (std::string(who) + ": more than KBEST_MAX_DIM_WIDE = 1024 rows (nL + nM) in a frame").c_str());
+    return KBEST_OK;
+}
+
+extern "C" int kbest_set_permanent_work_cap(kbest_ctx *ctx, size_t bytes)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    ctx->permCap = bytes ? bytes : KBEST_PERM_WORK_CAP;
+    return KBEST_OK;
+}
+
+extern "C" int kbest_reserve_permanent(kbest_ctx *ctx, int B, int maxRawRow, int maxCol)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    int rc = perm_check_shape(ctx, B, maxRawRow, maxCol, "kbest_reserve_permanent");
+    if (rc != KBEST_OK || B == 0) return rc;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const kb::PermPlan pl = kb::perm_plan(maxRawRow, maxCol, ctx->ldsLimit, ctx->ldsPerCU);
+    if (pl.slotDoubles == 0) return KBEST_OK;
+    const size_t slot = (size_t)pl.slotDoubles * 8;
+    const int g = perm_grid(ctx, pl, B, (size_t)-1);
+    return raw_reserve(ctx, ctx->permBuf, slot * (size_t)g);
+}
+
+extern "C" int kbest_permanent_probs_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, const int32_t *d_nL,
+                                                   const int32_t *d_nM, const double *d_cost, const int64_t *d_costOff,
+                                                   int condition, double *d_probs, const int64_t *d_probOff, double *d_perm,
+                                                   void *stream)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    int rc = perm_check_shape(ctx, B, maxRawRow, maxCol, "kbest_permanent_probs_batch_f64_dev");
+    if (rc != KBEST_OK) return rc;
+    if (!d_nL || !d_nM || !d_cost || !d_costOff || !d_probs || !d_probOff)
+        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_permanent_probs_batch_f64_dev: bad argument");
+    if (B == 0) return KBEST_OK;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const kb::PermPlan pl = kb::perm_plan(maxRawRow, maxCol, ctx->ldsLimit, ctx->ldsPerCU);
+    if (pl.slotDoubles > 0 && ctx->permBuf.bytes < (size_t)pl.slotDoubles * 8)  // asynchronous entry: never allocates
+        return fail(ctx, KBEST_ERR_NOT_RESERVED, "kbest_permanent_probs_batch_f64_dev: call kbest_reserve_permanent first");
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = order_behind_last(ctx, s);  // (one work space per context)
+    if (rc != KBEST_OK) return rc;
+    const Launched mark{ctx, s};
+    kb::PermParams pp;
+    pp.cost = d_cost;
+    pp.costOff = reinterpret_cast<const long long *>(d_costOff);
+    pp.probOff = reinterpret_cast<const long long *>(d_probOff);
+    pp.nL = d_nL;
+    pp.nM = d_nM;
+    pp.probs = d_probs;
+    pp.perm = d_perm;
+    pp.work = static_cast<double *>(ctx->permBuf.p);
+    pp.slotStride = pl.slotDoubles;
+    pp.B = B;
+    pp.maxRawRow = maxRawRow;
+    pp.maxCol = maxCol;
+    pp.condition = condition ? 1 : 0;
+    ctx->permLastGrid = perm_grid(ctx, pl, B, ctx->permBuf.bytes);
+    const hipError_t e = kb::launch_kbest_perm(pp, pl, ctx->permLastGrid, s);
+    if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "permanent kernel launch", e);
+    return KBEST_OK;
+}
+
+extern "C" int kbest_last_permanent_grid(kbest_ctx *ctx)
+{
+    if (!ctx) return -1;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    return ctx->permLastGrid;
+}
+
+extern "C" int kbest_permanent_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,
+                                               const int64_t *costOff, int condition, double *probs, const int64_t *probOff,
+                                               double *perm)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    if (B < 0 || (B > 0 && (!nL || !nM || !cost || !costOff || !probs || !probOff)))
+        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_permanent_probs_batch_f64: bad argument");
+    if (B == 0) return KBEST_OK;
+    int maxRawRow = 1, maxCol = 1;
+    size_t costN = 0, probN = 0;
+    for (int b = 0; b < B; b++) {
+        if (nL[b] < 0 || nM[b] < 1 || costOff[b] < 0 || probOff[b] < 0)
+            return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_permanent_probs_batch_f64: a frame with nL < 0, nM < 1 or a negative offset");
+        const long long nr = (long long)nL[b] + nM[b];
+        if (nr > maxRawRow) maxRawRow = nr > (1 << 30) ? (1 << 30) : (int)nr;
+        if (nM[b] > maxCol) maxCol = nM[b];
+        const size_t ce = (size_t)costOff[b] + (size_t)nr * (size_t)nM[b], pe = (size_t)probOff[b] + (size_t)nM[b] * ((size_t)nL[b] + 1);
+        if (ce > costN) costN = ce;
+        if (pe > probN) probN = pe;
+    }
+    int rc = perm_check_shape(ctx, B, maxRawRow, maxCol, "kbest_permanent_probs_batch_f64");
+    if (rc != KBEST_OK) return rc;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = kbest_reserve_permanent(ctx, B, maxRawRow, maxCol);
+    if (rc != KBEST_OK) return rc;
+    DevBuf dCost, dMeta, dProbs, dPerm;
+    // meta: costOff[B] | probOff[B] (int64) | nL[B] | nM[B] (int32)
+    std::vector<unsigned char> meta((size_t)B * 24);
+    memcpy(meta.data(), costOff, (size_t)B * 8);
+    memcpy(meta.data() + (size_t)B * 8, probOff, (size_t)B * 8);
+    memcpy(meta.data() + (size_t)B * 16, nL, (size_t)B * 4);
+    memcpy(meta.data() + (size_t)B * 20, nM, (size_t)B * 4);
+    hipError_t e;
+    if ((e = dCost.alloc(ctx, costN * 8)) != hipSuccess || (e = dMeta.alloc(ctx, meta.size())) != hipSuccess ||
+        (e = dProbs.alloc(ctx, probN * 8)) != hipSuccess || (e = dPerm.alloc(ctx, (size_t)B * 8)) != hipSuccess)
+        return fail(ctx, KBEST_ERR_NOMEM, "kbest_permanent_probs_batch_f64: device buffers", e);
+    HIP_TRY(ctx, hipMemcpy(dCost.p, cost, costN * 8, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(dMeta.p, meta.data(), meta.size(), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemsetAsync(dProbs.p, 0, probN * 8, ctx->stream));  // (gaps between the frames' slices come back as they went in: see below)
+    unsigned char *m8 = dMeta.as<unsigned char>();
+    rc = kbest_permanent_probs_batch_f64_dev(ctx, B, maxRawRow, maxCol, reinterpret_cast<const int32_t *>(m8 + (size_t)B * 16),
+                                             reinterpret_cast<const int32_t *>(m8 + (size_t)B * 20), dCost.as<double>(),
+                                             reinterpret_cast<const int64_t *>(m8), condition, dProbs.as<double>(),
+                                             reinterpret_cast<const int64_t *>(m8 + (size_t)B * 8), dPerm.as<double>(), nullptr);
+    if (rc != KBEST_OK) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    // every frame's own slice only: what lies between the slices in the caller's buffer is the caller's
+    std::vector<double> hp(probN);
+    HIP_TRY(ctx, hipMemcpy(hp.data(), dProbs.p, probN * 8, hipMemcpyDeviceToHost));
+    for (int b = 0; b < B; b++)
+        memcpy(probs + probOff[b], hp.data() + probOff[b], (size_t)nM[b] * ((size_t)nL[b] + 1) * 8);
+    if (perm) HIP_TRY(ctx, hipMemcpy(perm, dPerm.p, (size_t)B * 8, hipMemcpyDeviceToHost));
+    return KBEST_OK;
 }
 
 // tie (optional): [B] KBEST_TIE_* per frame.  tieExtra > 0: the general pipeline enumerates k + tieExtra solutions and weighs the

@@ -537,6 +537,26 @@ hipError_t launch_weights(const WeightParams &p, int B, hipStream_t stream);
 hipError_t launch_condition(const CondParams &p, int B, hipStream_t stream);
 hipError_t launch_to_probs(double *x, long long n, hipStream_t stream);
 
+// kbest_perm.hip: permanentProb, the exact association probabilities by sums over column subsets
+struct PermParams {
+    const double *cost;        // packed column-major (nL + nM) x nM blocks
+    const long long *costOff;  // [B]
+    const long long *probOff;  // [B]
+    const int *nL, *nM;        // [B]
+    double *probs;             // [nM][nL + 1] per frame
+    double *perm;              // [B] or nullptr: the permanent of the frame's toProbs matrix
+    double *work;              // work space: slotStride doubles per workgroup of the launch (modes 1, 2)
+    long long slotStride;
+    int B, maxRawRow, maxCol, condition;
+};
+struct PermPlan {
+    int mode;               // 0: every layer in LDS; 1: the forward layers in the work space; 2: everything there
+    int threads, lds;       // workgroup size, dynamic LDS bytes
+    long long slotDoubles;  // work space per workgroup
+};
+PermPlan perm_plan(int maxRawRow, int maxCol, int ldsLimit, int ldsPerCU);
+hipError_t launch_kbest_perm(const PermParams &p, const PermPlan &pl, int grid, hipStream_t stream);
+
 }  // namespace kb
 
 // kbest_capi.cpp: completes the gain levels that straddle slot k in the caller's HOST tables (see there)

@@ -237,4 +237,20 @@ std::vector<std::vector<double>> bruteForceProb(const std::vector<double> &costM
     return probs;
 }
 
+std::vector<std::vector<double>> permanentProb(std::vector<double> costMatrix, size_t nL, size_t nM, int permOpt)
+{
+    // permOpt 0 (Huber's sampling estimate), 1 (exact) and 2 (long double) are all answered exactly; anything else is the
+    // reference's error (assignment.cpp:344, 406)
+    if (permOpt < 0 || permOpt > 2) throw std::runtime_error("Unknown permanent option passed!");
+    kbest_ctx *ctx = global_ctx();
+    const int32_t l = (int32_t)nL, m = (int32_t)nM;
+    const int64_t zero = 0;
+    std::vector<double> flat(nM * (nL + 1), 0.0);
+    check(ctx, kbest_permanent_probs_batch_f64(ctx, 1, &l, &m, costMatrix.data(), &zero, 0, flat.data(), &zero, nullptr));
+    std::vector<std::vector<double>> probs(nM, std::vector<double>(nL + 1, 0.0));
+    for (size_t c = 0; c < nM; c++)
+        for (size_t j = 0; j <= nL; j++) probs[c][j] = flat[c * (nL + 1) + j];
+    return probs;
+}
+
 kbest_ctx *kbest_shims_context() { return global_ctx(); }

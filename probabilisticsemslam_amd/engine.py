@@ -29,6 +29,7 @@ KBEST_TIE_CAP = 4096
 KBEST_MAX_DIM = 64        # rows handled by the LDS-resident kernel
 KBEST_MAX_DIM_WIDE = 1024  # rows of the general-size kernel (beyond KBEST_MAX_DIM)
 KBEST_MAX_DIM_EXACT = 16384  # rows handled at all (the reference-order kernel beyond KBEST_MAX_DIM_WIDE)
+KBEST_PERM_MAX_COLS = 16     # measurements per frame of the exact (permanent) association probabilities
 
 # every symbol include/kbest_c.h declares
 C_ABI_SYMBOLS = (
@@ -43,7 +44,8 @@ C_ABI_SYMBOLS = (
     "kbest_unregister_host_buffer", "kbest_multi_timeline", "kbest_last_tie_flags", "kbest_set_assoc_tie_flags_dev",
     "kbest_relay_launches", "kbest_merge_topk_i8_f64_dev", "kbest_merge_gains_f64_dev", "kbest_multi_exchange_bytes",
     "kbest_last_route", "kbest_resolve_ties_dev", "kbest_multi_last_tie_flags", "kbest_reserve_exact",
-    "kbest_set_reference_order",
+    "kbest_set_reference_order", "kbest_permanent_probs_batch_f64", "kbest_permanent_probs_batch_f64_dev",
+    "kbest_reserve_permanent", "kbest_set_permanent_work_cap", "kbest_last_permanent_grid",
 )
 KBEST_MULTI_STAMPS = 6
 KBEST_MULTI_BATCH, KBEST_MULTI_SUBTREE = 0, 1
@@ -138,6 +140,12 @@ def load_library():
     if hasattr(lib, "kbest_last_tie_flags"):
         lib.kbest_last_tie_flags.argtypes = [vp, i32p, C.c_int]
         lib.kbest_set_assoc_tie_flags_dev.argtypes = [vp, vp]
+    if hasattr(lib, "kbest_permanent_probs_batch_f64"):
+        lib.kbest_permanent_probs_batch_f64.argtypes = [vp, C.c_int, i32p, i32p, dp, i64p, C.c_int, dp, i64p, dp]
+        lib.kbest_permanent_probs_batch_f64_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int, i32p, i32p, dp, i64p, C.c_int, dp, i64p, dp, vp]
+        lib.kbest_reserve_permanent.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+        lib.kbest_set_permanent_work_cap.argtypes = [vp, C.c_size_t]
+        lib.kbest_last_permanent_grid.argtypes = [vp]
     lib.kbest_register_host_buffer.argtypes = [vp, vp, C.c_size_t]
     lib.kbest_unregister_host_buffer.argtypes = [vp, vp]
     _lib = lib
@@ -315,6 +323,38 @@ class KBestEngine:
         out = [probs[probOff[b]: probOff[b] + psizes[b]].reshape(int(nM[b]), int(nL[b]) + 1) for b in range(B)]
         return out, nf
 
+    def permanent_probs(self, costs, nL, nM, condition=False):
+        """Batched permanentProb (assignment.h:13): the EXACT association probabilities, nM <= 16 (kbest_perm.hip).  Packing as
+        weights(); condition=True: raw blocks, conditionCosts -> permanentProb -> scatter back (getAssignmentProbs with usePerm).
+        Returns (list of [nM, nL+1] arrays, perm[B]: the permanent of every frame's toProbs matrix, the normaliser)."""
+        nL = np.ascontiguousarray(nL, dtype=np.int32)
+        nM = np.ascontiguousarray(nM, dtype=np.int32)
+        B = len(nL)
+        sizes = [(int(nL[b]) + int(nM[b])) * int(nM[b]) for b in range(B)]
+        psizes = [int(nM[b]) * (int(nL[b]) + 1) for b in range(B)]
+        costOff = np.zeros(B, np.int64)
+        probOff = np.zeros(B, np.int64)
+        costOff[1:] = np.cumsum(sizes)[:-1]
+        probOff[1:] = np.cumsum(psizes)[:-1]
+        flat = np.concatenate([np.ascontiguousarray(c, dtype=np.float64).reshape(-1) for c in costs])
+        if flat.size != sum(sizes):
+            raise KBestError("permanent_probs: a cost block is not (nL + nM) x nM")
+        probs = np.zeros(int(sum(psizes)), np.float64)
+        perm = np.zeros(B, np.float64)
+        self._check(self.lib.kbest_permanent_probs_batch_f64(self.ctx, B, _ptr(nL), _ptr(nM), _ptr(flat), _ptr(costOff),
+                                                             int(bool(condition)), _ptr(probs), _ptr(probOff), _ptr(perm)))
+        out = [probs[probOff[b]: probOff[b] + psizes[b]].reshape(int(nM[b]), int(nL[b]) + 1) for b in range(B)]
+        return out, perm
+
+    def set_permanent_work_cap(self, nbytes=0):
+        """Diagnostic (kbest_set_permanent_work_cap): cap of the permanent work space in bytes, 0 = the default; a lower cap means
+        fewer frames in flight and the same results."""
+        self._check(self.lib.kbest_set_permanent_work_cap(self.ctx, int(nbytes)))
+
+    def last_permanent_grid(self):
+        """Diagnostic (kbest_last_permanent_grid): workgroups -- frames in flight -- of this context's last permanent launch."""
+        return int(self.lib.kbest_last_permanent_grid(self.ctx))
+
     @staticmethod
     def _pack_quadrics(frames):
         """frames: list of (landMean (nL,3), landCov (nL,3,3), measMean (nM,3), measCov (nM,3,3))."""
@@ -446,6 +486,22 @@ class KBestEngine:
                                                              dp(d_cost), dp(d_costOff), k, int(bool(condition)), dp(d_probs),
                                                              dp(d_probOff), dp(d_nf), C.c_void_p(stream) if stream else None))
 
+    def reserve_permanent(self, B, maxRawRow, maxCol):
+        self._check(self.lib.kbest_reserve_permanent(self.ctx, B, maxRawRow, maxCol))
+
+    def permanent_probs_dev(self, B, maxRawRow, maxCol, d_nL, d_nM, d_cost, d_costOff, d_probs, d_probOff, d_perm=None,
+                            condition=False, stream=None, reserve=True):
+        """kbest_permanent_probs_batch_f64_dev on torch CUDA tensors, asynchronous on `stream` (a raw hipStream_t integer): one
+        launch.  The work space is sized here (a no-op once it is large enough): the C entry never allocates.  reserve=False: the
+        caller has called reserve_permanent (timed loops: nothing but the C entry between two events)."""
+        def dp(t):
+            return None if t is None else C.c_void_p(t.data_ptr())
+        if reserve:
+            self.reserve_permanent(B, maxRawRow, maxCol)
+        self._check(self.lib.kbest_permanent_probs_batch_f64_dev(self.ctx, B, maxRawRow, maxCol, dp(d_nL), dp(d_nM), dp(d_cost),
+                                                                 dp(d_costOff), int(bool(condition)), dp(d_probs), dp(d_probOff),
+                                                                 dp(d_perm), C.c_void_p(stream) if stream else None))
+
 
 class KBestMulti:
     """Multi-device engine of include/kbest_c.h: one context per GPU in ONE process, contiguous block sharding, RCCL
@@ -549,4 +605,12 @@ def kBest2DCutoff(k, numRow, numCol, maximize, C_, cutoff):
 def assignmentProb(costMatrix, nL, nM, k):
     """assignment.h:11.  Returns probs[nM][nL+1]."""
     out, _ = _engine().weights([costMatrix], [nL], [nM], k)
+    return out[0]
+
+
+def permanentProb(costMatrix, nL, nM, permOpt=1):
+    """assignment.h:13.  Returns probs[nM][nL+1]; exact for permOpt 0, 1 and 2, any other value raises as the reference throws."""
+    if permOpt not in (0, 1, 2):
+        raise RuntimeError("Unknown permanent option passed!")
+    out, _ = _engine().permanent_probs([costMatrix], [nL], [nM])
     return out[0]

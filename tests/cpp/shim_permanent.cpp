@@ -1,0 +1,43 @@
+// A caller of permanentProb written like the reference's own call sites (assignment.cpp:64, comparison.cpp:225, 233), compiled
+// against include/kbest_shims.hpp and linked to libkbest_amd.so.
+// usage: shim_permanent FILE   -- FILE: "nL nM" and then the (nL+nM)*nM column-major costs as C99 hex floats ("inf" allowed)
+// prints, for permOpt 0, 1, 2: one line "p <permOpt> <column> <nL+1 hex floats>" per column; then what permOpt 3 does.
+#include <cstdio>
+#include <cstdlib>
+#include <stdexcept>
+#include <vector>
+
+#include "kbest_shims.hpp"
+
+int main(int argc, char **argv)
+{
+    if (argc < 2) return 2;
+    FILE *f = fopen(argv[1], "r");
+    if (!f) return 2;
+    unsigned long nL = 0, nM = 0;
+    if (fscanf(f, "%lu %lu", &nL, &nM) != 2) return 2;
+    std::vector<double> cost((nL + nM) * nM);
+    char tok[64];
+    for (double &x : cost) {
+        if (fscanf(f, "%63s", tok) != 1) return 2;
+        x = strtod(tok, nullptr);
+    }
+    fclose(f);
+    for (int permOpt = 0; permOpt <= 2; permOpt++) {
+        const std::vector<std::vector<double>> probs = permanentProb(cost, nL, nM, permOpt);
+        if (probs.size() != nM) return 3;
+        for (size_t c = 0; c < nM; c++) {
+            if (probs[c].size() != nL + 1) return 3;
+            printf("p %d %zu", permOpt, c);
+            for (double v : probs[c]) printf(" %a", v);
+            printf("\n");
+        }
+    }
+    try {
+        permanentProb(cost, nL, nM, 3);
+        printf("permOpt 3: no throw\n");
+    } catch (const std::runtime_error &e) {
+        printf("permOpt 3: runtime_error %s\n", e.what());
+    }
+    return 0;
+}
