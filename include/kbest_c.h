@@ -24,6 +24,8 @@
  *        batched form of  asgnBB (assignment.cpp:724-797; k = 1, maximize)
  *   kbest_permanent_probs_batch_f64 / kbest_permanent_probs_batch_f64_dev
  *        batched form of  permanentProb (assignment.h:13, assignment.cpp:145-290), exact for every permOpt
+ *   kbest_belief_probs_batch_f64 / kbest_belief_probs_batch_f64_dev
+ *        the association probabilities by loopy belief propagation, for frames of any size (not in the reference)
  *
  * Conventions kept from the reference: cost matrices are column-major
  * C[row + col*numRow] with numRow >= numCol (shortestPathCPP.hpp:185-190);
@@ -384,6 +386,44 @@ int kbest_reserve_permanent(kbest_ctx *ctx, int B, int maxRawRow, int maxCol);
 int kbest_set_permanent_work_cap(kbest_ctx *ctx, size_t bytes);
 /* Diagnostic, for tests: workgroups -- frames in flight -- of the context's last permanent launch (-1: null context). */
 int kbest_last_permanent_grid(kbest_ctx *ctx);
+
+/*
+ * Association probabilities by loopy belief propagation on the assignment model (kbest_lbp.hip; not in the reference): the
+ * marginals of the Bethe approximation of the permanent, for the frames the exact entry above does not take -- deterministic,
+ * every term non-negative, O(rows x columns) per sweep.  Layout and conditioning of kbest_permanent_probs_batch_f64: frame b is an
+ * (nL+nM) x nM column-major block at costOff[b], probs [nM][nL+1] at probOff[b], rows r >= nL are folded into slot nL;
+ * condition = 1: raw blocks, conditionCosts -> the iteration -> scatter back (landmarks conditionCosts drops get exactly 0.0).
+ * On a = the frame's toProbs matrix (all-zero rows left out), from nu = 1, Jacobi sweeps
+ *     x = a nu,  s[r][c] = sum_{r' != r} x[r'][c],  mu = a / s where a > 0 (s = 0: +inf), else 0,
+ *     nu'[r][c] = 1 / (1 + sum_{c' != c} mu[r][c']),  resid = max over a > 0 of |nu' - nu|
+ * until resid <= tol or maxIter sweeps (tol <= 0: exactly maxIter sweeps); then w = a nu and
+ * probs[c][min(r, nL)] += w[r][c] / sum_r w[r][c].  iters (may be NULL): iters[b] = sweeps run, or -2 for an infeasible frame --
+ * a column whose w sums to 0 (no finite entry, two columns forced onto one row): all its probabilities 0, not NaN.  resid (may be
+ * NULL): resid[b] = the last sweep's resid.  An approximation: on 200 KITTI-like 30x10 frames the largest deviation from the exact
+ * probabilities has median 0.012 and maximum 0.20 (the numpy restatement, tests/test_lbp_cpu.py), about what 1 000 best assignments give; frames
+ * of a single measurement and frames whose rows have one finite entry each are exact.
+ * Limits: 1 <= nM <= KBEST_LBP_MAX_COLS, nL + nM <= KBEST_MAX_DIM_WIDE (KBEST_ERR_UNSUPPORTED beyond).  A frame's result does not
+ * depend on the batch it travels in, bit for bit.  Host buffers; stages, reserves and runs kbest_belief_probs_batch_f64_dev.
+ */
+#define KBEST_LBP_MAX_COLS 128
+int kbest_belief_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,
+                                 const int64_t *costOff, int condition, double tol, int maxIter, double *probs,
+                                 const int64_t *probOff, int32_t *iters, double *resid);
+/* The same on device buffers, asynchronous on `stream` (NULL: the context's): one launch, no allocation.  maxRawRow / maxCol:
+ * upper bounds of nL + nM / nM over the batch (a frame beyond them gets iters = -1 and its probs are left alone); the launch has
+ * one wave per 64 rows of maxRawRow in a workgroup, so bounds close to the frames keep frame-sized work frame-sized.  Needs
+ * kbest_reserve_belief first (KBEST_ERR_NOT_RESERVED): frames whose a and nu do not fit LDS keep them in a work space in HBM,
+ * 32 * maxRawRow * maxCol bytes per frame IN FLIGHT, at most KBEST_LBP_WORK_CAP bytes in all (at least one frame); the workgroups
+ * take frame after frame, none ever waits for another. */
+#define KBEST_LBP_WORK_CAP ((size_t)1 << 30)
+int kbest_belief_probs_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, const int32_t *d_nL,
+                                     const int32_t *d_nM, const double *d_cost, const int64_t *d_costOff, int condition,
+                                     double tol, int maxIter, double *d_probs, const int64_t *d_probOff, int32_t *d_iters,
+                                     double *d_resid, void *stream);
+int kbest_reserve_belief(kbest_ctx *ctx, int B, int maxRawRow, int maxCol);
+/* Diagnostic, for tests: the LDS bytes the belief-propagation launches of this context may plan with (0: the device's limit
+ * again).  A low value sends small frames through the work space in HBM -- the same results bit for bit. */
+int kbest_set_belief_lds_limit(kbest_ctx *ctx, size_t bytes);
 /* on = 1: the HOST-buffer association entries of this context (kbest_weights / assoc_probs / bruteforce / quadric_assoc) enumerate
  * their k best in the REFERENCE's own order of operations (the reference-order kernel, as KBEST_FLAG_REFERENCE_ORDER does for
  * kbest_batch_f64): where exactly equal gains straddle slot k the assignments that are weighed are the ones the reference's

@@ -121,6 +121,11 @@ std::vector<double> conditionCosts(const std::vector<double> &costs, size_t nRow
 // (assignment.cpp:344, 406).
 std::vector<std::vector<double>> permanentProb(std::vector<double> costMatrix, size_t nL, size_t nM, int permOpt);
 
+// Not in the reference: the association probabilities by loopy belief propagation (kbest_belief_probs_batch_f64, tol 1e-12, at most
+// 10 000 sweeps), [nM][nL+1] like assignmentProb, for frames of up to 128 measurements and 1 024 rows -- the frames permanentProb
+// does not take.  An approximation of known quality (include/kbest_c.h); an infeasible frame comes back as all zeros.
+std::vector<std::vector<double>> beliefProb(const std::vector<double> &costMatrix, size_t nL, size_t nM);
+
 // Not in the reference: the engine context behind the functions above (created on first use, GPU 0), for the entries of
 // kbest_c.h that take one -- e.g. kbest_last_tie_flags after a call.
 struct kbest_ctx;

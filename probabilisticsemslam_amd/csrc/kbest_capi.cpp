@@ -142,6 +142,8 @@ struct kbest_ctx {
     DevBufRaw permBuf;        // work space of the permanent kernel (kbest_perm.hip): the subset layers that do not fit LDS
     size_t permCap = KBEST_PERM_WORK_CAP;  // ... and its cap (kbest_set_permanent_work_cap)
     int permLastGrid = 0;     // workgroups (frames in flight) of the last permanent launch (kbest_last_permanent_grid)
+    DevBufRaw lbpBuf;         // work space of the belief-propagation kernel (kbest_lbp.hip): frames whose a and nu do not fit LDS
+    int lbpLdsLimit = 0;      // kbest_set_belief_lds_limit: LDS bytes that kernel may plan with (0: ldsLimit)
     DevBufRaw relayBuf;       // relay launches of the 64-row kernel: [B] LDS images (kbest_engine.hip)
     DevBufRaw relayFlags;     // ... and three words per matrix: claimed / done / gone (zeroed when the buffer is made, put back to zero by every launch)
     long long relayLaunches = 0;  // relay launches made (kbest_relay_launches)
@@ -490,6 +492,7 @@ int kbest_destroy(kbest_ctx *ctx)
     if (ctx->relayBuf.p) (void)hipFree(ctx->relayBuf.p);
     if (ctx->exactBuf.p) (void)hipFree(ctx->exactBuf.p);
     if (ctx->permBuf.p) (void)hipFree(ctx->permBuf.p);
+    if (ctx->lbpBuf.p) (void)hipFree(ctx->lbpBuf.p);
     if (ctx->relayFlags.p) (void)hipFree(ctx->relayFlags.p);
     if (ctx->lastEvent) (void)hipEventDestroy(ctx->lastEvent);
     for (auto &a : ctx->aux)
@@ -2771,6 +2774,163 @@ extern "C" int kbest_permanent_probs_batch_f64(kbest_ctx *ctx, int B, const int3
     for (int b = 0; b < B; b++)
         memcpy(probs + probOff[b], hp.data() + probOff[b], (size_t)nM[b] * ((size_t)nL[b] + 1) * 8);
     if (perm) HIP_TRY(ctx, hipMemcpy(perm, dPerm.p, (size_t)B * 8, hipMemcpyDeviceToHost));
+    return KBEST_OK;
+}
+
+// ---- beliefProb (kbest_lbp.hip) ----------------------------------------------------------------------------------------------
+static kb::LbpPlan lbp_plan_of(const kbest_ctx *ctx, int maxRawRow, int maxCol)
+{
+    const int lim = (ctx->lbpLdsLimit > 0 && ctx->lbpLdsLimit < ctx->ldsLimit) ? ctx->lbpLdsLimit : ctx->ldsLimit;
+    return kb::lbp_plan(maxRawRow, maxCol, lim);
+}
+
+// Workgroups of a launch = frames in flight: as many as the batch has, as the chip holds at a time (32 waves per CU, the
+// kernel's LDS) and as have a slice of the work space (at most KBEST_LBP_WORK_CAP bytes, at least one).
+static int lbp_grid(const kbest_ctx *ctx, const kb::LbpPlan &pl, int B, size_t bytes)
+{
+    long long g = B;
+    int perCU = 32 / (pl.threads / 64);
+    if (pl.lds > 0 && perCU > ctx->ldsPerCU / pl.lds) perCU = ctx->ldsPerCU / pl.lds;
+    if (perCU < 1) perCU = 1;
+    const long long resident = (long long)ctx->nCU * perCU;
+    if (g > resident) g = resident;
+    if (pl.slotDoubles > 0) {
+        const size_t cap = bytes < KBEST_LBP_WORK_CAP ? bytes : KBEST_LBP_WORK_CAP;
+        long long fit = (long long)(cap / ((size_t)pl.slotDoubles * 8));
+        if (fit < 1) fit = 1;
+        if (g > fit) g = fit;
+    }
+    return (int)g;
+}
+
+static int lbp_check_shape(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, const char *who)
+{
+    if (B < 0 || maxCol < 1 || maxRawRow < maxCol) return fail(ctx, KBEST_ERR_BAD_ARG, (std::string(who) + ": bad argument").c_str());
+    if (maxCol > KBEST_LBP_MAX_COLS)
+        return fail(ctx, KBEST_ERR_UNSUPPORTED, (std::string(who) + ": more than KBEST_LBP_MAX_COLS = 128 measurements in a frame").c_str());
+    if (maxRawRow > KBEST_MAX_DIM_WIDE)
+        return fail(ctx, KBEST_ERR_UNSUPPORTED, (std::string(who) + ": more than KBEST_MAX_DIM_WIDE = 1024 rows (nL + nM) in a frame").c_str());
+    return KBEST_OK;
+}
+
+extern "C" int kbest_set_belief_lds_limit(kbest_ctx *ctx, size_t bytes)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    ctx->lbpLdsLimit = bytes > (size_t)(1 << 30) ? (1 << 30) : (int)bytes;
+    return KBEST_OK;
+}
+
+extern "C" int kbest_reserve_belief(kbest_ctx *ctx, int B, int maxRawRow, int maxCol)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    int rc = lbp_check_shape(ctx, B, maxRawRow, maxCol, "kbest_reserve_belief");
+    if (rc != KBEST_OK || B == 0) return rc;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const kb::LbpPlan pl = lbp_plan_of(ctx, maxRawRow, maxCol);
+    if (pl.slotDoubles == 0) return KBEST_OK;
+    const int g = lbp_grid(ctx, pl, B, (size_t)-1);
+    return raw_reserve(ctx, ctx->lbpBuf, (size_t)pl.slotDoubles * 8 * (size_t)g);
+}
+
+extern "C" int kbest_belief_probs_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, const int32_t *d_nL,
+                                                const int32_t *d_nM, const double *d_cost, const int64_t *d_costOff,
+                                                int condition, double tol, int maxIter, double *d_probs,
+                                                const int64_t *d_probOff, int32_t *d_iters, double *d_resid, void *stream)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    int rc = lbp_check_shape(ctx, B, maxRawRow, maxCol, "kbest_belief_probs_batch_f64_dev");
+    if (rc != KBEST_OK) return rc;
+    if (!d_nL || !d_nM || !d_cost || !d_costOff || !d_probs || !d_probOff || maxIter < 0 || tol != tol)
+        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_belief_probs_batch_f64_dev: bad argument");
+    if (B == 0) return KBEST_OK;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const kb::LbpPlan pl = lbp_plan_of(ctx, maxRawRow, maxCol);
+    if (pl.slotDoubles > 0 && ctx->lbpBuf.bytes < (size_t)pl.slotDoubles * 8)  // asynchronous entry: never allocates
+        return fail(ctx, KBEST_ERR_NOT_RESERVED, "kbest_belief_probs_batch_f64_dev: call kbest_reserve_belief first");
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = order_behind_last(ctx, s);  // (one work space per context)
+    if (rc != KBEST_OK) return rc;
+    const Launched mark{ctx, s};
+    kb::LbpParams lp;
+    lp.cost = d_cost;
+    lp.costOff = reinterpret_cast<const long long *>(d_costOff);
+    lp.probOff = reinterpret_cast<const long long *>(d_probOff);
+    lp.nL = d_nL;
+    lp.nM = d_nM;
+    lp.probs = d_probs;
+    lp.iters = d_iters;
+    lp.resid = d_resid;
+    lp.work = static_cast<double *>(ctx->lbpBuf.p);
+    lp.slotStride = pl.slotDoubles;
+    lp.tol = tol;
+    lp.maxIter = maxIter;
+    lp.B = B;
+    lp.maxRawRow = maxRawRow;
+    lp.maxCol = maxCol;
+    lp.condition = condition ? 1 : 0;
+    const hipError_t e = kb::launch_kbest_lbp(lp, pl, lbp_grid(ctx, pl, B, ctx->lbpBuf.bytes), s);
+    if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "belief-propagation kernel launch", e);
+    return KBEST_OK;
+}
+
+extern "C" int kbest_belief_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,
+                                            const int64_t *costOff, int condition, double tol, int maxIter, double *probs,
+                                            const int64_t *probOff, int32_t *iters, double *resid)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    if (B < 0 || maxIter < 0 || tol != tol || (B > 0 && (!nL || !nM || !cost || !costOff || !probs || !probOff)))
+        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_belief_probs_batch_f64: bad argument");
+    if (B == 0) return KBEST_OK;
+    int maxRawRow = 1, maxCol = 1;
+    size_t costN = 0, probN = 0;
+    for (int b = 0; b < B; b++) {
+        if (nL[b] < 0 || nM[b] < 1 || costOff[b] < 0 || probOff[b] < 0)
+            return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_belief_probs_batch_f64: a frame with nL < 0, nM < 1 or a negative offset");
+        const long long nr = (long long)nL[b] + nM[b];
+        if (nr > maxRawRow) maxRawRow = nr > (1 << 30) ? (1 << 30) : (int)nr;
+        if (nM[b] > maxCol) maxCol = nM[b];
+        const size_t ce = (size_t)costOff[b] + (size_t)nr * (size_t)nM[b], pe = (size_t)probOff[b] + (size_t)nM[b] * ((size_t)nL[b] + 1);
+        if (ce > costN) costN = ce;
+        if (pe > probN) probN = pe;
+    }
+    int rc = lbp_check_shape(ctx, B, maxRawRow, maxCol, "kbest_belief_probs_batch_f64");
+    if (rc != KBEST_OK) return rc;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = kbest_reserve_belief(ctx, B, maxRawRow, maxCol);
+    if (rc != KBEST_OK) return rc;
+    DevBuf dCost, dMeta, dProbs, dOut;
+    // meta: costOff[B] | probOff[B] (int64) | nL[B] | nM[B] (int32);  out: resid[B] (double) | iters[B] (int32)
+    std::vector<unsigned char> meta((size_t)B * 24);
+    memcpy(meta.data(), costOff, (size_t)B * 8);
+    memcpy(meta.data() + (size_t)B * 8, probOff, (size_t)B * 8);
+    memcpy(meta.data() + (size_t)B * 16, nL, (size_t)B * 4);
+    memcpy(meta.data() + (size_t)B * 20, nM, (size_t)B * 4);
+    hipError_t e;
+    if ((e = dCost.alloc(ctx, costN * 8)) != hipSuccess || (e = dMeta.alloc(ctx, meta.size())) != hipSuccess ||
+        (e = dProbs.alloc(ctx, probN * 8)) != hipSuccess || (e = dOut.alloc(ctx, (size_t)B * 12)) != hipSuccess)
+        return fail(ctx, KBEST_ERR_NOMEM, "kbest_belief_probs_batch_f64: device buffers", e);
+    HIP_TRY(ctx, hipMemcpy(dCost.p, cost, costN * 8, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(dMeta.p, meta.data(), meta.size(), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemsetAsync(dProbs.p, 0, probN * 8, ctx->stream));
+    unsigned char *m8 = dMeta.as<unsigned char>(), *o8 = dOut.as<unsigned char>();
+    rc = kbest_belief_probs_batch_f64_dev(ctx, B, maxRawRow, maxCol, reinterpret_cast<const int32_t *>(m8 + (size_t)B * 16),
+                                          reinterpret_cast<const int32_t *>(m8 + (size_t)B * 20), dCost.as<double>(),
+                                          reinterpret_cast<const int64_t *>(m8), condition, tol, maxIter, dProbs.as<double>(),
+                                          reinterpret_cast<const int64_t *>(m8 + (size_t)B * 8),
+                                          reinterpret_cast<int32_t *>(o8 + (size_t)B * 8), reinterpret_cast<double *>(o8), nullptr);
+    if (rc != KBEST_OK) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    // every frame's own slice only: what lies between the slices in the caller's buffer is the caller's
+    std::vector<double> hp(probN);
+    HIP_TRY(ctx, hipMemcpy(hp.data(), dProbs.p, probN * 8, hipMemcpyDeviceToHost));
+    for (int b = 0; b < B; b++)
+        memcpy(probs + probOff[b], hp.data() + probOff[b], (size_t)nM[b] * ((size_t)nL[b] + 1) * 8);
+    if (resid) HIP_TRY(ctx, hipMemcpy(resid, o8, (size_t)B * 8, hipMemcpyDeviceToHost));
+    if (iters) HIP_TRY(ctx, hipMemcpy(iters, o8 + (size_t)B * 8, (size_t)B * 4, hipMemcpyDeviceToHost));
     return KBEST_OK;
 }
 

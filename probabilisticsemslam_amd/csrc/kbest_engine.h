@@ -557,6 +557,28 @@ struct PermPlan {
 PermPlan perm_plan(int maxRawRow, int maxCol, int ldsLimit, int ldsPerCU);
 hipError_t launch_kbest_perm(const PermParams &p, const PermPlan &pl, int grid, hipStream_t stream);
 
+// kbest_lbp.hip: beliefProb, the association probabilities by loopy belief propagation on the assignment model (any frame size)
+struct LbpParams {
+    const double *cost;        // packed column-major (nL + nM) x nM blocks
+    const long long *costOff;  // [B]
+    const long long *probOff;  // [B]
+    const int *nL, *nM;        // [B]
+    double *probs;             // [nM][nL + 1] per frame
+    int *iters;                // [B] or nullptr: sweeps run; -1: frame beyond the launch's bounds; -2: infeasible frame
+    double *resid;             // [B] or nullptr: max |nu' - nu| of the last sweep
+    double *work;              // work space: slotStride doubles per workgroup of the launch (mode 1)
+    long long slotStride;
+    double tol;
+    int maxIter, B, maxRawRow, maxCol, condition;
+};
+struct LbpPlan {
+    int mode;               // 0: a, nu and the two sweep buffers in LDS; 1: in the work space
+    int threads, lds;       // workgroup size (one wave per 64 rows of the launch's bound), dynamic LDS bytes
+    long long slotDoubles;  // work space per workgroup
+};
+LbpPlan lbp_plan(int maxRawRow, int maxCol, int ldsLimit);
+hipError_t launch_kbest_lbp(const LbpParams &p, const LbpPlan &pl, int grid, hipStream_t stream);
+
 }  // namespace kb
 
 // kbest_capi.cpp: completes the gain levels that straddle slot k in the caller's HOST tables (see there)

@@ -253,4 +253,18 @@ std::vector<std::vector<double>> permanentProb(std::vector<double> costMatrix, s
     return probs;
 }
 
+std::vector<std::vector<double>> beliefProb(const std::vector<double> &costMatrix, size_t nL, size_t nM)
+{
+    kbest_ctx *ctx = global_ctx();
+    const int32_t l = (int32_t)nL, m = (int32_t)nM;
+    const int64_t zero = 0;
+    std::vector<double> flat(nM * (nL + 1), 0.0);
+    check(ctx, kbest_belief_probs_batch_f64(ctx, 1, &l, &m, costMatrix.data(), &zero, 0, 1e-12, 10000, flat.data(), &zero, nullptr,
+                                            nullptr));
+    std::vector<std::vector<double>> probs(nM, std::vector<double>(nL + 1, 0.0));
+    for (size_t c = 0; c < nM; c++)
+        for (size_t j = 0; j <= nL; j++) probs[c][j] = flat[c * (nL + 1) + j];
+    return probs;
+}
+
 kbest_ctx *kbest_shims_context() { return global_ctx(); }

@@ -30,6 +30,7 @@ KBEST_MAX_DIM = 64        # rows handled by the LDS-resident kernel
 KBEST_MAX_DIM_WIDE = 1024  # rows of the general-size kernel (beyond KBEST_MAX_DIM)
 KBEST_MAX_DIM_EXACT = 16384  # rows handled at all (the reference-order kernel beyond KBEST_MAX_DIM_WIDE)
 KBEST_PERM_MAX_COLS = 16     # measurements per frame of the exact (permanent) association probabilities
+KBEST_LBP_MAX_COLS = 128     # measurements per frame of the belief-propagation association probabilities
 
 # every symbol include/kbest_c.h declares
 C_ABI_SYMBOLS = (
@@ -46,6 +47,7 @@ C_ABI_SYMBOLS = (
     "kbest_last_route", "kbest_resolve_ties_dev", "kbest_multi_last_tie_flags", "kbest_reserve_exact",
     "kbest_set_reference_order", "kbest_permanent_probs_batch_f64", "kbest_permanent_probs_batch_f64_dev",
     "kbest_reserve_permanent", "kbest_set_permanent_work_cap", "kbest_last_permanent_grid",
+    "kbest_belief_probs_batch_f64", "kbest_belief_probs_batch_f64_dev", "kbest_reserve_belief", "kbest_set_belief_lds_limit",
 )
 KBEST_MULTI_STAMPS = 6
 KBEST_MULTI_BATCH, KBEST_MULTI_SUBTREE = 0, 1
@@ -146,6 +148,12 @@ def load_library():
         lib.kbest_reserve_permanent.argtypes = [vp, C.c_int, C.c_int, C.c_int]
         lib.kbest_set_permanent_work_cap.argtypes = [vp, C.c_size_t]
         lib.kbest_last_permanent_grid.argtypes = [vp]
+    if hasattr(lib, "kbest_belief_probs_batch_f64"):
+        lib.kbest_belief_probs_batch_f64.argtypes = [vp, C.c_int, i32p, i32p, dp, i64p, C.c_int, C.c_double, C.c_int, dp, i64p, i32p, dp]
+        lib.kbest_belief_probs_batch_f64_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int, i32p, i32p, dp, i64p, C.c_int, C.c_double,
+                                                         C.c_int, dp, i64p, i32p, dp, vp]
+        lib.kbest_reserve_belief.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+        lib.kbest_set_belief_lds_limit.argtypes = [vp, C.c_size_t]
     lib.kbest_register_host_buffer.argtypes = [vp, vp, C.c_size_t]
     lib.kbest_unregister_host_buffer.argtypes = [vp, vp]
     _lib = lib
@@ -355,6 +363,37 @@ class KBestEngine:
         """Diagnostic (kbest_last_permanent_grid): workgroups -- frames in flight -- of this context's last permanent launch."""
         return int(self.lib.kbest_last_permanent_grid(self.ctx))
 
+    def belief_probs(self, costs, nL, nM, condition=False, tol=1e-12, max_iter=10000):
+        """Batched beliefProb (kbest_lbp.hip): the association probabilities by loopy belief propagation, nM <= 128 and
+        nL + nM <= 1024.  Packing and condition as permanent_probs().  Stops after the sweep whose resid <= tol or after max_iter
+        sweeps (tol <= 0: exactly max_iter).  Returns (list of [nM, nL+1] arrays, iters[B]: sweeps run, -2 for an infeasible frame
+        (all zeros), resid[B]: the last sweep's max |nu' - nu|)."""
+        nL = np.ascontiguousarray(nL, dtype=np.int32)
+        nM = np.ascontiguousarray(nM, dtype=np.int32)
+        B = len(nL)
+        sizes = [(int(nL[b]) + int(nM[b])) * int(nM[b]) for b in range(B)]
+        psizes = [int(nM[b]) * (int(nL[b]) + 1) for b in range(B)]
+        costOff = np.zeros(B, np.int64)
+        probOff = np.zeros(B, np.int64)
+        costOff[1:] = np.cumsum(sizes)[:-1]
+        probOff[1:] = np.cumsum(psizes)[:-1]
+        flat = np.concatenate([np.ascontiguousarray(c, dtype=np.float64).reshape(-1) for c in costs])
+        if flat.size != sum(sizes):
+            raise KBestError("belief_probs: a cost block is not (nL + nM) x nM")
+        probs = np.zeros(int(sum(psizes)), np.float64)
+        iters = np.zeros(B, np.int32)
+        resid = np.zeros(B, np.float64)
+        self._check(self.lib.kbest_belief_probs_batch_f64(self.ctx, B, _ptr(nL), _ptr(nM), _ptr(flat), _ptr(costOff),
+                                                          int(bool(condition)), float(tol), int(max_iter), _ptr(probs),
+                                                          _ptr(probOff), _ptr(iters), _ptr(resid)))
+        out = [probs[probOff[b]: probOff[b] + psizes[b]].reshape(int(nM[b]), int(nL[b]) + 1) for b in range(B)]
+        return out, iters, resid
+
+    def set_belief_lds_limit(self, nbytes=0):
+        """Diagnostic (kbest_set_belief_lds_limit): LDS bytes the belief-propagation launches may plan with, 0 = the device's limit;
+        a low value keeps a and nu of small frames in the HBM work space -- the same results."""
+        self._check(self.lib.kbest_set_belief_lds_limit(self.ctx, int(nbytes)))
+
     @staticmethod
     def _pack_quadrics(frames):
         """frames: list of (landMean (nL,3), landCov (nL,3,3), measMean (nM,3), measCov (nM,3,3))."""
@@ -502,6 +541,23 @@ class KBestEngine:
                                                                  dp(d_costOff), int(bool(condition)), dp(d_probs), dp(d_probOff),
                                                                  dp(d_perm), C.c_void_p(stream) if stream else None))
 
+    def reserve_belief(self, B, maxRawRow, maxCol):
+        self._check(self.lib.kbest_reserve_belief(self.ctx, B, maxRawRow, maxCol))
+
+    def belief_probs_dev(self, B, maxRawRow, maxCol, d_nL, d_nM, d_cost, d_costOff, d_probs, d_probOff, d_iters=None, d_resid=None,
+                         condition=False, tol=1e-12, max_iter=10000, stream=None, reserve=True):
+        """kbest_belief_probs_batch_f64_dev on torch CUDA tensors, asynchronous on `stream` (a raw hipStream_t integer): one
+        launch.  The work space is sized here (a no-op once it is large enough): the C entry never allocates.  reserve=False: the
+        caller has called reserve_belief (timed loops: nothing but the C entry between two events)."""
+        def dp(t):
+            return None if t is None else C.c_void_p(t.data_ptr())
+        if reserve:
+            self.reserve_belief(B, maxRawRow, maxCol)
+        self._check(self.lib.kbest_belief_probs_batch_f64_dev(self.ctx, B, maxRawRow, maxCol, dp(d_nL), dp(d_nM), dp(d_cost),
+                                                              dp(d_costOff), int(bool(condition)), float(tol), int(max_iter),
+                                                              dp(d_probs), dp(d_probOff), dp(d_iters), dp(d_resid),
+                                                              C.c_void_p(stream) if stream else None))
+
 
 class KBestMulti:
     """Multi-device engine of include/kbest_c.h: one context per GPU in ONE process, contiguous block sharding, RCCL
@@ -613,4 +669,11 @@ def permanentProb(costMatrix, nL, nM, permOpt=1):
     if permOpt not in (0, 1, 2):
         raise RuntimeError("Unknown permanent option passed!")
     out, _ = _engine().permanent_probs([costMatrix], [nL], [nM])
+    return out[0]
+
+
+def beliefProb(costMatrix, nL, nM):
+    """Not in the reference: the association probabilities by loopy belief propagation (tol 1e-12, at most 10 000 sweeps), for
+    frames of up to 128 measurements.  Returns probs[nM][nL+1]; an infeasible frame comes back as all zeros."""
+    out, _, _ = _engine().belief_probs([costMatrix], [nL], [nM])
     return out[0]
