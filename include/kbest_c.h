@@ -26,6 +26,8 @@
  *        batched form of  permanentProb (assignment.h:13, assignment.cpp:145-290), exact for every permOpt
  *   kbest_belief_probs_batch_f64 / kbest_belief_probs_batch_f64_dev
  *        the association probabilities by loopy belief propagation, for frames of any size (not in the reference)
+ *   kbest_clustered_probs_batch_f64 / kbest_clustered_probs_batch_f64_dev
+ *        the exact association probabilities by gated clusters, for frames of up to 128 measurements (not in the reference)
  *
  * Conventions kept from the reference: cost matrices are column-major
  * C[row + col*numRow] with numRow >= numCol (shortestPathCPP.hpp:185-190);
@@ -424,6 +426,50 @@ int kbest_reserve_belief(kbest_ctx *ctx, int B, int maxRawRow, int maxCol);
 /* Diagnostic, for tests: the LDS bytes the belief-propagation launches of this context may plan with (0: the device's limit
  * again).  A low value sends small frames through the work space in HBM -- the same results bit for bit. */
 int kbest_set_belief_lds_limit(kbest_ctx *ctx, size_t bytes);
+
+/*
+ * The EXACT association probabilities by gated clusters (kbest_cluster.hip; not in the reference), for frames of up to
+ * KBEST_CLUSTER_MAX_COLS measurements and KBEST_MAX_DIM_WIDE rows.  Layout and conditioning of kbest_permanent_probs_batch_f64:
+ * frame b is an (nL+nM) x nM column-major block at costOff[b], probs [nM][nL+1] at probOff[b], rows r >= nL are folded into slot nL;
+ * condition = 1: raw blocks, conditionCosts -> the sums -> scatter back (landmarks conditionCosts drops get exactly 0.0).
+ * On a = the frame's toProbs matrix (the minimum of the WHOLE block): columns c and c' are adjacent when some row has a non-zero
+ * entry in both; a cluster is a connected component of columns with every row that has a non-zero entry in one of them (a column
+ * without a non-zero entry is a cluster by itself).  The permanent factorises over the clusters and so do the marginals: per
+ * cluster k the sums of kbest_permanent_probs_batch_f64 on the sub-matrix give Z_k and probs[c][min(r, nL)] += w[r][c] / Z_k.
+ *   logPerm (may be NULL): logPerm[b] = sum_k log Z_k in cluster order (the product itself leaves the doubles);
+ *   info (may be NULL): info[b] > 0: the number of clusters, every probability is exact;  0: infeasible (some Z_k = 0): zeros and
+ *       logPerm = -inf;  -1: the frame lies beyond the launch's bounds and is untouched (the device entry);  -2: a cluster of more
+ *       than KBEST_CLUSTER_MAX_SIZE measurements;  -3: a cluster whose layers, (R_k + 2) * 2^m_k * 8 bytes, exceed the slot cap.
+ *       -2 and -3 refuse the FRAME, not the call: its probabilities are zeros and logPerm is NaN;
+ *   maxCluster (may be NULL): maxCluster[b] = measurements of the frame's largest cluster, always written;
+ *   label (may be NULL; int32 [B][labelStride], labelStride >= the largest nM): label[b][c] = the lowest column of the cluster of
+ *       column c, -1 for c >= nM.  Clusters are ordered by label.
+ * A frame's result does not depend on the batch it travels in, on the launch's bounds or on the caps, bit for bit.  Host buffers;
+ * stages, reserves and runs kbest_clustered_probs_batch_f64_dev.  nM > 128 or nL + nM > 1 024: KBEST_ERR_UNSUPPORTED.
+ */
+#define KBEST_CLUSTER_MAX_COLS 128                   /* per frame */
+#define KBEST_CLUSTER_MAX_SIZE 16                    /* per cluster: KBEST_PERM_MAX_COLS, for its reason */
+#define KBEST_CLUSTER_SLOT_CAP ((size_t)64 << 20)    /* layers of one cluster: 16 columns x 126 rows */
+#define KBEST_CLUSTER_WORK_CAP ((size_t)1 << 30)
+int kbest_clustered_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,
+                                    const int64_t *costOff, int condition, double *probs, const int64_t *probOff, double *logPerm,
+                                    int32_t *info, int32_t *maxCluster, int32_t *label, int labelStride);
+/* The same on device buffers, asynchronous on `stream` (NULL: the context's): one launch, no allocation.  maxRawRow / maxCol: upper
+ * bounds of nL + nM / nM over the batch (a frame beyond them gets info = -1 and is left alone).  Needs kbest_reserve_clustered
+ * first (KBEST_ERR_NOT_RESERVED): per frame IN FLIGHT a slot of min(slot cap, (maxRawRow + 2) * 2^min(maxCol, 16) * 8) bytes of
+ * layers plus maxRawRow * 128 bytes, at most KBEST_CLUSTER_WORK_CAP bytes in all (at least one frame); the workgroups take frame
+ * after frame, none ever waits for another. */
+int kbest_clustered_probs_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, const int32_t *d_nL,
+                                        const int32_t *d_nM, const double *d_cost, const int64_t *d_costOff, int condition,
+                                        double *d_probs, const int64_t *d_probOff, double *d_logPerm, int32_t *d_info,
+                                        int32_t *d_maxCluster, int32_t *d_label, int labelStride, void *stream);
+int kbest_reserve_clustered(kbest_ctx *ctx, int B, int maxRawRow, int maxCol);
+/* For tests: the layers of one cluster / the whole work space at the most (0: the default again).  The results do not depend on
+ * either, bit for bit -- except that a lower slot cap refuses (-3) the frames whose clusters need more. */
+int kbest_set_clustered_slot_cap(kbest_ctx *ctx, size_t bytes);
+int kbest_set_clustered_work_cap(kbest_ctx *ctx, size_t bytes);
+/* Diagnostic, for tests: workgroups -- frames in flight -- of the context's last clustered launch (-1: null context). */
+int kbest_last_clustered_grid(kbest_ctx *ctx);
 /* on = 1: the HOST-buffer association entries of this context (kbest_weights / assoc_probs / bruteforce / quadric_assoc) enumerate
  * their k best in the REFERENCE's own order of operations (the reference-order kernel, as KBEST_FLAG_REFERENCE_ORDER does for
  * kbest_batch_f64): where exactly equal gains straddle slot k the assignments that are weighed are the ones the reference's

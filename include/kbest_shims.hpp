@@ -126,6 +126,11 @@ std::vector<std::vector<double>> permanentProb(std::vector<double> costMatrix, s
 // does not take.  An approximation of known quality (include/kbest_c.h); an infeasible frame comes back as all zeros.
 std::vector<std::vector<double>> beliefProb(const std::vector<double> &costMatrix, size_t nL, size_t nM);
 
+// Not in the reference: the EXACT association probabilities by gated clusters (kbest_clustered_probs_batch_f64), [nM][nL+1] like
+// assignmentProb, for frames of up to 128 measurements and 1 024 rows whose clusters have at most 16 measurements.  Throws
+// std::runtime_error naming the largest cluster when the frame is refused; an infeasible frame comes back as all zeros.
+std::vector<std::vector<double>> clusterProb(const std::vector<double> &costMatrix, size_t nL, size_t nM);
+
 // Not in the reference: the engine context behind the functions above (created on first use, GPU 0), for the entries of
 // kbest_c.h that take one -- e.g. kbest_last_tie_flags after a call.
 struct kbest_ctx;

@@ -144,6 +144,10 @@ struct kbest_ctx {
     int permLastGrid = 0;     // workgroups (frames in flight) of the last permanent launch (kbest_last_permanent_grid)
     DevBufRaw lbpBuf;         // work space of the belief-propagation kernel (kbest_lbp.hip): frames whose a and nu do not fit LDS
     int lbpLdsLimit = 0;      // kbest_set_belief_lds_limit: LDS bytes that kernel may plan with (0: ldsLimit)
+    DevBufRaw clusBuf;        // work space of the clustered exact kernel (kbest_cluster.hip): a cluster's layers that do not fit LDS
+    size_t clusSlotCap = KBEST_CLUSTER_SLOT_CAP;  // ... the layers of one cluster at the most (kbest_set_clustered_slot_cap)
+    size_t clusWorkCap = KBEST_CLUSTER_WORK_CAP;  // ... the whole work space at the most (kbest_set_clustered_work_cap)
+    int clusLastGrid = 0;     // workgroups (frames in flight) of the last clustered launch (kbest_last_clustered_grid)
     DevBufRaw relayBuf;       // relay launches of the 64-row kernel: [B] LDS images (kbest_engine.hip)
     DevBufRaw relayFlags;     // ... and three words per matrix: claimed / done / gone (zeroed when the buffer is made, put back to zero by every launch)
     long long relayLaunches = 0;  // relay launches made (kbest_relay_launches)
@@ -493,6 +497,7 @@ int kbest_destroy(kbest_ctx *ctx)
     if (ctx->exactBuf.p) (void)hipFree(ctx->exactBuf.p);
     if (ctx->permBuf.p) (void)hipFree(ctx->permBuf.p);
     if (ctx->lbpBuf.p) (void)hipFree(ctx->lbpBuf.p);
+    if (ctx->clusBuf.p) (void)hipFree(ctx->clusBuf.p);
     if (ctx->relayFlags.p) (void)hipFree(ctx->relayFlags.p);
     if (ctx->lastEvent) (void)hipEventDestroy(ctx->lastEvent);
     for (auto &a : ctx->aux)
@@ -2931,6 +2936,192 @@ extern "C" int kbest_belief_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t
         memcpy(probs + probOff[b], hp.data() + probOff[b], (size_t)nM[b] * ((size_t)nL[b] + 1) * 8);
     if (resid) HIP_TRY(ctx, hipMemcpy(resid, o8, (size_t)B * 8, hipMemcpyDeviceToHost));
     if (iters) HIP_TRY(ctx, hipMemcpy(iters, o8 + (size_t)B * 8, (size_t)B * 4, hipMemcpyDeviceToHost));
+    return KBEST_OK;
+}
+
+// ---- clusterProb (kbest_cluster.hip) -----------------------------------------------------------------------------------------
+// Workgroups of a launch = frames in flight: as many as the batch has, as the chip holds at a time (the kernel's 155 VGPRs give
+// 3 waves per SIMD, 12 per CU; its LDS the rest), and as have a slot of the work space under the cap (at least one).
+static int cluster_grid(const kbest_ctx *ctx, const kb::ClusterPlan &pl, int B, size_t bytes)
+{
+    long long g = B;
+    int perCU = 12 / (pl.threads / 64);
+    if (pl.lds > 0 && perCU > ctx->ldsPerCU / pl.lds) perCU = ctx->ldsPerCU / pl.lds;
+    if (perCU < 1) perCU = 1;
+    const long long resident = (long long)ctx->nCU * perCU;
+    if (g > resident) g = resident;
+    const size_t cap = bytes < ctx->clusWorkCap ? bytes : ctx->clusWorkCap;
+    long long fit = (long long)(cap / ((size_t)pl.slotDoubles * 8));
+    if (fit < 1) fit = 1;
+    if (g > fit) g = fit;
+    return (int)g;
+}
+
+static int cluster_check_shape(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, const char *who)
+{
+    if (B < 0 || maxCol < 1 || maxRawRow < maxCol) return fail(ctx, KBEST_ERR_BAD_ARG, (std::string(who) + ": bad argument").c_str());
+    if (maxCol > KBEST_CLUSTER_MAX_COLS)
+        return fail(ctx, KBEST_ERR_UNSUPPORTED, (std::string(who) + ": more than KBEST_CLUSTER_MAX_COLS = 128 measurements in a frame").c_str());
+    if (maxRawRow > KBEST_MAX_DIM_WIDE)
+        return fail(ctx, KBEST_ERR_UNSUPPORTED, (std::string(who) + ": more than KBEST_MAX_DIM_WIDE = 1024 rows (nL + nM) in a frame").c_str());
+    return KBEST_OK;
+}
+
+static int cluster_plan_of(kbest_ctx *ctx, int maxRawRow, int maxCol, kb::ClusterPlan &pl, const char *who)
+{
+    pl = kb::cluster_plan(maxRawRow, maxCol, ctx->ldsLimit, ctx->clusSlotCap);
+    if (pl.lds < 0) return fail(ctx, KBEST_ERR_UNSUPPORTED, (std::string(who) + ": the device's LDS is too small for the clustered kernel").c_str());
+    return KBEST_OK;
+}
+
+extern "C" int kbest_set_clustered_slot_cap(kbest_ctx *ctx, size_t bytes)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    ctx->clusSlotCap = bytes ? bytes : KBEST_CLUSTER_SLOT_CAP;
+    return KBEST_OK;
+}
+
+extern "C" int kbest_set_clustered_work_cap(kbest_ctx *ctx, size_t bytes)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    ctx->clusWorkCap = bytes ? bytes : KBEST_CLUSTER_WORK_CAP;
+    return KBEST_OK;
+}
+
+extern "C" int kbest_last_clustered_grid(kbest_ctx *ctx)
+{
+    if (!ctx) return -1;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    return ctx->clusLastGrid;
+}
+
+extern "C" int kbest_reserve_clustered(kbest_ctx *ctx, int B, int maxRawRow, int maxCol)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    int rc = cluster_check_shape(ctx, B, maxRawRow, maxCol, "kbest_reserve_clustered");
+    if (rc != KBEST_OK || B == 0) return rc;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    kb::ClusterPlan pl;
+    rc = cluster_plan_of(ctx, maxRawRow, maxCol, pl, "kbest_reserve_clustered");
+    if (rc != KBEST_OK) return rc;
+    const int g = cluster_grid(ctx, pl, B, (size_t)-1);
+    return raw_reserve(ctx, ctx->clusBuf, (size_t)pl.slotDoubles * 8 * (size_t)g);
+}
+
+extern "C" int kbest_clustered_probs_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, const int32_t *d_nL,
+                                                   const int32_t *d_nM, const double *d_cost, const int64_t *d_costOff,
+                                                   int condition, double *d_probs, const int64_t *d_probOff, double *d_logPerm,
+                                                   int32_t *d_info, int32_t *d_maxCluster, int32_t *d_label, int labelStride,
+                                                   void *stream)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    int rc = cluster_check_shape(ctx, B, maxRawRow, maxCol, "kbest_clustered_probs_batch_f64_dev");
+    if (rc != KBEST_OK) return rc;
+    if (!d_nL || !d_nM || !d_cost || !d_costOff || !d_probs || !d_probOff || (d_label && labelStride < maxCol))
+        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_clustered_probs_batch_f64_dev: bad argument");
+    if (B == 0) return KBEST_OK;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    kb::ClusterPlan pl;
+    rc = cluster_plan_of(ctx, maxRawRow, maxCol, pl, "kbest_clustered_probs_batch_f64_dev");
+    if (rc != KBEST_OK) return rc;
+    if (ctx->clusBuf.bytes < (size_t)pl.slotDoubles * 8)  // asynchronous entry: never allocates
+        return fail(ctx, KBEST_ERR_NOT_RESERVED, "kbest_clustered_probs_batch_f64_dev: call kbest_reserve_clustered first");
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = order_behind_last(ctx, s);  // (one work space per context)
+    if (rc != KBEST_OK) return rc;
+    const Launched mark{ctx, s};
+    kb::ClusterParams cp;
+    cp.cost = d_cost;
+    cp.costOff = reinterpret_cast<const long long *>(d_costOff);
+    cp.probOff = reinterpret_cast<const long long *>(d_probOff);
+    cp.nL = d_nL;
+    cp.nM = d_nM;
+    cp.probs = d_probs;
+    cp.logPerm = d_logPerm;
+    cp.info = d_info;
+    cp.maxCluster = d_maxCluster;
+    cp.label = d_label;
+    cp.work = static_cast<double *>(ctx->clusBuf.p);
+    cp.slotStride = pl.slotDoubles;
+    cp.slotBytes = pl.slotBytes;
+    cp.labelStride = d_label ? labelStride : 0;
+    cp.arenaBytes = pl.arena;
+    cp.B = B;
+    cp.maxRawRow = maxRawRow;
+    cp.maxCol = maxCol;
+    cp.condition = condition ? 1 : 0;
+    ctx->clusLastGrid = cluster_grid(ctx, pl, B, ctx->clusBuf.bytes);
+    const hipError_t e = kb::launch_kbest_cluster(cp, pl, ctx->clusLastGrid, s);
+    if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "clustered kernel launch", e);
+    return KBEST_OK;
+}
+
+extern "C" int kbest_clustered_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,
+                                               const int64_t *costOff, int condition, double *probs, const int64_t *probOff,
+                                               double *logPerm, int32_t *info, int32_t *maxCluster, int32_t *label, int labelStride)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    if (B < 0 || (B > 0 && (!nL || !nM || !cost || !costOff || !probs || !probOff)))
+        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_clustered_probs_batch_f64: bad argument");
+    if (B == 0) return KBEST_OK;
+    int maxRawRow = 1, maxCol = 1;
+    size_t costN = 0, probN = 0;
+    for (int b = 0; b < B; b++) {
+        if (nL[b] < 0 || nM[b] < 1 || costOff[b] < 0 || probOff[b] < 0)
+            return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_clustered_probs_batch_f64: a frame with nL < 0, nM < 1 or a negative offset");
+        const long long nr = (long long)nL[b] + nM[b];
+        if (nr > maxRawRow) maxRawRow = nr > (1 << 30) ? (1 << 30) : (int)nr;
+        if (nM[b] > maxCol) maxCol = nM[b];
+        const size_t ce = (size_t)costOff[b] + (size_t)nr * (size_t)nM[b], pe = (size_t)probOff[b] + (size_t)nM[b] * ((size_t)nL[b] + 1);
+        if (ce > costN) costN = ce;
+        if (pe > probN) probN = pe;
+    }
+    int rc = cluster_check_shape(ctx, B, maxRawRow, maxCol, "kbest_clustered_probs_batch_f64");
+    if (rc != KBEST_OK) return rc;
+    if (label && labelStride < maxCol) return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_clustered_probs_batch_f64: labelStride below the largest nM");
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = kbest_reserve_clustered(ctx, B, maxRawRow, maxCol);
+    if (rc != KBEST_OK) return rc;
+    DevBuf dCost, dMeta, dProbs, dOut, dLabel;
+    // meta: costOff[B] | probOff[B] (int64) | nL[B] | nM[B] (int32);  out: logPerm[B] (double) | info[B] | maxCluster[B] (int32)
+    std::vector<unsigned char> meta((size_t)B * 24);
+    memcpy(meta.data(), costOff, (size_t)B * 8);
+    memcpy(meta.data() + (size_t)B * 8, probOff, (size_t)B * 8);
+    memcpy(meta.data() + (size_t)B * 16, nL, (size_t)B * 4);
+    memcpy(meta.data() + (size_t)B * 20, nM, (size_t)B * 4);
+    const size_t labelBytes = label ? (size_t)B * (size_t)labelStride * 4 : 0;
+    hipError_t e;
+    if ((e = dCost.alloc(ctx, costN * 8)) != hipSuccess || (e = dMeta.alloc(ctx, meta.size())) != hipSuccess ||
+        (e = dProbs.alloc(ctx, probN * 8)) != hipSuccess || (e = dOut.alloc(ctx, (size_t)B * 16)) != hipSuccess ||
+        (labelBytes && (e = dLabel.alloc(ctx, labelBytes)) != hipSuccess))
+        return fail(ctx, KBEST_ERR_NOMEM, "kbest_clustered_probs_batch_f64: device buffers", e);
+    HIP_TRY(ctx, hipMemcpy(dCost.p, cost, costN * 8, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(dMeta.p, meta.data(), meta.size(), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemsetAsync(dProbs.p, 0, probN * 8, ctx->stream));
+    unsigned char *m8 = dMeta.as<unsigned char>(), *o8 = dOut.as<unsigned char>();
+    rc = kbest_clustered_probs_batch_f64_dev(ctx, B, maxRawRow, maxCol, reinterpret_cast<const int32_t *>(m8 + (size_t)B * 16),
+                                             reinterpret_cast<const int32_t *>(m8 + (size_t)B * 20), dCost.as<double>(),
+                                             reinterpret_cast<const int64_t *>(m8), condition, dProbs.as<double>(),
+                                             reinterpret_cast<const int64_t *>(m8 + (size_t)B * 8), reinterpret_cast<double *>(o8),
+                                             reinterpret_cast<int32_t *>(o8 + (size_t)B * 8),
+                                             reinterpret_cast<int32_t *>(o8 + (size_t)B * 12),
+                                             labelBytes ? dLabel.as<int32_t>() : nullptr, labelStride, nullptr);
+    if (rc != KBEST_OK) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    // every frame's own slice only: what lies between the slices in the caller's buffer is the caller's
+    std::vector<double> hp(probN);
+    HIP_TRY(ctx, hipMemcpy(hp.data(), dProbs.p, probN * 8, hipMemcpyDeviceToHost));
+    for (int b = 0; b < B; b++)
+        memcpy(probs + probOff[b], hp.data() + probOff[b], (size_t)nM[b] * ((size_t)nL[b] + 1) * 8);
+    if (logPerm) HIP_TRY(ctx, hipMemcpy(logPerm, o8, (size_t)B * 8, hipMemcpyDeviceToHost));
+    if (info) HIP_TRY(ctx, hipMemcpy(info, o8 + (size_t)B * 8, (size_t)B * 4, hipMemcpyDeviceToHost));
+    if (maxCluster) HIP_TRY(ctx, hipMemcpy(maxCluster, o8 + (size_t)B * 12, (size_t)B * 4, hipMemcpyDeviceToHost));
+    if (labelBytes) HIP_TRY(ctx, hipMemcpy(label, dLabel.p, labelBytes, hipMemcpyDeviceToHost));
     return KBEST_OK;
 }
 

@@ -579,6 +579,30 @@ struct LbpPlan {
 LbpPlan lbp_plan(int maxRawRow, int maxCol, int ldsLimit);
 hipError_t launch_kbest_lbp(const LbpParams &p, const LbpPlan &pl, int grid, hipStream_t stream);
 
+// kbest_cluster.hip: clusterProb, the exact association probabilities by gated clusters (frames of up to 128 measurements whose
+// clusters have at most 16)
+struct ClusterParams {
+    const double *cost;        // packed column-major (nL + nM) x nM blocks
+    const long long *costOff;  // [B]
+    const long long *probOff;  // [B]
+    const int *nL, *nM;        // [B]
+    double *probs;             // [nM][nL + 1] per frame
+    double *logPerm;           // [B] or nullptr: sum over the clusters of log Z_k; -inf: infeasible; NaN: refused
+    int *info;                 // [B] or nullptr: clusters; 0: infeasible; -1: beyond the launch's bounds; -2 / -3: refused
+    int *maxCluster;           // [B] or nullptr: columns of the frame's largest cluster
+    int *label;                // [B][labelStride] or nullptr: the lowest column of every column's cluster, -1 beyond nM
+    double *work;              // work space: slotStride doubles per workgroup of the launch
+    long long slotStride;      // maxRawRow * 16 doubles for a cluster's a, then slotBytes of layers
+    long long slotBytes;       // layers (R_k + 2) 2^m_k 8 bytes beyond it: the frame is refused (-3)
+    int labelStride, arenaBytes, B, maxRawRow, maxCol, condition;
+};
+struct ClusterPlan {
+    int threads, lds, arena;  // workgroup size, dynamic LDS bytes (-1: the device's LDS is too small), its part for layers
+    long long slotBytes, slotDoubles;
+};
+ClusterPlan cluster_plan(int maxRawRow, int maxCol, int ldsLimit, size_t slotCap);
+hipError_t launch_kbest_cluster(const ClusterParams &p, const ClusterPlan &pl, int grid, hipStream_t stream);
+
 }  // namespace kb
 
 // kbest_capi.cpp: completes the gain levels that straddle slot k in the caller's HOST tables (see there)

@@ -31,6 +31,8 @@ KBEST_MAX_DIM_WIDE = 1024  # rows of the general-size kernel (beyond KBEST_MAX_D
 KBEST_MAX_DIM_EXACT = 16384  # rows handled at all (the reference-order kernel beyond KBEST_MAX_DIM_WIDE)
 KBEST_PERM_MAX_COLS = 16     # measurements per frame of the exact (permanent) association probabilities
 KBEST_LBP_MAX_COLS = 128     # measurements per frame of the belief-propagation association probabilities
+KBEST_CLUSTER_MAX_COLS = 128  # measurements per frame of the clustered exact association probabilities
+KBEST_CLUSTER_MAX_SIZE = 16   # ... and per cluster
 
 # every symbol include/kbest_c.h declares
 C_ABI_SYMBOLS = (
@@ -48,6 +50,8 @@ C_ABI_SYMBOLS = (
     "kbest_set_reference_order", "kbest_permanent_probs_batch_f64", "kbest_permanent_probs_batch_f64_dev",
     "kbest_reserve_permanent", "kbest_set_permanent_work_cap", "kbest_last_permanent_grid",
     "kbest_belief_probs_batch_f64", "kbest_belief_probs_batch_f64_dev", "kbest_reserve_belief", "kbest_set_belief_lds_limit",
+    "kbest_clustered_probs_batch_f64", "kbest_clustered_probs_batch_f64_dev", "kbest_reserve_clustered",
+    "kbest_set_clustered_slot_cap", "kbest_set_clustered_work_cap", "kbest_last_clustered_grid",
 )
 KBEST_MULTI_STAMPS = 6
 KBEST_MULTI_BATCH, KBEST_MULTI_SUBTREE = 0, 1
@@ -154,6 +158,15 @@ def load_library():
                                                          C.c_int, dp, i64p, i32p, dp, vp]
         lib.kbest_reserve_belief.argtypes = [vp, C.c_int, C.c_int, C.c_int]
         lib.kbest_set_belief_lds_limit.argtypes = [vp, C.c_size_t]
+    if hasattr(lib, "kbest_clustered_probs_batch_f64"):
+        lib.kbest_clustered_probs_batch_f64.argtypes = [vp, C.c_int, i32p, i32p, dp, i64p, C.c_int, dp, i64p, dp, i32p, i32p, i32p,
+                                                        C.c_int]
+        lib.kbest_clustered_probs_batch_f64_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int, i32p, i32p, dp, i64p, C.c_int, dp, i64p,
+                                                            dp, i32p, i32p, i32p, C.c_int, vp]
+        lib.kbest_reserve_clustered.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+        lib.kbest_set_clustered_slot_cap.argtypes = [vp, C.c_size_t]
+        lib.kbest_set_clustered_work_cap.argtypes = [vp, C.c_size_t]
+        lib.kbest_last_clustered_grid.argtypes = [vp]
     lib.kbest_register_host_buffer.argtypes = [vp, vp, C.c_size_t]
     lib.kbest_unregister_host_buffer.argtypes = [vp, vp]
     _lib = lib
@@ -394,6 +407,65 @@ class KBestEngine:
         a low value keeps a and nu of small frames in the HBM work space -- the same results."""
         self._check(self.lib.kbest_set_belief_lds_limit(self.ctx, int(nbytes)))
 
+    def clustered_probs(self, costs, nL, nM, condition=False, labels=False):
+        """Batched clusterProb (kbest_cluster.hip): the EXACT association probabilities by gated clusters, nM <= 128 and
+        nL + nM <= 1024, clusters of at most 16 measurements.  Packing and condition as permanent_probs().  Returns (list of
+        [nM, nL+1] arrays, logPerm[B]: the sum of log Z_k over the clusters (-inf: infeasible, NaN: refused), info[B]: the number of
+        clusters, 0 for an infeasible frame, -2 / -3 for a refused one (all zeros), maxCluster[B]: measurements of the largest
+        cluster) and, with labels=True, label[B, max nM]: the lowest column of every column's cluster, -1 beyond the frame's nM."""
+        nL = np.ascontiguousarray(nL, dtype=np.int32)
+        nM = np.ascontiguousarray(nM, dtype=np.int32)
+        B = len(nL)
+        sizes = [(int(nL[b]) + int(nM[b])) * int(nM[b]) for b in range(B)]
+        psizes = [int(nM[b]) * (int(nL[b]) + 1) for b in range(B)]
+        costOff = np.zeros(B, np.int64)
+        probOff = np.zeros(B, np.int64)
+        costOff[1:] = np.cumsum(sizes)[:-1]
+        probOff[1:] = np.cumsum(psizes)[:-1]
+        flat = np.concatenate([np.ascontiguousarray(c, dtype=np.float64).reshape(-1) for c in costs])
+        if flat.size != sum(sizes):
+            raise KBestError("clustered_probs: a cost block is not (nL + nM) x nM")
+        probs = np.zeros(int(sum(psizes)), np.float64)
+        logPerm = np.zeros(B, np.float64)
+        info = np.zeros(B, np.int32)
+        maxCluster = np.zeros(B, np.int32)
+        stride = int(nM.max()) if B else 1
+        lab = np.full((B, stride), -1, np.int32) if labels else None
+        self._check(self.lib.kbest_clustered_probs_batch_f64(self.ctx, B, _ptr(nL), _ptr(nM), _ptr(flat), _ptr(costOff),
+                                                             int(bool(condition)), _ptr(probs), _ptr(probOff), _ptr(logPerm),
+                                                             _ptr(info), _ptr(maxCluster), _ptr(lab), stride))
+        out = [probs[probOff[b]: probOff[b] + psizes[b]].reshape(int(nM[b]), int(nL[b]) + 1) for b in range(B)]
+        return (out, logPerm, info, maxCluster, lab) if labels else (out, logPerm, info, maxCluster)
+
+    def exact_or_belief_probs(self, costs, nL, nM, condition=False, tol=1e-12, max_iter=10000):
+        """The exact probabilities wherever the gate leaves clusters of at most 16 measurements, belief propagation elsewhere:
+        clustered_probs() once, then belief_probs() on the refused frames only.  Returns (list of [nM, nL+1] arrays, method[B]:
+        0 exact, 1 belief propagation, -2 infeasible (all zeros))."""
+        out, _, info, _ = self.clustered_probs(costs, nL, nM, condition=condition)
+        method = np.where(info > 0, 0, np.where(info == 0, -2, 1)).astype(np.int32)
+        refused = [b for b in range(len(info)) if info[b] < 0]
+        if refused:
+            bp, iters, _ = self.belief_probs([costs[b] for b in refused], [int(nL[b]) for b in refused],
+                                             [int(nM[b]) for b in refused], condition=condition, tol=tol, max_iter=max_iter)
+            for j, b in enumerate(refused):
+                out[b] = bp[j]
+                if iters[j] == -2:
+                    method[b] = -2
+        return out, method
+
+    def set_clustered_slot_cap(self, nbytes=0):
+        """For tests (kbest_set_clustered_slot_cap): the layers of one cluster at the most, 0 = KBEST_CLUSTER_SLOT_CAP again; a frame
+        with a cluster that needs more is refused (info = -3)."""
+        self._check(self.lib.kbest_set_clustered_slot_cap(self.ctx, int(nbytes)))
+
+    def set_clustered_work_cap(self, nbytes=0):
+        """For tests (kbest_set_clustered_work_cap): cap of the clustered kernel's work space, 0 = KBEST_CLUSTER_WORK_CAP again."""
+        self._check(self.lib.kbest_set_clustered_work_cap(self.ctx, int(nbytes)))
+
+    def last_clustered_grid(self):
+        """Diagnostic (kbest_last_clustered_grid): workgroups -- frames in flight -- of this context's last clustered launch."""
+        return int(self.lib.kbest_last_clustered_grid(self.ctx))
+
     @staticmethod
     def _pack_quadrics(frames):
         """frames: list of (landMean (nL,3), landCov (nL,3,3), measMean (nM,3), measCov (nM,3,3))."""
@@ -558,6 +630,24 @@ class KBestEngine:
                                                               dp(d_probs), dp(d_probOff), dp(d_iters), dp(d_resid),
                                                               C.c_void_p(stream) if stream else None))
 
+    def reserve_clustered(self, B, maxRawRow, maxCol):
+        self._check(self.lib.kbest_reserve_clustered(self.ctx, B, maxRawRow, maxCol))
+
+    def clustered_probs_dev(self, B, maxRawRow, maxCol, d_nL, d_nM, d_cost, d_costOff, d_probs, d_probOff, d_logPerm=None,
+                            d_info=None, d_maxCluster=None, d_label=None, labelStride=0, condition=False, stream=None,
+                            reserve=True):
+        """kbest_clustered_probs_batch_f64_dev on torch CUDA tensors, asynchronous on `stream` (a raw hipStream_t integer): one
+        launch.  The work space is sized here (a no-op once it is large enough): the C entry never allocates.  reserve=False: the
+        caller has called reserve_clustered (timed loops: nothing but the C entry between two events)."""
+        def dp(t):
+            return None if t is None else C.c_void_p(t.data_ptr())
+        if reserve:
+            self.reserve_clustered(B, maxRawRow, maxCol)
+        self._check(self.lib.kbest_clustered_probs_batch_f64_dev(self.ctx, B, maxRawRow, maxCol, dp(d_nL), dp(d_nM), dp(d_cost),
+                                                                 dp(d_costOff), int(bool(condition)), dp(d_probs), dp(d_probOff),
+                                                                 dp(d_logPerm), dp(d_info), dp(d_maxCluster), dp(d_label),
+                                                                 int(labelStride), C.c_void_p(stream) if stream else None))
+
 
 class KBestMulti:
     """Multi-device engine of include/kbest_c.h: one context per GPU in ONE process, contiguous block sharding, RCCL
@@ -676,4 +766,14 @@ def beliefProb(costMatrix, nL, nM):
     """Not in the reference: the association probabilities by loopy belief propagation (tol 1e-12, at most 10 000 sweeps), for
     frames of up to 128 measurements.  Returns probs[nM][nL+1]; an infeasible frame comes back as all zeros."""
     out, _, _ = _engine().belief_probs([costMatrix], [nL], [nM])
+    return out[0]
+
+
+def clusterProb(costMatrix, nL, nM):
+    """Not in the reference: the EXACT association probabilities by gated clusters, for frames of up to 128 measurements whose
+    clusters have at most 16.  Returns probs[nM][nL+1]; raises RuntimeError naming the largest cluster when the frame is refused;
+    an infeasible frame comes back as all zeros."""
+    out, _, info, maxCluster = _engine().clustered_probs([costMatrix], [nL], [nM])
+    if info[0] < 0:
+        raise RuntimeError(f"clusterProb: frame refused (info {int(info[0])}): its largest cluster has {int(maxCluster[0])} measurements")
     return out[0]

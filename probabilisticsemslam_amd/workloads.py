@@ -98,3 +98,28 @@ def kitti_like_frames(F: int, nL: int = 20, nM: int = 10, seed: int = 0xC0FFEE, 
             C[c * nR + nL + c] = gate
         frames.append(C)
     return frames
+
+
+def scene_frames(F: int, nL: int, nM: int, side: float, seed: int = 0x5CE7E, gate: float = 10.0):
+    """Frames with geometry: nL landmarks uniform in a side x side square of the plane, measurement c scattered around landmark c
+    (+-1 in each coordinate; needs nM <= nL), cost = 4 x squared distance, dummy block +inf except C[nL+c, c] = gate.
+
+    per = 2 nL + 2 nM draws a frame from one splitmix64 stream (the first frames do not depend on F): the landmarks' (x, y) first,
+    then the measurements' offsets.  Returns a list of 1-D float64 arrays of length (nL+nM)*nM, column-major as kitti_like_frames.
+    """
+    if nM > nL:
+        raise ValueError("scene_frames: needs nM <= nL")
+    per = 2 * nL + 2 * nM
+    u = splitmix64_u01(seed, F * per).reshape(F, per)
+    nR = nL + nM
+    frames = []
+    for f in range(F):
+        L = side * u[f, : 2 * nL].reshape(nL, 2)
+        Z = L[:nM] + 2.0 * (u[f, 2 * nL:].reshape(nM, 2) - 0.5)
+        dx = Z[None, :, 0] - L[:, None, 0]  # [r, c]
+        dy = Z[None, :, 1] - L[:, None, 1]
+        block = np.full((nR, nM), INF)
+        block[:nL] = 4.0 * (dx * dx + dy * dy)
+        block[nL + np.arange(nM), np.arange(nM)] = gate
+        frames.append(np.ascontiguousarray(block.T).reshape(-1))
+    return frames
