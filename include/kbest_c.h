@@ -27,6 +27,7 @@
  *   kbest_belief_probs_batch_f64 / kbest_belief_probs_batch_f64_dev
  *        the association probabilities by loopy belief propagation, for frames of any size (not in the reference)
  *   kbest_clustered_probs_batch_f64 / kbest_clustered_probs_batch_f64_dev
+ *   kbest_hybrid_probs_batch_f64 / kbest_clustered_partial_batch_f64_dev
  *        the exact association probabilities by gated clusters, for frames of up to 128 measurements (not in the reference)
  *
  * Conventions kept from the reference: cost matrices are column-major
@@ -470,6 +471,52 @@ int kbest_set_clustered_slot_cap(kbest_ctx *ctx, size_t bytes);
 int kbest_set_clustered_work_cap(kbest_ctx *ctx, size_t bytes);
 /* Diagnostic, for tests: workgroups -- frames in flight -- of the context's last clustered launch (-1: null context). */
 int kbest_last_clustered_grid(kbest_ctx *ctx);
+
+/*
+ * Hybrid association probabilities (not in the reference): every gated frame of up to KBEST_CLUSTER_MAX_COLS measurements is
+ * answered -- exactly on every cluster the clustered kernel can take, by assignmentProb (kBest2DCutoff(k, 42) -> weights) on the
+ * clusters it cannot.  The marginals factorise over the clusters, and so does a k-best approximation: all k assignments are spent
+ * on the cluster that needs them.
+ *
+ * kbest_clustered_partial_batch_f64_dev: kbest_clustered_probs_batch_f64_dev in its PARTIAL mode (a second instantiation of the
+ * kernel; the plain entries do not run it).  maxExact (1 .. 16, 0 = 16): the largest cluster answered exactly.  A cluster of more
+ * columns, or one whose layers exceed the slot (the plain entry's -3), is OPEN: it does not refuse the frame.  The columns of every
+ * other cluster are bit-identical to kbest_clustered_probs_batch_f64, whatever maxExact is and whatever else is open; the
+ * columns of open clusters stay 0.0.  Per frame b (device buffers of the caller, all required):
+ *   d_nOpen[b]: its open clusters, in label order j = 0 .. nOpen - 1;
+ *   d_openDesc (int32 [B][descStride][4], descStride >= maxCol): { root label, m_k, nL_k, R_k } of open cluster j: its columns
+ *       are those with d_label[b][c] == root (ascending), nL_k of its R_k rows are landmarks (raw row < nL);
+ *   d_openRows (int32 [B][rowStride], rowStride >= maxRawRow): those landmark rows in the caller's numbering, ascending, cluster
+ *       after cluster (cluster j starts at the sum of nL_k' over j' < j);
+ *   d_sub (doubles, sized and addressed like d_cost): from d_costOff[b] on, cluster after cluster, the (nL_k + m_k) x m_k
+ *       column-major sub-block of open cluster j: the cluster's R_k rows in ascending raw order (its landmark rows first, then
+ *       its rows >= nL -- in the reference's layout the miss rows of its columns, in column order), then rows that are all +inf up
+ *       to nL_k + m_k; columns ascending.  An entry is the value toProbs is applied to -- the raw cost, x - colMin[c] with
+ *       condition = 1: the bits kbest_condition_costs_f64 gives -- and +inf wherever the frame's gate (block minimum + 42) makes a
+ *       zero.  The sum of (nL_k + m_k) m_k over a frame never exceeds (nL + nM) nM.  Nothing else of d_sub is written.
+ *   d_info[b]: the number of clusters, open ones included;  0: an ANSWERED cluster has Z_k = 0: zeros, logPerm -inf, nOpen 0 (what
+ *       was written to d_sub / d_openDesc / d_openRows before that was known stays);  -1: beyond the launch's bounds;  -2: an open
+ *       cluster holds more rows >= nL than columns (not the reference's block-diagonal layout): zeros, logPerm NaN, nOpen 0;
+ *   d_logPerm[b]: the sum over the answered clusters only;  d_maxCluster, d_label: as the plain entry.
+ * Asynchronous, never allocates or synchronises; needs kbest_reserve_clustered (the same work space and the same launch plan).
+ *
+ * kbest_hybrid_probs_batch_f64 (host buffers, synchronous): the partial kernel on the whole batch; the descriptors and ONLY the
+ * open clusters' sub-blocks come back; the open clusters of ALL frames go through kbest_weights_batch_f64's path as one batch (with
+ * the context's tie settings); their [m_k][nL_k + 1] probabilities are scattered into the frames on the host.
+ *   method[b]:  0: every cluster exact, the bits of kbest_clustered_probs_batch_f64;  1: some clusters enumerated and every
+ *       enumeration ended before k (nf < k): everything within the cutoff 42 was weighed;  2: some enumeration was cut at k;
+ *       -2: infeasible, zeros (an answered cluster with Z = 0 or an open one without an assignment);  -1: refused (d_info < 0);
+ *   nOpen, maxCluster (may be NULL): as above.  k < 1 or maxExact outside 0 .. 16: KBEST_ERR_BAD_ARG.
+ */
+int kbest_clustered_partial_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, const int32_t *d_nL,
+                                          const int32_t *d_nM, const double *d_cost, const int64_t *d_costOff, int condition,
+                                          int maxExact, double *d_probs, const int64_t *d_probOff, double *d_logPerm,
+                                          int32_t *d_info, int32_t *d_maxCluster, int32_t *d_label, int labelStride,
+                                          int32_t *d_nOpen, int32_t *d_openDesc, int descStride, int32_t *d_openRows, int rowStride,
+                                          double *d_sub, void *stream);
+int kbest_hybrid_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,
+                                 const int64_t *costOff, int condition, int k, int maxExact, double *probs, const int64_t *probOff,
+                                 int32_t *method, int32_t *nOpen, int32_t *maxCluster);
 /* on = 1: the HOST-buffer association entries of this context (kbest_weights / assoc_probs / bruteforce / quadric_assoc) enumerate
  * their k best in the REFERENCE's own order of operations (the reference-order kernel, as KBEST_FLAG_REFERENCE_ORDER does for
  * kbest_batch_f64): where exactly equal gains straddle slot k the assignments that are weighed are the ones the reference's

@@ -131,6 +131,12 @@ std::vector<std::vector<double>> beliefProb(const std::vector<double> &costMatri
 // std::runtime_error naming the largest cluster when the frame is refused; an infeasible frame comes back as all zeros.
 std::vector<std::vector<double>> clusterProb(const std::vector<double> &costMatrix, size_t nL, size_t nM);
 
+// Not in the reference: the hybrid association probabilities (kbest_hybrid_probs_batch_f64), [nM][nL+1] like assignmentProb, for
+// frames of up to 128 measurements and 1 024 rows: exact on every cluster of at most 16 measurements, assignmentProb(k) on the
+// larger ones alone.  Throws std::runtime_error only when the frame is refused (method -1: not the reference's layout of miss
+// rows); an infeasible frame comes back as all zeros.
+std::vector<std::vector<double>> hybridProb(const std::vector<double> &costMatrix, size_t nL, size_t nM, size_t k);
+
 // Not in the reference: the engine context behind the functions above (created on first use, GPU 0), for the entries of
 // kbest_c.h that take one -- e.g. kbest_last_tie_flags after a call.
 struct kbest_ctx;

@@ -3011,25 +3011,35 @@ extern "C" int kbest_reserve_clustered(kbest_ctx *ctx, int B, int maxRawRow, int
     return raw_reserve(ctx, ctx->clusBuf, (size_t)pl.slotDoubles * 8 * (size_t)g);
 }
 
-extern "C" int kbest_clustered_probs_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, const int32_t *d_nL,
-                                                   const int32_t *d_nM, const double *d_cost, const int64_t *d_costOff,
-                                                   int condition, double *d_probs, const int64_t *d_probOff, double *d_logPerm,
-                                                   int32_t *d_info, int32_t *d_maxCluster, int32_t *d_label, int labelStride,
-                                                   void *stream)
+// the partial mode's own arguments (kbest_clustered_partial_batch_f64_dev); nullptr: the plain entry
+struct ClusterPartialArgs {
+    int maxExact;
+    int32_t *d_nOpen, *d_openDesc, *d_openRows;
+    int descStride, rowStride;
+    double *d_sub;
+};
+
+static int cluster_launch_dev(kbest_ctx *ctx, const char *who, const ClusterPartialArgs *part, int B, int maxRawRow, int maxCol,
+                              const int32_t *d_nL, const int32_t *d_nM, const double *d_cost, const int64_t *d_costOff, int condition,
+                              double *d_probs, const int64_t *d_probOff, double *d_logPerm, int32_t *d_info, int32_t *d_maxCluster,
+                              int32_t *d_label, int labelStride, void *stream)
 {
     if (!ctx) return KBEST_ERR_BAD_ARG;
-    int rc = cluster_check_shape(ctx, B, maxRawRow, maxCol, "kbest_clustered_probs_batch_f64_dev");
+    int rc = cluster_check_shape(ctx, B, maxRawRow, maxCol, who);
     if (rc != KBEST_OK) return rc;
     if (!d_nL || !d_nM || !d_cost || !d_costOff || !d_probs || !d_probOff || (d_label && labelStride < maxCol))
-        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_clustered_probs_batch_f64_dev: bad argument");
+        return fail(ctx, KBEST_ERR_BAD_ARG, (std::string(who) + ": bad argument").c_str());
+    if (part && (part->maxExact < 0 || part->maxExact > KBEST_CLUSTER_MAX_SIZE || !part->d_nOpen || !part->d_openDesc ||
+                 !part->d_openRows || !part->d_sub || part->descStride < maxCol || part->rowStride < maxRawRow))
+        return fail(ctx, KBEST_ERR_BAD_ARG, (std::string(who) + ": bad argument (maxExact 0 .. 16, descStride >= maxCol, rowStride >= maxRawRow)").c_str());
     if (B == 0) return KBEST_OK;
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     kb::ClusterPlan pl;
-    rc = cluster_plan_of(ctx, maxRawRow, maxCol, pl, "kbest_clustered_probs_batch_f64_dev");
+    rc = cluster_plan_of(ctx, maxRawRow, maxCol, pl, who);
     if (rc != KBEST_OK) return rc;
     if (ctx->clusBuf.bytes < (size_t)pl.slotDoubles * 8)  // asynchronous entry: never allocates
-        return fail(ctx, KBEST_ERR_NOT_RESERVED, "kbest_clustered_probs_batch_f64_dev: call kbest_reserve_clustered first");
+        return fail(ctx, KBEST_ERR_NOT_RESERVED, (std::string(who) + ": call kbest_reserve_clustered first").c_str());
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
     rc = order_behind_last(ctx, s);  // (one work space per context)
     if (rc != KBEST_OK) return rc;
@@ -3054,10 +3064,43 @@ extern "C" int kbest_clustered_probs_batch_f64_dev(kbest_ctx *ctx, int B, int ma
     cp.maxRawRow = maxRawRow;
     cp.maxCol = maxCol;
     cp.condition = condition ? 1 : 0;
+    kb::ClusterOpenParams op{};
+    if (part) {
+        op.maxExact = part->maxExact ? part->maxExact : KBEST_CLUSTER_MAX_SIZE;
+        op.descStride = part->descStride;
+        op.rowStride = part->rowStride;
+        op.nOpen = part->d_nOpen;
+        op.openDesc = part->d_openDesc;
+        op.openRows = part->d_openRows;
+        op.sub = part->d_sub;
+    }
     ctx->clusLastGrid = cluster_grid(ctx, pl, B, ctx->clusBuf.bytes);
-    const hipError_t e = kb::launch_kbest_cluster(cp, pl, ctx->clusLastGrid, s);
+    const hipError_t e = part ? kb::launch_kbest_cluster_partial(cp, op, pl, ctx->clusLastGrid, s)
+                              : kb::launch_kbest_cluster(cp, pl, ctx->clusLastGrid, s);
     if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "clustered kernel launch", e);
     return KBEST_OK;
+}
+
+extern "C" int kbest_clustered_probs_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, const int32_t *d_nL,
+                                                   const int32_t *d_nM, const double *d_cost, const int64_t *d_costOff,
+                                                   int condition, double *d_probs, const int64_t *d_probOff, double *d_logPerm,
+                                                   int32_t *d_info, int32_t *d_maxCluster, int32_t *d_label, int labelStride,
+                                                   void *stream)
+{
+    return cluster_launch_dev(ctx, "kbest_clustered_probs_batch_f64_dev", nullptr, B, maxRawRow, maxCol, d_nL, d_nM, d_cost, d_costOff,
+                              condition, d_probs, d_probOff, d_logPerm, d_info, d_maxCluster, d_label, labelStride, stream);
+}
+
+extern "C" int kbest_clustered_partial_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, const int32_t *d_nL,
+                                                     const int32_t *d_nM, const double *d_cost, const int64_t *d_costOff,
+                                                     int condition, int maxExact, double *d_probs, const int64_t *d_probOff,
+                                                     double *d_logPerm, int32_t *d_info, int32_t *d_maxCluster, int32_t *d_label,
+                                                     int labelStride, int32_t *d_nOpen, int32_t *d_openDesc, int descStride,
+                                                     int32_t *d_openRows, int rowStride, double *d_sub, void *stream)
+{
+    const ClusterPartialArgs part{maxExact, d_nOpen, d_openDesc, d_openRows, descStride, rowStride, d_sub};
+    return cluster_launch_dev(ctx, "kbest_clustered_partial_batch_f64_dev", &part, B, maxRawRow, maxCol, d_nL, d_nM, d_cost, d_costOff,
+                              condition, d_probs, d_probOff, d_logPerm, d_info, d_maxCluster, d_label, labelStride, stream);
 }
 
 extern "C" int kbest_clustered_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,
@@ -3484,6 +3527,149 @@ int kbest_weights_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int3
                             const int64_t *costOff, int k, double *probs, const int64_t *probOff, int32_t *nf)
 {
     return weights_entry(ctx, B, nL, nM, cost, costOff, k, probs, probOff, nf, false, nullptr, false);
+}
+
+// hybridProb: the partial clustered kernel on the whole batch, then the open clusters of all frames as ONE batch through the
+// assignmentProb path (weights_entry, condition = false: kBest2DCutoff(k, 42) -> weights), scattered back on the host.
+int kbest_hybrid_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,
+                                 const int64_t *costOff, int condition, int k, int maxExact, double *probs, const int64_t *probOff,
+                                 int32_t *method, int32_t *nOpen, int32_t *maxCluster)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    if (B < 0 || k < 1 || maxExact < 0 || maxExact > KBEST_CLUSTER_MAX_SIZE ||
+        (B > 0 && (!nL || !nM || !cost || !costOff || !probs || !probOff || !method)))
+        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_hybrid_probs_batch_f64: bad argument (k >= 1, maxExact 0 .. 16)");
+    if (B == 0) return KBEST_OK;
+    int maxRawRow = 1, maxCol = 1;
+    size_t costN = 0, probN = 0;
+    for (int b = 0; b < B; b++) {
+        if (nL[b] < 0 || nM[b] < 1 || costOff[b] < 0 || probOff[b] < 0)
+            return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_hybrid_probs_batch_f64: a frame with nL < 0, nM < 1 or a negative offset");
+        const long long nr = (long long)nL[b] + nM[b];
+        if (nr > maxRawRow) maxRawRow = nr > (1 << 30) ? (1 << 30) : (int)nr;
+        if (nM[b] > maxCol) maxCol = nM[b];
+        const size_t ce = (size_t)costOff[b] + (size_t)nr * (size_t)nM[b], pe = (size_t)probOff[b] + (size_t)nM[b] * ((size_t)nL[b] + 1);
+        if (ce > costN) costN = ce;
+        if (pe > probN) probN = pe;
+    }
+    int rc = cluster_check_shape(ctx, B, maxRawRow, maxCol, "kbest_hybrid_probs_batch_f64");
+    if (rc != KBEST_OK) return rc;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = kbest_reserve_clustered(ctx, B, maxRawRow, maxCol);
+    if (rc != KBEST_OK) return rc;
+    std::vector<double> hp(probN);
+    std::vector<int32_t> hInt((size_t)B * 3), hDesc, hRows, hLabel;  // info | maxCluster | nOpen
+    struct Open { int b, root, m, cL; size_t rowAt; };
+    std::vector<Open> open;
+    std::vector<double> sub;      // the open clusters' sub-blocks, packed
+    std::vector<int64_t> sCo, sPo;
+    const size_t descStride = (size_t)maxCol, rowStride = (size_t)maxRawRow;
+    {
+        DevBuf dCost, dMeta, dProbs, dOut, dLabel, dDesc, dRows, dSub;
+        // meta: costOff[B] | probOff[B] (int64) | nL[B] | nM[B] (int32);  out: info[B] | maxCluster[B] | nOpen[B] (int32)
+        std::vector<unsigned char> meta((size_t)B * 24);
+        memcpy(meta.data(), costOff, (size_t)B * 8);
+        memcpy(meta.data() + (size_t)B * 8, probOff, (size_t)B * 8);
+        memcpy(meta.data() + (size_t)B * 16, nL, (size_t)B * 4);
+        memcpy(meta.data() + (size_t)B * 20, nM, (size_t)B * 4);
+        hipError_t e;
+        if ((e = dCost.alloc(ctx, costN * 8)) != hipSuccess || (e = dMeta.alloc(ctx, meta.size())) != hipSuccess ||
+            (e = dProbs.alloc(ctx, probN * 8)) != hipSuccess || (e = dOut.alloc(ctx, (size_t)B * 12)) != hipSuccess ||
+            (e = dLabel.alloc(ctx, (size_t)B * maxCol * 4)) != hipSuccess || (e = dDesc.alloc(ctx, (size_t)B * descStride * 16)) != hipSuccess ||
+            (e = dRows.alloc(ctx, (size_t)B * rowStride * 4)) != hipSuccess || (e = dSub.alloc(ctx, costN * 8)) != hipSuccess)
+            return fail(ctx, KBEST_ERR_NOMEM, "kbest_hybrid_probs_batch_f64: device buffers", e);
+        HIP_TRY(ctx, hipMemcpy(dCost.p, cost, costN * 8, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(dMeta.p, meta.data(), meta.size(), hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemsetAsync(dProbs.p, 0, probN * 8, ctx->stream));
+        unsigned char *m8 = dMeta.as<unsigned char>();
+        int32_t *o4 = dOut.as<int32_t>();
+        rc = kbest_clustered_partial_batch_f64_dev(ctx, B, maxRawRow, maxCol, reinterpret_cast<const int32_t *>(m8 + (size_t)B * 16),
+                                                   reinterpret_cast<const int32_t *>(m8 + (size_t)B * 20), dCost.as<double>(),
+                                                   reinterpret_cast<const int64_t *>(m8), condition, maxExact, dProbs.as<double>(),
+                                                   reinterpret_cast<const int64_t *>(m8 + (size_t)B * 8), nullptr, o4, o4 + B,
+                                                   dLabel.as<int32_t>(), maxCol, o4 + 2 * (size_t)B, dDesc.as<int32_t>(),
+                                                   (int)descStride, dRows.as<int32_t>(), (int)rowStride, dSub.as<double>(), nullptr);
+        if (rc != KBEST_OK) return rc;
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, hipMemcpy(hp.data(), dProbs.p, probN * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(hInt.data(), dOut.p, (size_t)B * 12, hipMemcpyDeviceToHost));
+        const int32_t *hOpen = hInt.data() + 2 * (size_t)B;
+        bool any = false;
+        for (int b = 0; b < B; b++) any = any || hOpen[b] > 0;
+        if (any) {  // the descriptors (small), then the sub-blocks of the frames that have open clusters and nothing else
+            hDesc.resize((size_t)B * descStride * 4);
+            hRows.resize((size_t)B * rowStride);
+            hLabel.resize((size_t)B * maxCol);
+            HIP_TRY(ctx, hipMemcpy(hDesc.data(), dDesc.p, hDesc.size() * 4, hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(hRows.data(), dRows.p, hRows.size() * 4, hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(hLabel.data(), dLabel.p, hLabel.size() * 4, hipMemcpyDeviceToHost));
+            size_t total = 0;
+            for (int b = 0; b < B; b++)
+                for (int j = 0; j < hOpen[b]; j++) {
+                    const int32_t *d = hDesc.data() + ((size_t)b * descStride + j) * 4;
+                    total += (size_t)(d[2] + d[1]) * d[1];
+                }
+            sub.resize(total);
+            size_t at = 0, pat = 0;
+            for (int b = 0; b < B; b++) {
+                if (hOpen[b] <= 0) continue;
+                size_t n = 0, rowAt = (size_t)b * rowStride;
+                for (int j = 0; j < hOpen[b]; j++) {
+                    const int32_t *d = hDesc.data() + ((size_t)b * descStride + j) * 4;
+                    open.push_back(Open{b, d[0], d[1], d[2], rowAt});
+                    sCo.push_back((int64_t)(at + n));
+                    sPo.push_back((int64_t)pat);
+                    n += (size_t)(d[2] + d[1]) * d[1];
+                    pat += (size_t)d[1] * ((size_t)d[2] + 1);
+                    rowAt += (size_t)d[2];
+                }
+                HIP_TRY(ctx, hipMemcpy(sub.data() + at, dSub.as<double>() + costOff[b], n * 8, hipMemcpyDeviceToHost));
+                at += n;
+            }
+        }
+    }
+    const int32_t *hInfo = hInt.data(), *hOpen = hInt.data() + 2 * (size_t)B;
+    for (int b = 0; b < B; b++) method[b] = hInfo[b] < 0 ? -1 : hInfo[b] == 0 ? -2 : 0;
+    if (!open.empty()) {
+        const int S = (int)open.size();
+        std::vector<int32_t> sL(S), sM(S), sNf(S, 0);
+        size_t pn = 0;
+        for (int i = 0; i < S; i++) {
+            sL[i] = open[i].cL;
+            sM[i] = open[i].m;
+            pn += (size_t)open[i].m * ((size_t)open[i].cL + 1);
+        }
+        std::vector<double> sp(pn, 0.0);
+        rc = weights_entry(ctx, S, sL.data(), sM.data(), sub.data(), sCo.data(), k, sp.data(), sPo.data(), sNf.data(), false, nullptr, false);
+        if (rc != KBEST_OK) return rc;
+        for (int i = 0; i < S; i++) {  // slot nL_k -> slot nL, landmark rows through the row list, columns through the labels
+            const Open &o = open[i];
+            const int b = o.b;
+            if (sNf[i] <= 0) method[b] = -2;
+            else if (method[b] >= 0) method[b] = (sNf[i] >= k || method[b] == 2) ? 2 : 1;
+            double *fp = hp.data() + probOff[b];
+            const double *q = sp.data() + sPo[i];
+            const int32_t *lab = hLabel.data() + (size_t)b * maxCol, *rows = hRows.data() + o.rowAt;
+            int j = 0;
+            for (int c = 0; c < nM[b] && j < o.m; c++) {
+                if (lab[c] != o.root) continue;
+                double *col = fp + (size_t)c * ((size_t)nL[b] + 1);
+                for (int r = 0; r < o.cL; r++) col[rows[r]] = q[(size_t)j * (o.cL + 1) + r];
+                col[nL[b]] = q[(size_t)j * (o.cL + 1) + o.cL];
+                j++;
+            }
+        }
+        for (int b = 0; b < B; b++)
+            if (method[b] == -2 && hOpen[b] > 0)  // an open cluster without a feasible assignment: the whole frame is zeros
+                std::fill(hp.begin() + probOff[b], hp.begin() + probOff[b] + (size_t)nM[b] * ((size_t)nL[b] + 1), 0.0);
+    }
+    // every frame's own slice only: what lies between the slices in the caller's buffer is the caller's
+    for (int b = 0; b < B; b++)
+        memcpy(probs + probOff[b], hp.data() + probOff[b], (size_t)nM[b] * ((size_t)nL[b] + 1) * 8);
+    if (nOpen) memcpy(nOpen, hOpen, (size_t)B * 4);
+    if (maxCluster) memcpy(maxCluster, hInt.data() + B, (size_t)B * 4);
+    return KBEST_OK;
 }
 
 int kbest_bruteforce_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,

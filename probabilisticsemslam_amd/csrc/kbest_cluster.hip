@@ -29,6 +29,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <type_traits>
 
 #include "kbest_engine.h"
 #include "kbest_wave.h"
@@ -129,7 +130,46 @@ __device__ __forceinline__ bool cl_nonzero(const double *Cg, int NR, int c, int 
     return mn + CL_GATE > x;
 }
 
-__global__ void __launch_bounds__(512) kbest_cluster_kernel(ClusterParams p)
+// The partial mode hands one open cluster out: its (nLk + m) x m column-major sub-block -- the cluster's
+// rows in ascending raw order (the nLk landmark rows first), then all-+inf rows up to nLk + m; its columns ascending; the value
+// cl_entry forms before the exp, +inf where cl_nonzero is false -- and its landmark rows in the caller's numbering.  Every thread
+// of the workgroup calls it; eCol (LDS) takes the cluster's columns.  Kept out of line: the sweeps' registers are not its.
+__device__ __noinline__ void cl_emit_open(const double *Cg, int NR, int M, bool cond, const double *colMin, double mn, const int *label,
+                                          int root, const unsigned short *rawRow, const unsigned short *rows, int R, int m, int nLk,
+                                          int *eCol, double *sub, int *rowOut)
+{
+    const int tid = threadIdx.x, NT = blockDim.x;
+    for (int c = tid; c < M; c += NT)
+        if (label[c] == root) {
+            int rank = 0;
+            for (int j = 0; j < c; j++) rank += (label[j] == root) ? 1 : 0;
+            eCol[rank] = c;
+        }
+    __syncthreads();
+    const int nr = nLk + m;
+    for (int i = tid; i < nr * m; i += NT) {
+        const int j = i / nr, r = i - j * nr;
+        double v = d_inf();
+        if (r < R) {
+            const int c = eCol[j];
+            double x = Cg[(long long)c * NR + rawRow[rows[r]]];
+            if (cond) x = (x <= colMin[c] + CL_GATE) ? (x - colMin[c]) : d_inf();
+            v = (mn + CL_GATE > x) ? x : d_inf();
+        }
+        sub[i] = v;
+    }
+    for (int r = tid; r < nLk; r += NT) rowOut[r] = rawRow[rows[r]];
+    __syncthreads();
+}
+
+// PARTIAL = false: every existing entry.  PARTIAL = true (kbest_clustered_partial_batch_f64_dev): a cluster of more than
+// q.maxExact columns, or whose layers exceed the slot, is OPEN: it does not refuse the frame, its columns stay 0.0 and its
+// sub-problem is handed out; every other cluster goes through the same tiers, the same sums, the same bits.
+struct ClusterNoOpen {};  // the plain kernel's second argument: nothing
+
+template <bool PARTIAL>
+__global__ void __launch_bounds__(512)
+kbest_cluster_kernel(ClusterParams p, [[maybe_unused]] std::conditional_t<PARTIAL, ClusterOpenParams, ClusterNoOpen> q)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     const int tid = threadIdx.x, NT = blockDim.x, lane = tid & 63, wave = tid >> 6, NWV = NT >> 6;
@@ -167,6 +207,8 @@ __global__ void __launch_bounds__(512) kbest_cluster_kernel(ClusterParams p)
         // (uniform over the workgroup) a frame beyond what the launch was sized for: info = -1 and nothing else is touched
         if (M < 1 || M > p.maxCol || M > CL_MAX_COLS || nLo < 0 || NR > p.maxRawRow) {
             if (tid == 0 && p.info) p.info[b] = -1;
+            if constexpr (PARTIAL)
+                if (tid == 0) q.nOpen[b] = 0;
             continue;
         }
         for (int i = tid; i < M * (nLo + 1); i += NT) probOut[i] = 0.0;  // (rows conditionCosts drops, zero rows: exactly 0.0)
@@ -285,6 +327,7 @@ __global__ void __launch_bounds__(512) kbest_cluster_kernel(ClusterParams p)
         __syncthreads();
         if (tid == 0) {  // (at most 128 columns: one thread)
             int n = 0, at = 0, maxC = 0, refuse = 0;
+            [[maybe_unused]] int nOpenT = 0;
             for (int c = 0; c < M; c++)
                 if (label[c] == c) {
                     const int m = csize[c], R = crows[c];
@@ -292,12 +335,20 @@ __global__ void __launch_bounds__(512) kbest_cluster_kernel(ClusterParams p)
                     cstart[c] = at;
                     at += R;
                     if (m > maxC) maxC = m;
-                    if (m > CL_MAX_SIZE) refuse = -2;
-                    else if (refuse == 0 && ((long long)(R + 2) << m) * 8 > p.slotBytes) refuse = -3;
+                    if constexpr (PARTIAL) {  // answered clusters from the front of clist, open ones from its back: both in label order
+                        if (m > q.maxExact || ((long long)(R + 2) << m) * 8 > p.slotBytes) {
+                            n--;
+                            clist[M - 1 - nOpenT++] = c;
+                        }
+                    } else {
+                        if (m > CL_MAX_SIZE) refuse = -2;
+                        else if (refuse == 0 && ((long long)(R + 2) << m) * 8 > p.slotBytes) refuse = -3;
+                    }
                 }
             ctl[2] = n;
             ctl[3] = maxC;
             ctl[4] = refuse;
+            if constexpr (PARTIAL) ctl[6] = nOpenT;
         }
         __syncthreads();
         const int nClus = ctl[2], refuse = ctl[4];
@@ -319,6 +370,55 @@ __global__ void __launch_bounds__(512) kbest_cluster_kernel(ClusterParams p)
             rowList[cstart[root] + rank] = act[i];
         }
         __syncthreads();
+        [[maybe_unused]] int nOpen = 0;
+        if constexpr (PARTIAL) {
+            // ---- the open clusters, in label order: their landmark rows counted, their places in the outputs, then handed out ---------
+            nOpen = ctl[6];
+            int *eNL = reinterpret_cast<int *>(red), *eRowOff = eNL + CL_MAX_COLS, *eCol = eRowOff + CL_MAX_COLS;  // (red: free until
+            long long *eSubOff = reinterpret_cast<long long *>(eCol + CL_MAX_COLS);                               //  the sweeps)
+            for (int j = tid; j < nOpen; j += NT) {
+                const int root = clist[M - 1 - j], R = crows[root], st = cstart[root];
+                int n = 0;
+                for (int r = 0; r < R; r++) n += (rawRow[rowList[st + r]] < nLo) ? 1 : 0;
+                eNL[j] = n;
+            }
+            __syncthreads();
+            if (tid == 0) {
+                int rowAt = 0, layout = 0;
+                long long subAt = 0;
+                for (int j = 0; j < nOpen; j++) {
+                    const int root = clist[M - 1 - j], m = csize[root];
+                    if (crows[root] - eNL[j] > m) layout = -2;  // more rows >= nL than columns: not the reference's layout
+                    eRowOff[j] = rowAt;
+                    eSubOff[j] = subAt;
+                    rowAt += eNL[j];
+                    subAt += (long long)(eNL[j] + m) * m;
+                }
+                ctl[4] = layout;
+            }
+            __syncthreads();
+            if (ctl[4] != 0) {  // (uniform) refused as a whole: zeros, nothing handed out
+                if (tid == 0) {
+                    if (p.info) p.info[b] = ctl[4];
+                    if (p.logPerm) p.logPerm[b] = __longlong_as_double(0x7ff8000000000000LL);
+                    q.nOpen[b] = 0;
+                }
+                __syncthreads();
+                continue;
+            }
+            for (int j = 0; j < nOpen; j++) {  // (uniform)
+                const int root = clist[M - 1 - j], m = csize[root];
+                if (tid == 0) {
+                    int *d = q.openDesc + ((long long)b * q.descStride + j) * 4;
+                    d[0] = root;
+                    d[1] = m;
+                    d[2] = eNL[j];
+                    d[3] = crows[root];
+                }
+                cl_emit_open(Cg, NR, M, cond, colMin, mn, label, root, rawRow, rowList + cstart[root], crows[root], m, eNL[j], eCol,
+                             q.sub + p.costOff[b] + eSubOff[j], q.openRows + (long long)b * q.rowStride + eRowOff[j]);
+            }
+        }
 
         // ---- the small clusters: one wave each, side by side, no workgroup barrier ------------------------------------------------
         for (int k = wave; k < nClus; k += NWV) {
@@ -544,7 +644,12 @@ __global__ void __launch_bounds__(512) kbest_cluster_kernel(ClusterParams p)
             double lp = 0.0;
             for (int k = 0; k < nClus; k++) lp = lp + logZ[k];
             if (p.logPerm) p.logPerm[b] = bad ? -INF : lp;
-            if (p.info) p.info[b] = bad ? 0 : nClus;
+            if constexpr (PARTIAL) {
+                if (p.info) p.info[b] = bad ? 0 : nClus + nOpen;
+                q.nOpen[b] = bad ? 0 : nOpen;
+            } else {
+                if (p.info) p.info[b] = bad ? 0 : nClus;
+            }
         }
         __syncthreads();
     }
@@ -583,12 +688,28 @@ hipError_t launch_kbest_cluster(const ClusterParams &p, const ClusterPlan &pl, i
     int dev = 0;
     (void)hipGetDevice(&dev);
     if (pl.lds > granted[dev & 15].load(std::memory_order_relaxed)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kbest_cluster_kernel),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kbest_cluster_kernel<false>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
         if (e != hipSuccess) return e;
         granted[dev & 15].store(pl.lds, std::memory_order_relaxed);
     }
-    hipLaunchKernelGGL(kbest_cluster_kernel, dim3(grid), dim3(pl.threads), pl.lds, stream, p);
+    hipLaunchKernelGGL(kbest_cluster_kernel<false>, dim3(grid), dim3(pl.threads), pl.lds, stream, p, ClusterNoOpen{});
+    return hipGetLastError();
+}
+
+hipError_t launch_kbest_cluster_partial(const ClusterParams &p, const ClusterOpenParams &q, const ClusterPlan &pl, int grid,
+                                        hipStream_t stream)
+{
+    static std::atomic<int> granted[16];
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (pl.lds > granted[dev & 15].load(std::memory_order_relaxed)) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kbest_cluster_kernel<true>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
+        if (e != hipSuccess) return e;
+        granted[dev & 15].store(pl.lds, std::memory_order_relaxed);
+    }
+    hipLaunchKernelGGL(kbest_cluster_kernel<true>, dim3(grid), dim3(pl.threads), pl.lds, stream, p, q);
     return hipGetLastError();
 }
 

@@ -596,12 +596,23 @@ struct ClusterParams {
     long long slotBytes;       // layers (R_k + 2) 2^m_k 8 bytes beyond it: the frame is refused (-3)
     int labelStride, arenaBytes, B, maxRawRow, maxCol, condition;
 };
+// the partial mode's own arguments (launch_kbest_cluster_partial; kbest_c.h, "Hybrid association probabilities")
+struct ClusterOpenParams {
+    int maxExact;              // 1 .. 16: a cluster of more columns is open
+    int descStride, rowStride; // >= the largest nM; >= the largest nL
+    int *nOpen;                // [B]: open clusters of the frame
+    int *openDesc;             // [B][descStride][4]: root label, m_k, nL_k, R_k of every open cluster, in label order
+    int *openRows;             // [B][rowStride]: their landmark rows (caller numbering, ascending), one cluster after another
+    double *sub;               // shaped like cost: their (nL_k + m_k) x m_k sub-blocks, one after another from costOff[b]
+};
 struct ClusterPlan {
     int threads, lds, arena;  // workgroup size, dynamic LDS bytes (-1: the device's LDS is too small), its part for layers
     long long slotBytes, slotDoubles;
 };
 ClusterPlan cluster_plan(int maxRawRow, int maxCol, int ldsLimit, size_t slotCap);
 hipError_t launch_kbest_cluster(const ClusterParams &p, const ClusterPlan &pl, int grid, hipStream_t stream);
+hipError_t launch_kbest_cluster_partial(const ClusterParams &p, const ClusterOpenParams &q, const ClusterPlan &pl, int grid,
+                                        hipStream_t stream);
 
 }  // namespace kb
 

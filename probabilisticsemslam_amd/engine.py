@@ -52,6 +52,7 @@ C_ABI_SYMBOLS = (
     "kbest_belief_probs_batch_f64", "kbest_belief_probs_batch_f64_dev", "kbest_reserve_belief", "kbest_set_belief_lds_limit",
     "kbest_clustered_probs_batch_f64", "kbest_clustered_probs_batch_f64_dev", "kbest_reserve_clustered",
     "kbest_set_clustered_slot_cap", "kbest_set_clustered_work_cap", "kbest_last_clustered_grid",
+    "kbest_clustered_partial_batch_f64_dev", "kbest_hybrid_probs_batch_f64",
 )
 KBEST_MULTI_STAMPS = 6
 KBEST_MULTI_BATCH, KBEST_MULTI_SUBTREE = 0, 1
@@ -167,6 +168,12 @@ def load_library():
         lib.kbest_set_clustered_slot_cap.argtypes = [vp, C.c_size_t]
         lib.kbest_set_clustered_work_cap.argtypes = [vp, C.c_size_t]
         lib.kbest_last_clustered_grid.argtypes = [vp]
+    if hasattr(lib, "kbest_hybrid_probs_batch_f64"):
+        lib.kbest_clustered_partial_batch_f64_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int, i32p, i32p, dp, i64p, C.c_int, C.c_int,
+                                                              dp, i64p, dp, i32p, i32p, i32p, C.c_int, i32p, i32p, C.c_int, i32p,
+                                                              C.c_int, dp, vp]
+        lib.kbest_hybrid_probs_batch_f64.argtypes = [vp, C.c_int, i32p, i32p, dp, i64p, C.c_int, C.c_int, C.c_int, dp, i64p, i32p,
+                                                     i32p, i32p]
     lib.kbest_register_host_buffer.argtypes = [vp, vp, C.c_size_t]
     lib.kbest_unregister_host_buffer.argtypes = [vp, vp]
     _lib = lib
@@ -440,7 +447,8 @@ class KBestEngine:
     def exact_or_belief_probs(self, costs, nL, nM, condition=False, tol=1e-12, max_iter=10000):
         """The exact probabilities wherever the gate leaves clusters of at most 16 measurements, belief propagation elsewhere:
         clustered_probs() once, then belief_probs() on the refused frames only.  Returns (list of [nM, nL+1] arrays, method[B]:
-        0 exact, 1 belief propagation, -2 infeasible (all zeros))."""
+        0 exact, 1 belief propagation, -2 infeasible (all zeros)).  hybrid_probs() is the better answer for the refused frames:
+        it keeps every cluster it can take exact and spends a k-best enumeration on the oversized one alone."""
         out, _, info, _ = self.clustered_probs(costs, nL, nM, condition=condition)
         method = np.where(info > 0, 0, np.where(info == 0, -2, 1)).astype(np.int32)
         refused = [b for b in range(len(info)) if info[b] < 0]
@@ -452,6 +460,35 @@ class KBestEngine:
                 if iters[j] == -2:
                     method[b] = -2
         return out, method
+
+    def hybrid_probs(self, costs, nL, nM, k, condition=False, max_exact=16):
+        """Batched hybridProb (kbest_hybrid_probs_batch_f64): exact on every gated cluster of at most max_exact (1 .. 16, 0 = 16)
+        measurements, assignmentProb(k) -- kBest2DCutoff(k, 42) -> weights -- on each larger cluster alone; nM <= 128 and
+        nL + nM <= 1024.  Packing and condition as permanent_probs().  Returns (list of [nM, nL+1] arrays, method[B]: 0 every
+        cluster exact (the bits of clustered_probs), 1 some clusters enumerated and every enumeration ended before k, 2 some
+        enumeration cut at k, -2 infeasible (all zeros), -1 refused (all zeros), nOpen[B]: clusters enumerated, maxCluster[B])."""
+        nL = np.ascontiguousarray(nL, dtype=np.int32)
+        nM = np.ascontiguousarray(nM, dtype=np.int32)
+        B = len(nL)
+        sizes = [(int(nL[b]) + int(nM[b])) * int(nM[b]) for b in range(B)]
+        psizes = [int(nM[b]) * (int(nL[b]) + 1) for b in range(B)]
+        costOff = np.zeros(B, np.int64)
+        probOff = np.zeros(B, np.int64)
+        costOff[1:] = np.cumsum(sizes)[:-1]
+        probOff[1:] = np.cumsum(psizes)[:-1]
+        flat = (np.concatenate([np.ascontiguousarray(c, dtype=np.float64).reshape(-1) for c in costs]) if B
+                else np.zeros(0, np.float64))
+        if flat.size != sum(sizes):
+            raise KBestError("hybrid_probs: a cost block is not (nL + nM) x nM")
+        probs = np.zeros(int(sum(psizes)), np.float64)
+        method = np.zeros(B, np.int32)
+        nOpen = np.zeros(B, np.int32)
+        maxCluster = np.zeros(B, np.int32)
+        self._check(self.lib.kbest_hybrid_probs_batch_f64(self.ctx, B, _ptr(nL), _ptr(nM), _ptr(flat), _ptr(costOff),
+                                                          int(bool(condition)), int(k), int(max_exact), _ptr(probs), _ptr(probOff),
+                                                          _ptr(method), _ptr(nOpen), _ptr(maxCluster)))
+        out = [probs[probOff[b]: probOff[b] + psizes[b]].reshape(int(nM[b]), int(nL[b]) + 1) for b in range(B)]
+        return out, method, nOpen, maxCluster
 
     def set_clustered_slot_cap(self, nbytes=0):
         """For tests (kbest_set_clustered_slot_cap): the layers of one cluster at the most, 0 = KBEST_CLUSTER_SLOT_CAP again; a frame
@@ -648,6 +685,24 @@ class KBestEngine:
                                                                  dp(d_logPerm), dp(d_info), dp(d_maxCluster), dp(d_label),
                                                                  int(labelStride), C.c_void_p(stream) if stream else None))
 
+    def clustered_partial_dev(self, B, maxRawRow, maxCol, d_nL, d_nM, d_cost, d_costOff, d_probs, d_probOff, d_nOpen, d_openDesc,
+                              descStride, d_openRows, rowStride, d_sub, max_exact=16, d_logPerm=None, d_info=None,
+                              d_maxCluster=None, d_label=None, labelStride=0, condition=False, stream=None, reserve=True):
+        """kbest_clustered_partial_batch_f64_dev on torch CUDA tensors, asynchronous on `stream`: clustered_probs_dev in the partial
+        mode -- clusters of more than max_exact measurements stay open (zeros) and come back as sub-problems: d_nOpen int32 [B],
+        d_openDesc int32 [B, descStride, 4] (root, m_k, nL_k, R_k), d_openRows int32 [B, rowStride], d_sub doubles shaped like
+        d_cost (include/kbest_c.h has the layout)."""
+        def dp(t):
+            return None if t is None else C.c_void_p(t.data_ptr())
+        if reserve:
+            self.reserve_clustered(B, maxRawRow, maxCol)
+        self._check(self.lib.kbest_clustered_partial_batch_f64_dev(self.ctx, B, maxRawRow, maxCol, dp(d_nL), dp(d_nM), dp(d_cost),
+                                                                   dp(d_costOff), int(bool(condition)), int(max_exact), dp(d_probs),
+                                                                   dp(d_probOff), dp(d_logPerm), dp(d_info), dp(d_maxCluster),
+                                                                   dp(d_label), int(labelStride), dp(d_nOpen), dp(d_openDesc),
+                                                                   int(descStride), dp(d_openRows), int(rowStride), dp(d_sub),
+                                                                   C.c_void_p(stream) if stream else None))
+
 
 class KBestMulti:
     """Multi-device engine of include/kbest_c.h: one context per GPU in ONE process, contiguous block sharding, RCCL
@@ -776,4 +831,15 @@ def clusterProb(costMatrix, nL, nM):
     out, _, info, maxCluster = _engine().clustered_probs([costMatrix], [nL], [nM])
     if info[0] < 0:
         raise RuntimeError(f"clusterProb: frame refused (info {int(info[0])}): its largest cluster has {int(maxCluster[0])} measurements")
+    return out[0]
+
+
+def hybridProb(costMatrix, nL, nM, k):
+    """Not in the reference: the hybrid association probabilities, for frames of up to 128 measurements: exact on every gated
+    cluster of at most 16 measurements, assignmentProb(k) on each larger cluster alone.  Returns probs[nM][nL+1]; raises
+    RuntimeError only when the frame is refused (a cluster with more rows >= nL than measurements); an infeasible frame comes back
+    as all zeros."""
+    out, method, _, _ = _engine().hybrid_probs([costMatrix], [nL], [nM], k)
+    if method[0] == -1:
+        raise RuntimeError("hybridProb: frame refused: a cluster holds more rows >= nL than measurements")
     return out[0]
