@@ -28,6 +28,7 @@
  *        the association probabilities by loopy belief propagation, for frames of any size (not in the reference)
  *   kbest_clustered_probs_batch_f64 / kbest_clustered_probs_batch_f64_dev
  *   kbest_hybrid_probs_batch_f64 / kbest_clustered_partial_batch_f64_dev
+ *   kbest_hybrid_exact_probs_batch_f64 / kbest_bigcluster_probs_f64_dev
  *        the exact association probabilities by gated clusters, for frames of up to 128 measurements (not in the reference)
  *
  * Conventions kept from the reference: cost matrices are column-major
@@ -517,6 +518,55 @@ int kbest_clustered_partial_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawRow, 
 int kbest_hybrid_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,
                                  const int64_t *costOff, int condition, int k, int maxExact, double *probs, const int64_t *probOff,
                                  int32_t *method, int32_t *nOpen, int32_t *maxCluster);
+/*
+ * Exact association probabilities of clusters of 17 .. 20 measurements (kbest_bigcluster.hip; not in the reference): a third tier
+ * of the exact subset sums -- ONE cluster over the whole chip, its layers in HBM -- fed by what the partial mode above hands out.
+ *
+ * The 16 of KBEST_CLUSTER_MAX_SIZE has a numeric reason (entries of a lie in (e^-42, 1]: a product of 17 may leave the normal
+ * doubles) and a structural one (one workgroup does a whole cluster).  This tier lifts both.  Per cluster it works on
+ * a'[r][c] = exp(colMin_c - x[r][c]), colMin_c the smallest finite entry of column c INSIDE the sub-block: a column factor is the
+ * only rescaling that commutes with the recurrence, it leaves the marginals alone, and log Z_k = log Z'_k - sum_c colMin_c in the
+ * units a = exp(-x).  What remains: every a' lies in (0, 1] and every column holds a 1, so Z'_k underflows only when EVERY complete
+ * assignment of the cluster costs about 700 more than the sum of its column minima; such a cluster reports Z = 0 (info 0).
+ *
+ * kbest_bigcluster_probs_f64_dev: n clusters.  m[k] (1 .. KBEST_BIGCLUSTER_MAX_SIZE), nLk[k], subOff[k], probOff[k] are HOST arrays
+ * (the launches are planned from them); the data is on the device: cluster k is the (nLk + m) x m column-major block at
+ * d_sub + subOff[k] in the format of d_sub above (+inf: zero; rows that are all +inf are left out), d_probs + probOff[k] takes its
+ * [m][nLk + 1] probabilities (sub-block row i < nLk -> slot i, rows >= nLk -> slot nLk), d_logZ[k] (may be NULL) its log Z_k in
+ * the units a = exp(-x) -- add m * (the frame's block minimum) for the frame's units a = exp(min - x) --, d_info[k] (may be NULL):
+ * 1 answered;  0: Z_k = 0 (zeros, log Z_k = -inf);  -3: its layers, (nLk + m + 3) * 2^m * 8 bytes (R_k counted as the sub-block's
+ * rows), exceed the work cap: its outputs are untouched.
+ * One launch per row forward and backward: launches of one stream order the layers, no kernel waits for another workgroup.  The
+ * workgroups of every launch follow from m alone and no floating-point atomics are used: a cluster gives the same bits alone, in
+ * any batch and under any cap.  Clusters share launches as far as the work space holds their layers (at most KBEST_BIGCLUSTER_WORK_CAP
+ * bytes in flight), else they run one after another.  Asynchronous on `stream` (NULL: the context's), allocates nothing: needs
+ * kbest_reserve_bigcluster(ctx, maxM, maxRows) first -- layers of min(cap, (maxRows + 3) * 2^maxM * 8) bytes, maxRows the largest
+ * nLk + m -- else KBEST_ERR_NOT_RESERVED.  m outside 1 .. 20: KBEST_ERR_BAD_ARG.
+ *
+ * kbest_hybrid_exact_probs_batch_f64 (host buffers, synchronous): kbest_hybrid_probs_batch_f64 with this tier between the two.  The
+ * partial kernel runs as there; every open cluster of at most maxBig (0 .. 20) measurements whose layers fit the work cap is
+ * answered by the tier from the sub-block that already lies on the device; the remaining open clusters go through the k-best path
+ * unchanged when k >= 1; with k = 0 a frame that has one is refused (method -1, zeros, logPerm NaN).
+ *   method[b]:  0: every cluster exact (either tier);  1 / 2 / -2 / -1: as kbest_hybrid_probs_batch_f64; a big cluster with Z = 0: -2;
+ *   nOpen[b] (may be NULL): the clusters the partial kernel left open;  nBig[b] (may be NULL): those of them this tier answered;
+ *   logPerm[b] (may be NULL): the sum of log Z_k over all exactly answered clusters in the frame's units (method 0: the definition
+ *       of kbest_clustered_probs_batch_f64);  -inf for method -2, NaN for method -1.
+ * With maxBig = 0 and k >= 1 every common output carries the bits of kbest_hybrid_probs_batch_f64.  maxBig outside 0 .. 20, maxExact
+ * outside 0 .. 16 or k < 0: KBEST_ERR_BAD_ARG.
+ */
+#define KBEST_BIGCLUSTER_MAX_SIZE 20
+#define KBEST_BIGCLUSTER_WORK_CAP ((size_t)1 << 30)  /* the layers of the clusters in flight */
+int kbest_reserve_bigcluster(kbest_ctx *ctx, int maxM, int maxRows);
+/* For tests: the layers in flight at the most (0: the default again).  The results do not depend on it, bit for bit -- except that
+ * a cluster whose own layers exceed it is not answered (-3). */
+int kbest_set_bigcluster_work_cap(kbest_ctx *ctx, size_t bytes);
+int kbest_bigcluster_probs_f64_dev(kbest_ctx *ctx, int n, const int32_t *m, const int32_t *nLk, const int64_t *subOff,
+                                   const int64_t *probOff, const double *d_sub, double *d_probs, double *d_logZ, int32_t *d_info,
+                                   void *stream);
+int kbest_hybrid_exact_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,
+                                       const int64_t *costOff, int condition, int k, int maxExact, int maxBig, double *probs,
+                                       const int64_t *probOff, double *logPerm, int32_t *method, int32_t *nOpen, int32_t *nBig,
+                                       int32_t *maxCluster);
 /* on = 1: the HOST-buffer association entries of this context (kbest_weights / assoc_probs / bruteforce / quadric_assoc) enumerate
  * their k best in the REFERENCE's own order of operations (the reference-order kernel, as KBEST_FLAG_REFERENCE_ORDER does for
  * kbest_batch_f64): where exactly equal gains straddle slot k the assignments that are weighed are the ones the reference's

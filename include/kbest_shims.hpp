@@ -137,6 +137,12 @@ std::vector<std::vector<double>> clusterProb(const std::vector<double> &costMatr
 // rows); an infeasible frame comes back as all zeros.
 std::vector<std::vector<double>> hybridProb(const std::vector<double> &costMatrix, size_t nL, size_t nM, size_t k);
 
+// Not in the reference: hybridProb with the exact tier for clusters of 17 .. 20 measurements in between
+// (kbest_hybrid_exact_probs_batch_f64): exact on every cluster of at most 20 measurements, assignmentProb(k) on the larger ones alone;
+// k = 0: a frame with a larger cluster is refused.  Throws std::runtime_error only when the frame is refused (method -1); an
+// infeasible frame comes back as all zeros.
+std::vector<std::vector<double>> hybridExactProb(const std::vector<double> &costMatrix, size_t nL, size_t nM, size_t k);
+
 // Not in the reference: the engine context behind the functions above (created on first use, GPU 0), for the entries of
 // kbest_c.h that take one -- e.g. kbest_last_tie_flags after a call.
 struct kbest_ctx;

@@ -8,5 +8,5 @@ surface (``kBest2D``, ``kBest2DCutoff``, ``assignmentProb``, ``permanentProb``; 
 pointer entry for buffers that already live in HBM (torch is only the
 allocator / stream / process-group plumbing).
 """
-from .engine import (KBestEngine, KBestError, KBestMulti, assignmentProb, beliefProb, clusterProb, hybridProb, kBest2D, kBest2DCutoff, lib_path, load_library,
+from .engine import (KBestEngine, KBestError, KBestMulti, assignmentProb, beliefProb, clusterProb, hybridExactProb, hybridProb, kBest2D, kBest2DCutoff, lib_path, load_library,
                      permanentProb)  # noqa: F401

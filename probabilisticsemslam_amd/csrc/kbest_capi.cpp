@@ -11,6 +11,7 @@
 #include <cstring>
 #include <condition_variable>
 #include <functional>
+#include <limits>
 #include <mutex>
 #include <string>
 #include <system_error>
@@ -148,6 +149,9 @@ struct kbest_ctx {
     size_t clusSlotCap = KBEST_CLUSTER_SLOT_CAP;  // ... the layers of one cluster at the most (kbest_set_clustered_slot_cap)
     size_t clusWorkCap = KBEST_CLUSTER_WORK_CAP;  // ... the whole work space at the most (kbest_set_clustered_work_cap)
     int clusLastGrid = 0;     // workgroups (frames in flight) of the last clustered launch (kbest_last_clustered_grid)
+    DevBufRaw bigLayers;      // the big-cluster tier (kbest_bigcluster.hip): the layers of the clusters in flight
+    DevBufRaw bigSmall;       // ... and their small arrays: a', row lists, per-workgroup partial sums
+    size_t bigWorkCap = KBEST_BIGCLUSTER_WORK_CAP;  // ... the layers in flight at the most (kbest_set_bigcluster_work_cap)
     DevBufRaw relayBuf;       // relay launches of the 64-row kernel: [B] LDS images (kbest_engine.hip)
     DevBufRaw relayFlags;     // ... and three words per matrix: claimed / done / gone (zeroed when the buffer is made, put back to zero by every launch)
     long long relayLaunches = 0;  // relay launches made (kbest_relay_launches)
@@ -498,6 +502,8 @@ int kbest_destroy(kbest_ctx *ctx)
     if (ctx->permBuf.p) (void)hipFree(ctx->permBuf.p);
     if (ctx->lbpBuf.p) (void)hipFree(ctx->lbpBuf.p);
     if (ctx->clusBuf.p) (void)hipFree(ctx->clusBuf.p);
+    if (ctx->bigLayers.p) (void)hipFree(ctx->bigLayers.p);
+    if (ctx->bigSmall.p) (void)hipFree(ctx->bigSmall.p);
     if (ctx->relayFlags.p) (void)hipFree(ctx->relayFlags.p);
     if (ctx->lastEvent) (void)hipEventDestroy(ctx->lastEvent);
     for (auto &a : ctx->aux)
@@ -3529,22 +3535,121 @@ int kbest_weights_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int3
     return weights_entry(ctx, B, nL, nM, cost, costOff, k, probs, probOff, nf, false, nullptr, false);
 }
 
-// hybridProb: the partial clustered kernel on the whole batch, then the open clusters of all frames as ONE batch through the
-// assignmentProb path (weights_entry, condition = false: kBest2DCutoff(k, 42) -> weights), scattered back on the host.
-int kbest_hybrid_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,
-                                 const int64_t *costOff, int condition, int k, int maxExact, double *probs, const int64_t *probOff,
-                                 int32_t *method, int32_t *nOpen, int32_t *maxCluster)
+// ---- the big-cluster tier (kbest_bigcluster.hip): one open cluster over the whole chip, its layers in HBM -----------------------
+static size_t big_layers_bytes(int m, int rows) { return ((size_t)(rows + 3) << m) * 8; }
+
+// layers of layerBytes, and the small arrays of whatever those layers can hold: KB_BIGCLUSTER_PACK clusters of the largest shape
+// without their partial sums, and partial sums of rows * workgroups(m) * m doubles each -- at most layers * m / 1 024 from 11
+// columns on, rows * m below
+static int big_reserve(kbest_ctx *ctx, size_t layerBytes, int maxM, int maxRows)
+{
+    const kb::BigClusterSmall s = kb::bigcluster_small(maxM, maxRows);
+    const size_t fixed = (size_t)(s.total - (long long)maxRows * kb::bigcluster_workgroups(maxM) * maxM + (long long)maxRows * maxM);
+    const size_t smallBytes = (size_t)kb::KB_BIGCLUSTER_PACK * fixed * 8 + layerBytes / 1024 * KBEST_BIGCLUSTER_MAX_SIZE + 4096;
+    int rc = raw_reserve(ctx, ctx->bigLayers, layerBytes);
+    if (rc != KBEST_OK) return rc;
+    return raw_reserve(ctx, ctx->bigSmall, smallBytes);
+}
+
+int kbest_set_bigcluster_work_cap(kbest_ctx *ctx, size_t bytes)
 {
     if (!ctx) return KBEST_ERR_BAD_ARG;
-    if (B < 0 || k < 1 || maxExact < 0 || maxExact > KBEST_CLUSTER_MAX_SIZE ||
-        (B > 0 && (!nL || !nM || !cost || !costOff || !probs || !probOff || !method)))
-        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_hybrid_probs_batch_f64: bad argument (k >= 1, maxExact 0 .. 16)");
-    if (B == 0) return KBEST_OK;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    ctx->bigWorkCap = bytes ? bytes : KBEST_BIGCLUSTER_WORK_CAP;
+    return KBEST_OK;
+}
+
+int kbest_reserve_bigcluster(kbest_ctx *ctx, int maxM, int maxRows)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    if (maxM < 1 || maxM > KBEST_BIGCLUSTER_MAX_SIZE || maxRows < maxM || maxRows > KBEST_MAX_DIM_WIDE)
+        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_reserve_bigcluster: bad argument (maxM 1 .. 20, maxM <= maxRows <= 1024)");
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t need = big_layers_bytes(maxM, maxRows);
+    return big_reserve(ctx, need < ctx->bigWorkCap ? need : ctx->bigWorkCap, maxM, maxRows);
+}
+
+int kbest_bigcluster_probs_f64_dev(kbest_ctx *ctx, int n, const int32_t *m, const int32_t *nLk, const int64_t *subOff,
+                                   const int64_t *probOff, const double *d_sub, double *d_probs, double *d_logZ, int32_t *d_info,
+                                   void *stream)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    if (n < 0 || (n > 0 && (!m || !nLk || !subOff || !probOff || !d_sub || !d_probs)))
+        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_bigcluster_probs_f64_dev: bad argument");
+    if (n == 0) return KBEST_OK;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    const size_t cap = ctx->bigWorkCap < ctx->bigLayers.bytes ? ctx->bigWorkCap : ctx->bigLayers.bytes;
+    for (int k = 0; k < n; k++) {  // everything is checked before anything is launched
+        if (m[k] < 1 || m[k] > KBEST_BIGCLUSTER_MAX_SIZE || nLk[k] < 0 || (long long)nLk[k] + m[k] > KBEST_MAX_DIM_WIDE || subOff[k] < 0 ||
+            probOff[k] < 0)
+            return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_bigcluster_probs_f64_dev: a cluster with m outside 1 .. 20, nLk < 0, nLk + m > 1024 or a negative offset");
+        const int rows = nLk[k] + m[k];
+        if (big_layers_bytes(m[k], rows) > ctx->bigWorkCap) continue;  // (-3)
+        if (big_layers_bytes(m[k], rows) > ctx->bigLayers.bytes || (size_t)kb::bigcluster_small(m[k], rows).total * 8 > ctx->bigSmall.bytes)
+            return fail(ctx, KBEST_ERR_NOT_RESERVED, "kbest_bigcluster_probs_f64_dev: call kbest_reserve_bigcluster first");
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    int rc = order_behind_last(ctx, s);  // (one work space per context)
+    if (rc != KBEST_OK) return rc;
+    const Launched mark{ctx, s};
+    kb::BigClusterPack pk;
+    pk.n = 0;
+    size_t layAt = 0, smAt = 0;  // doubles
+    auto flush = [&]() -> hipError_t {
+        if (pk.n == 0) return hipSuccess;
+        const hipError_t e = kb::launch_bigcluster_pack(pk, d_sub, d_probs, d_logZ, d_info, static_cast<double *>(ctx->bigLayers.p),
+                                                        static_cast<double *>(ctx->bigSmall.p), s);
+        pk.n = 0;
+        layAt = smAt = 0;
+        return e;
+    };
+    for (int k = 0; k < n; k++) {
+        const int rows = nLk[k] + m[k];
+        const size_t need = big_layers_bytes(m[k], rows), sm = (size_t)kb::bigcluster_small(m[k], rows).total;
+        if (need > ctx->bigWorkCap) {
+            if (d_info) {
+                const hipError_t e = kb::launch_bigcluster_flag(d_info, k, -3, s);
+                if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "big-cluster kernel launch", e);
+            }
+            continue;
+        }
+        if (pk.n == kb::KB_BIGCLUSTER_PACK || layAt * 8 + need > cap || (smAt + sm) * 8 > ctx->bigSmall.bytes) {
+            const hipError_t e = flush();
+            if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "big-cluster kernel launch", e);
+        }
+        kb::BigClusterDesc &d = pk.c[pk.n++];
+        d.subOff = subOff[k];
+        d.probOff = probOff[k];
+        d.layerOff = (long long)layAt;
+        d.smallOff = (long long)smAt;
+        d.m = m[k];
+        d.nL = nLk[k];
+        d.rows = rows;
+        d.idx = k;
+        layAt += need / 8;
+        smAt += sm;
+    }
+    const hipError_t e = flush();
+    if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "big-cluster kernel launch", e);
+    return KBEST_OK;
+}
+
+// hybridProb: the partial clustered kernel on the whole batch, then the open clusters of all frames as ONE batch through the
+// assignmentProb path (weights_entry, condition = false: kBest2DCutoff(k, 42) -> weights), scattered back on the host.
+// maxBig > 0 (kbest_hybrid_exact_probs_batch_f64): the open clusters of at most maxBig columns whose layers fit the work cap go
+// through the big-cluster tier first, from the sub-blocks that already lie on the device; k = 0: whatever else is open refuses
+// its frame.  maxBig = 0, k >= 1: kbest_hybrid_probs_batch_f64, step for step.
+static int hybrid_impl(kbest_ctx *ctx, const char *who, int B, const int32_t *nL, const int32_t *nM, const double *cost,
+                       const int64_t *costOff, int condition, int k, int maxExact, int maxBig, double *probs, const int64_t *probOff,
+                       double *logPerm, int32_t *method, int32_t *nOpen, int32_t *nBig, int32_t *maxCluster)
+{
     int maxRawRow = 1, maxCol = 1;
     size_t costN = 0, probN = 0;
     for (int b = 0; b < B; b++) {
         if (nL[b] < 0 || nM[b] < 1 || costOff[b] < 0 || probOff[b] < 0)
-            return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_hybrid_probs_batch_f64: a frame with nL < 0, nM < 1 or a negative offset");
+            return fail(ctx, KBEST_ERR_BAD_ARG, (std::string(who) + ": a frame with nL < 0, nM < 1 or a negative offset").c_str());
         const long long nr = (long long)nL[b] + nM[b];
         if (nr > maxRawRow) maxRawRow = nr > (1 << 30) ? (1 << 30) : (int)nr;
         if (nM[b] > maxCol) maxCol = nM[b];
@@ -3552,21 +3657,24 @@ int kbest_hybrid_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const
         if (ce > costN) costN = ce;
         if (pe > probN) probN = pe;
     }
-    int rc = cluster_check_shape(ctx, B, maxRawRow, maxCol, "kbest_hybrid_probs_batch_f64");
+    int rc = cluster_check_shape(ctx, B, maxRawRow, maxCol, who);
     if (rc != KBEST_OK) return rc;
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     rc = kbest_reserve_clustered(ctx, B, maxRawRow, maxCol);
     if (rc != KBEST_OK) return rc;
-    std::vector<double> hp(probN);
+    std::vector<double> hp(probN), hLp;
     std::vector<int32_t> hInt((size_t)B * 3), hDesc, hRows, hLabel;  // info | maxCluster | nOpen
-    struct Open { int b, root, m, cL; size_t rowAt; };
+    struct Open { int b, root, m, cL; size_t rowAt; int big, at; };  // at: its place among the big / the enumerated clusters
     std::vector<Open> open;
-    std::vector<double> sub;      // the open clusters' sub-blocks, packed
+    std::vector<double> sub;      // the enumerated clusters' sub-blocks, packed
     std::vector<int64_t> sCo, sPo;
+    std::vector<double> bigP, bigLogZ;  // the big clusters' [m][nL_k + 1] probabilities, packed, and their log Z_k
+    std::vector<int32_t> bigInfo;
+    std::vector<int64_t> bPo;
     const size_t descStride = (size_t)maxCol, rowStride = (size_t)maxRawRow;
     {
-        DevBuf dCost, dMeta, dProbs, dOut, dLabel, dDesc, dRows, dSub;
+        DevBuf dCost, dMeta, dProbs, dOut, dLabel, dDesc, dRows, dSub, dLp;
         // meta: costOff[B] | probOff[B] (int64) | nL[B] | nM[B] (int32);  out: info[B] | maxCluster[B] | nOpen[B] (int32)
         std::vector<unsigned char> meta((size_t)B * 24);
         memcpy(meta.data(), costOff, (size_t)B * 8);
@@ -3577,8 +3685,9 @@ int kbest_hybrid_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const
         if ((e = dCost.alloc(ctx, costN * 8)) != hipSuccess || (e = dMeta.alloc(ctx, meta.size())) != hipSuccess ||
             (e = dProbs.alloc(ctx, probN * 8)) != hipSuccess || (e = dOut.alloc(ctx, (size_t)B * 12)) != hipSuccess ||
             (e = dLabel.alloc(ctx, (size_t)B * maxCol * 4)) != hipSuccess || (e = dDesc.alloc(ctx, (size_t)B * descStride * 16)) != hipSuccess ||
-            (e = dRows.alloc(ctx, (size_t)B * rowStride * 4)) != hipSuccess || (e = dSub.alloc(ctx, costN * 8)) != hipSuccess)
-            return fail(ctx, KBEST_ERR_NOMEM, "kbest_hybrid_probs_batch_f64: device buffers", e);
+            (e = dRows.alloc(ctx, (size_t)B * rowStride * 4)) != hipSuccess || (e = dSub.alloc(ctx, costN * 8)) != hipSuccess ||
+            (logPerm && (e = dLp.alloc(ctx, (size_t)B * 8)) != hipSuccess))
+            return fail(ctx, KBEST_ERR_NOMEM, (std::string(who) + ": device buffers").c_str(), e);
         HIP_TRY(ctx, hipMemcpy(dCost.p, cost, costN * 8, hipMemcpyHostToDevice));
         HIP_TRY(ctx, hipMemcpy(dMeta.p, meta.data(), meta.size(), hipMemcpyHostToDevice));
         HIP_TRY(ctx, hipMemsetAsync(dProbs.p, 0, probN * 8, ctx->stream));
@@ -3587,13 +3696,18 @@ int kbest_hybrid_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const
         rc = kbest_clustered_partial_batch_f64_dev(ctx, B, maxRawRow, maxCol, reinterpret_cast<const int32_t *>(m8 + (size_t)B * 16),
                                                    reinterpret_cast<const int32_t *>(m8 + (size_t)B * 20), dCost.as<double>(),
                                                    reinterpret_cast<const int64_t *>(m8), condition, maxExact, dProbs.as<double>(),
-                                                   reinterpret_cast<const int64_t *>(m8 + (size_t)B * 8), nullptr, o4, o4 + B,
+                                                   reinterpret_cast<const int64_t *>(m8 + (size_t)B * 8),
+                                                   logPerm ? dLp.as<double>() : nullptr, o4, o4 + B,
                                                    dLabel.as<int32_t>(), maxCol, o4 + 2 * (size_t)B, dDesc.as<int32_t>(),
                                                    (int)descStride, dRows.as<int32_t>(), (int)rowStride, dSub.as<double>(), nullptr);
         if (rc != KBEST_OK) return rc;
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         HIP_TRY(ctx, hipMemcpy(hp.data(), dProbs.p, probN * 8, hipMemcpyDeviceToHost));
         HIP_TRY(ctx, hipMemcpy(hInt.data(), dOut.p, (size_t)B * 12, hipMemcpyDeviceToHost));
+        if (logPerm) {
+            hLp.resize(B);
+            HIP_TRY(ctx, hipMemcpy(hLp.data(), dLp.p, (size_t)B * 8, hipMemcpyDeviceToHost));
+        }
         const int32_t *hOpen = hInt.data() + 2 * (size_t)B;
         bool any = false;
         for (int b = 0; b < B; b++) any = any || hOpen[b] > 0;
@@ -3604,52 +3718,124 @@ int kbest_hybrid_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const
             HIP_TRY(ctx, hipMemcpy(hDesc.data(), dDesc.p, hDesc.size() * 4, hipMemcpyDeviceToHost));
             HIP_TRY(ctx, hipMemcpy(hRows.data(), dRows.p, hRows.size() * 4, hipMemcpyDeviceToHost));
             HIP_TRY(ctx, hipMemcpy(hLabel.data(), dLabel.p, hLabel.size() * 4, hipMemcpyDeviceToHost));
+            auto is_big = [&](const int32_t *d) {
+                return maxBig > 0 && d[1] <= maxBig && big_layers_bytes(d[1], d[2] + d[1]) <= ctx->bigWorkCap;
+            };
             size_t total = 0;
             for (int b = 0; b < B; b++)
                 for (int j = 0; j < hOpen[b]; j++) {
                     const int32_t *d = hDesc.data() + ((size_t)b * descStride + j) * 4;
-                    total += (size_t)(d[2] + d[1]) * d[1];
+                    if (!is_big(d)) total += (size_t)(d[2] + d[1]) * d[1];
                 }
             sub.resize(total);
-            size_t at = 0, pat = 0;
+            std::vector<int32_t> bM, bL;
+            std::vector<int64_t> bSo;
+            size_t at = 0, pat = 0, bpat = 0, bigLayers = 0;
+            int bigM = 1, bigRows = 1;
             for (int b = 0; b < B; b++) {
                 if (hOpen[b] <= 0) continue;
-                size_t n = 0, rowAt = (size_t)b * rowStride;
+                size_t n = 0, nKeep = 0, rowAt = (size_t)b * rowStride;
+                bool bigHere = false;
                 for (int j = 0; j < hOpen[b]; j++) {
                     const int32_t *d = hDesc.data() + ((size_t)b * descStride + j) * 4;
-                    open.push_back(Open{b, d[0], d[1], d[2], rowAt});
-                    sCo.push_back((int64_t)(at + n));
-                    sPo.push_back((int64_t)pat);
-                    n += (size_t)(d[2] + d[1]) * d[1];
-                    pat += (size_t)d[1] * ((size_t)d[2] + 1);
+                    const size_t sz = (size_t)(d[2] + d[1]) * d[1];
+                    if (is_big(d)) {
+                        open.push_back(Open{b, d[0], d[1], d[2], rowAt, 1, (int)bM.size()});
+                        bM.push_back(d[1]);
+                        bL.push_back(d[2]);
+                        bSo.push_back(costOff[b] + (int64_t)n);
+                        bPo.push_back((int64_t)bpat);
+                        bpat += (size_t)d[1] * ((size_t)d[2] + 1);
+                        bigLayers += big_layers_bytes(d[1], d[2] + d[1]);
+                        if (d[1] > bigM) bigM = d[1];
+                        if (d[2] + d[1] > bigRows) bigRows = d[2] + d[1];
+                        bigHere = true;
+                    } else {
+                        open.push_back(Open{b, d[0], d[1], d[2], rowAt, 0, (int)sCo.size()});
+                        sCo.push_back((int64_t)(at + nKeep));
+                        sPo.push_back((int64_t)pat);
+                        pat += (size_t)d[1] * ((size_t)d[2] + 1);
+                        nKeep += sz;
+                    }
+                    n += sz;
                     rowAt += (size_t)d[2];
                 }
-                HIP_TRY(ctx, hipMemcpy(sub.data() + at, dSub.as<double>() + costOff[b], n * 8, hipMemcpyDeviceToHost));
-                at += n;
+                if (k >= 1 && nKeep > 0) {
+                    if (!bigHere) {
+                        HIP_TRY(ctx, hipMemcpy(sub.data() + at, dSub.as<double>() + costOff[b], n * 8, hipMemcpyDeviceToHost));
+                    } else {  // the enumerated clusters of a frame that has big ones too: one by one
+                        size_t from = 0, to = at;
+                        for (int j = 0; j < hOpen[b]; j++) {
+                            const int32_t *d = hDesc.data() + ((size_t)b * descStride + j) * 4;
+                            const size_t sz = (size_t)(d[2] + d[1]) * d[1];
+                            if (!is_big(d)) {
+                                HIP_TRY(ctx, hipMemcpy(sub.data() + to, dSub.as<double>() + costOff[b] + from, sz * 8, hipMemcpyDeviceToHost));
+                                to += sz;
+                            }
+                            from += sz;
+                        }
+                    }
+                }
+                at += nKeep;
+            }
+            if (!bM.empty()) {  // the big clusters of all frames: from the sub-blocks where they lie
+                const int nb = (int)bM.size();
+                rc = big_reserve(ctx, bigLayers < ctx->bigWorkCap ? bigLayers : ctx->bigWorkCap, bigM, bigRows);
+                if (rc != KBEST_OK) return rc;
+                DevBuf dBigP, dBigOut;  // out: logZ[nb] (double) | info[nb] (int32)
+                if ((e = dBigP.alloc(ctx, bpat * 8)) != hipSuccess || (e = dBigOut.alloc(ctx, (size_t)nb * 12)) != hipSuccess)
+                    return fail(ctx, KBEST_ERR_NOMEM, (std::string(who) + ": device buffers").c_str(), e);
+                unsigned char *b8 = dBigOut.as<unsigned char>();
+                rc = kbest_bigcluster_probs_f64_dev(ctx, nb, bM.data(), bL.data(), bSo.data(), bPo.data(), dSub.as<double>(),
+                                                    dBigP.as<double>(), reinterpret_cast<double *>(b8),
+                                                    reinterpret_cast<int32_t *>(b8 + (size_t)nb * 8), nullptr);
+                if (rc != KBEST_OK) return rc;
+                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+                bigP.resize(bpat);
+                bigLogZ.resize(nb);
+                bigInfo.resize(nb);
+                HIP_TRY(ctx, hipMemcpy(bigP.data(), dBigP.p, bpat * 8, hipMemcpyDeviceToHost));
+                HIP_TRY(ctx, hipMemcpy(bigLogZ.data(), b8, (size_t)nb * 8, hipMemcpyDeviceToHost));
+                HIP_TRY(ctx, hipMemcpy(bigInfo.data(), b8 + (size_t)nb * 8, (size_t)nb * 4, hipMemcpyDeviceToHost));
             }
         }
     }
     const int32_t *hInfo = hInt.data(), *hOpen = hInt.data() + 2 * (size_t)B;
     for (int b = 0; b < B; b++) method[b] = hInfo[b] < 0 ? -1 : hInfo[b] == 0 ? -2 : 0;
+    if (nBig)
+        for (int b = 0; b < B; b++) nBig[b] = 0;
     if (!open.empty()) {
-        const int S = (int)open.size();
+        const int S = (int)sCo.size();
         std::vector<int32_t> sL(S), sM(S), sNf(S, 0);
         size_t pn = 0;
-        for (int i = 0; i < S; i++) {
-            sL[i] = open[i].cL;
-            sM[i] = open[i].m;
-            pn += (size_t)open[i].m * ((size_t)open[i].cL + 1);
-        }
+        for (const Open &o : open)
+            if (!o.big) {
+                sL[o.at] = o.cL;
+                sM[o.at] = o.m;
+                pn += (size_t)o.m * ((size_t)o.cL + 1);
+            }
         std::vector<double> sp(pn, 0.0);
-        rc = weights_entry(ctx, S, sL.data(), sM.data(), sub.data(), sCo.data(), k, sp.data(), sPo.data(), sNf.data(), false, nullptr, false);
-        if (rc != KBEST_OK) return rc;
-        for (int i = 0; i < S; i++) {  // slot nL_k -> slot nL, landmark rows through the row list, columns through the labels
-            const Open &o = open[i];
+        if (S > 0 && k >= 1) {
+            rc = weights_entry(ctx, S, sL.data(), sM.data(), sub.data(), sCo.data(), k, sp.data(), sPo.data(), sNf.data(), false, nullptr, false);
+            if (rc != KBEST_OK) return rc;
+        }
+        std::vector<char> refused(B, 0);
+        for (const Open &o : open) {  // slot nL_k -> slot nL, landmark rows through the row list, columns through the labels
             const int b = o.b;
-            if (sNf[i] <= 0) method[b] = -2;
-            else if (method[b] >= 0) method[b] = (sNf[i] >= k || method[b] == 2) ? 2 : 1;
+            const double *q;
+            if (o.big) {
+                if (bigInfo[o.at] <= 0) method[b] = -2;
+                else if (nBig) nBig[b]++;
+                q = bigP.data() + bPo[o.at];
+            } else if (k < 1) {  // (kbest_hybrid_exact_probs_batch_f64 with k = 0: nothing enumerates it)
+                refused[b] = 1;
+                continue;
+            } else {
+                if (sNf[o.at] <= 0) method[b] = -2;
+                else if (method[b] >= 0) method[b] = (sNf[o.at] >= k || method[b] == 2) ? 2 : 1;
+                q = sp.data() + sPo[o.at];
+            }
             double *fp = hp.data() + probOff[b];
-            const double *q = sp.data() + sPo[i];
             const int32_t *lab = hLabel.data() + (size_t)b * maxCol, *rows = hRows.data() + o.rowAt;
             int j = 0;
             for (int c = 0; c < nM[b] && j < o.m; c++) {
@@ -3660,9 +3846,33 @@ int kbest_hybrid_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const
                 j++;
             }
         }
-        for (int b = 0; b < B; b++)
-            if (method[b] == -2 && hOpen[b] > 0)  // an open cluster without a feasible assignment: the whole frame is zeros
-                std::fill(hp.begin() + probOff[b], hp.begin() + probOff[b] + (size_t)nM[b] * ((size_t)nL[b] + 1), 0.0);
+        for (int b = 0; b < B; b++) {
+            if (refused[b]) method[b] = -1;
+            if ((method[b] == -2 || method[b] == -1) && hOpen[b] > 0) {  // an open cluster without a feasible assignment (or without
+                std::fill(hp.begin() + probOff[b], hp.begin() + probOff[b] + (size_t)nM[b] * ((size_t)nL[b] + 1), 0.0);  // an answer):
+                if (nBig) nBig[b] = 0;                                                                              // the whole frame is zeros
+            }
+        }
+    }
+    if (logPerm) {
+        // the partial kernel's sum over the clusters it answered, then the big clusters in label order; their log Z_k are in the
+        // units a = exp(-x): m_k times the frame's block minimum (0 after conditionCosts) brings them to the frame's a = exp(min - x)
+        for (int b = 0; b < B; b++) logPerm[b] = hLp[b];
+        for (const Open &o : open) {
+            if (!o.big || method[o.b] < 0) continue;
+            double mn = 0.0;
+            if (!condition) {
+                const double *x = cost + costOff[o.b];
+                const size_t cnt = ((size_t)nL[o.b] + nM[o.b]) * (size_t)nM[o.b];
+                mn = x[0];
+                for (size_t i = 1; i < cnt; i++) mn = x[i] < mn ? x[i] : mn;
+            }
+            logPerm[o.b] = logPerm[o.b] + (bigLogZ[o.at] + (double)o.m * mn);
+        }
+        for (int b = 0; b < B; b++) {
+            if (method[b] == -2) logPerm[b] = -std::numeric_limits<double>::infinity();
+            if (method[b] == -1) logPerm[b] = std::numeric_limits<double>::quiet_NaN();
+        }
     }
     // every frame's own slice only: what lies between the slices in the caller's buffer is the caller's
     for (int b = 0; b < B; b++)
@@ -3670,6 +3880,33 @@ int kbest_hybrid_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const
     if (nOpen) memcpy(nOpen, hOpen, (size_t)B * 4);
     if (maxCluster) memcpy(maxCluster, hInt.data() + B, (size_t)B * 4);
     return KBEST_OK;
+}
+
+int kbest_hybrid_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,
+                                 const int64_t *costOff, int condition, int k, int maxExact, double *probs, const int64_t *probOff,
+                                 int32_t *method, int32_t *nOpen, int32_t *maxCluster)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    if (B < 0 || k < 1 || maxExact < 0 || maxExact > KBEST_CLUSTER_MAX_SIZE ||
+        (B > 0 && (!nL || !nM || !cost || !costOff || !probs || !probOff || !method)))
+        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_hybrid_probs_batch_f64: bad argument (k >= 1, maxExact 0 .. 16)");
+    if (B == 0) return KBEST_OK;
+    return hybrid_impl(ctx, "kbest_hybrid_probs_batch_f64", B, nL, nM, cost, costOff, condition, k, maxExact, 0, probs, probOff, nullptr,
+                       method, nOpen, nullptr, maxCluster);
+}
+
+int kbest_hybrid_exact_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,
+                                       const int64_t *costOff, int condition, int k, int maxExact, int maxBig, double *probs,
+                                       const int64_t *probOff, double *logPerm, int32_t *method, int32_t *nOpen, int32_t *nBig,
+                                       int32_t *maxCluster)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    if (B < 0 || k < 0 || maxExact < 0 || maxExact > KBEST_CLUSTER_MAX_SIZE || maxBig < 0 || maxBig > KBEST_BIGCLUSTER_MAX_SIZE ||
+        (B > 0 && (!nL || !nM || !cost || !costOff || !probs || !probOff || !method)))
+        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_hybrid_exact_probs_batch_f64: bad argument (k >= 0, maxExact 0 .. 16, maxBig 0 .. 20)");
+    if (B == 0) return KBEST_OK;
+    return hybrid_impl(ctx, "kbest_hybrid_exact_probs_batch_f64", B, nL, nM, cost, costOff, condition, k, maxExact, maxBig, probs, probOff,
+                       logPerm, method, nOpen, nBig, maxCluster);
 }
 
 int kbest_bruteforce_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,

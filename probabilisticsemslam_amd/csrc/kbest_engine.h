@@ -614,6 +614,38 @@ hipError_t launch_kbest_cluster(const ClusterParams &p, const ClusterPlan &pl, i
 hipError_t launch_kbest_cluster_partial(const ClusterParams &p, const ClusterOpenParams &q, const ClusterPlan &pl, int grid,
                                         hipStream_t stream);
 
+// kbest_bigcluster.hip: one open cluster of up to 20 measurements over the whole chip, its layers in HBM (kbest_c.h, "Exact
+// association probabilities of clusters of 17 .. 20 measurements").  The clusters of a pack share every launch (grid.y).
+constexpr int KB_BIGCLUSTER_PACK = 32;
+struct BigClusterDesc {
+    long long subOff, probOff;     // the cluster's sub-block / its [m][nL + 1] probabilities, in doubles from the caller's buffers
+    long long layerOff, smallOff;  // its layers (rows + 3) 2^m / its small arrays (bigcluster_small), in doubles from the work spaces
+    int m, nL, rows, idx;          // columns, landmark rows, rows of the sub-block (nL + m), its place in logZ / info
+};
+struct BigClusterPack {
+    BigClusterDesc c[KB_BIGCLUSTER_PACK];
+    int n;
+};
+// workgroups of the backward sweep, one partial sum each: from m alone (1 024 subsets a workgroup)
+__host__ __device__ inline int bigcluster_workgroups(int m) { return m <= 10 ? 1 : 1 << (m - 10); }
+struct BigClusterSmall { long long a, colMin, sumCol, miss, part, ints, total; };  // offsets in doubles
+__host__ __device__ inline BigClusterSmall bigcluster_small(int m, int rows)
+{
+    BigClusterSmall s;
+    long long o = 0;
+    s.a = o;      o += (long long)rows * m;                              // a'[R][m]
+    s.colMin = o; o += m;
+    s.sumCol = o; o += 1;
+    s.miss = o;   o += (long long)m * m;                                 // w of the rows >= nL: [row - nL][column]
+    s.part = o;   o += (long long)rows * bigcluster_workgroups(m) * m;   // [row][workgroup][column]
+    s.ints = o;   o += (2ll * rows + 1 + 1) / 2;                         // int R, rowIdx[rows], mask[rows]
+    s.total = o;
+    return s;
+}
+hipError_t launch_bigcluster_pack(const BigClusterPack &p, const double *sub, double *probs, double *logZ, int *info, double *layers,
+                                  double *small, hipStream_t stream);
+hipError_t launch_bigcluster_flag(int *info, int idx, int value, hipStream_t stream);
+
 }  // namespace kb
 
 // kbest_capi.cpp: completes the gain levels that straddle slot k in the caller's HOST tables (see there)

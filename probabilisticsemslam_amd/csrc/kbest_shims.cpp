@@ -301,4 +301,21 @@ std::vector<std::vector<double>> hybridProb(const std::vector<double> &costMatri
     return probs;
 }
 
+std::vector<std::vector<double>> hybridExactProb(const std::vector<double> &costMatrix, size_t nL, size_t nM, size_t k)
+{
+    kbest_ctx *ctx = global_ctx();
+    const int32_t l = (int32_t)nL, m = (int32_t)nM;
+    const int64_t zero = 0;
+    int32_t method = 0, maxCluster = 0;
+    std::vector<double> flat(nM * (nL + 1), 0.0);
+    check(ctx, kbest_hybrid_exact_probs_batch_f64(ctx, 1, &l, &m, costMatrix.data(), &zero, 0, (int)k, 0, KBEST_BIGCLUSTER_MAX_SIZE,
+                                                  flat.data(), &zero, nullptr, &method, nullptr, nullptr, &maxCluster));
+    if (method == -1)
+        throw std::runtime_error("hybridExactProb: frame refused: its largest cluster has " + std::to_string(maxCluster) + " measurements");
+    std::vector<std::vector<double>> probs(nM, std::vector<double>(nL + 1, 0.0));
+    for (size_t c = 0; c < nM; c++)
+        for (size_t j = 0; j <= nL; j++) probs[c][j] = flat[c * (nL + 1) + j];
+    return probs;
+}
+
 kbest_ctx *kbest_shims_context() { return global_ctx(); }

@@ -33,6 +33,7 @@ KBEST_PERM_MAX_COLS = 16     # measurements per frame of the exact (permanent) a
 KBEST_LBP_MAX_COLS = 128     # measurements per frame of the belief-propagation association probabilities
 KBEST_CLUSTER_MAX_COLS = 128  # measurements per frame of the clustered exact association probabilities
 KBEST_CLUSTER_MAX_SIZE = 16   # ... and per cluster
+KBEST_BIGCLUSTER_MAX_SIZE = 20  # ... and per cluster of the big-cluster tier (one cluster over the whole chip)
 
 # every symbol include/kbest_c.h declares
 C_ABI_SYMBOLS = (
@@ -53,6 +54,8 @@ C_ABI_SYMBOLS = (
     "kbest_clustered_probs_batch_f64", "kbest_clustered_probs_batch_f64_dev", "kbest_reserve_clustered",
     "kbest_set_clustered_slot_cap", "kbest_set_clustered_work_cap", "kbest_last_clustered_grid",
     "kbest_clustered_partial_batch_f64_dev", "kbest_hybrid_probs_batch_f64",
+    "kbest_reserve_bigcluster", "kbest_set_bigcluster_work_cap", "kbest_bigcluster_probs_f64_dev",
+    "kbest_hybrid_exact_probs_batch_f64",
 )
 KBEST_MULTI_STAMPS = 6
 KBEST_MULTI_BATCH, KBEST_MULTI_SUBTREE = 0, 1
@@ -174,6 +177,12 @@ def load_library():
                                                               C.c_int, dp, vp]
         lib.kbest_hybrid_probs_batch_f64.argtypes = [vp, C.c_int, i32p, i32p, dp, i64p, C.c_int, C.c_int, C.c_int, dp, i64p, i32p,
                                                      i32p, i32p]
+    if hasattr(lib, "kbest_hybrid_exact_probs_batch_f64"):
+        lib.kbest_reserve_bigcluster.argtypes = [vp, C.c_int, C.c_int]
+        lib.kbest_set_bigcluster_work_cap.argtypes = [vp, C.c_size_t]
+        lib.kbest_bigcluster_probs_f64_dev.argtypes = [vp, C.c_int, i32p, i32p, i64p, i64p, dp, dp, dp, i32p, vp]
+        lib.kbest_hybrid_exact_probs_batch_f64.argtypes = [vp, C.c_int, i32p, i32p, dp, i64p, C.c_int, C.c_int, C.c_int, C.c_int, dp,
+                                                           i64p, dp, i32p, i32p, i32p, i32p]
     lib.kbest_register_host_buffer.argtypes = [vp, vp, C.c_size_t]
     lib.kbest_unregister_host_buffer.argtypes = [vp, vp]
     _lib = lib
@@ -489,6 +498,65 @@ class KBestEngine:
                                                           _ptr(method), _ptr(nOpen), _ptr(maxCluster)))
         out = [probs[probOff[b]: probOff[b] + psizes[b]].reshape(int(nM[b]), int(nL[b]) + 1) for b in range(B)]
         return out, method, nOpen, maxCluster
+
+    def hybrid_exact_probs(self, costs, nL, nM, k=0, condition=False, max_exact=16, max_big=20):
+        """Batched hybridExactProb (kbest_hybrid_exact_probs_batch_f64): hybrid_probs() with the big-cluster tier between its two --
+        every cluster of more than max_exact and at most max_big (0 .. 20) measurements whose layers fit the work cap is answered
+        EXACTLY, one cluster over the whole chip; what is still open goes through assignmentProb(k) when k >= 1 and refuses its
+        frame when k = 0.  Returns (list of [nM, nL+1] arrays, method[B]: 0 every cluster exact, 1 / 2 some cluster enumerated
+        (complete / cut at k), -2 infeasible (all zeros), -1 refused (all zeros), nOpen[B]: clusters beyond max_exact, nBig[B]: those
+        of them answered exactly, maxCluster[B], logPerm[B]: the sum of log Z_k over the exactly answered clusters)."""
+        nL = np.ascontiguousarray(nL, dtype=np.int32)
+        nM = np.ascontiguousarray(nM, dtype=np.int32)
+        B = len(nL)
+        sizes = [(int(nL[b]) + int(nM[b])) * int(nM[b]) for b in range(B)]
+        psizes = [int(nM[b]) * (int(nL[b]) + 1) for b in range(B)]
+        costOff = np.zeros(B, np.int64)
+        probOff = np.zeros(B, np.int64)
+        costOff[1:] = np.cumsum(sizes)[:-1]
+        probOff[1:] = np.cumsum(psizes)[:-1]
+        flat = (np.concatenate([np.ascontiguousarray(c, dtype=np.float64).reshape(-1) for c in costs]) if B
+                else np.zeros(0, np.float64))
+        if flat.size != sum(sizes):
+            raise KBestError("hybrid_exact_probs: a cost block is not (nL + nM) x nM")
+        probs = np.zeros(int(sum(psizes)), np.float64)
+        method = np.zeros(B, np.int32)
+        nOpen = np.zeros(B, np.int32)
+        nBig = np.zeros(B, np.int32)
+        maxCluster = np.zeros(B, np.int32)
+        logPerm = np.zeros(B, np.float64)
+        self._check(self.lib.kbest_hybrid_exact_probs_batch_f64(self.ctx, B, _ptr(nL), _ptr(nM), _ptr(flat), _ptr(costOff),
+                                                                int(bool(condition)), int(k), int(max_exact), int(max_big),
+                                                                _ptr(probs), _ptr(probOff), _ptr(logPerm), _ptr(method), _ptr(nOpen),
+                                                                _ptr(nBig), _ptr(maxCluster)))
+        out = [probs[probOff[b]: probOff[b] + psizes[b]].reshape(int(nM[b]), int(nL[b]) + 1) for b in range(B)]
+        return out, method, nOpen, nBig, maxCluster, logPerm
+
+    def reserve_bigcluster(self, maxM, maxRows):
+        """kbest_reserve_bigcluster: the work space of bigcluster_probs_dev for clusters of up to maxM measurements and maxRows
+        (nL_k + m_k) rows."""
+        self._check(self.lib.kbest_reserve_bigcluster(self.ctx, int(maxM), int(maxRows)))
+
+    def set_bigcluster_work_cap(self, nbytes=0):
+        """For tests (kbest_set_bigcluster_work_cap): the layers of the big clusters in flight at the most, 0 = the default again."""
+        self._check(self.lib.kbest_set_bigcluster_work_cap(self.ctx, int(nbytes)))
+
+    def bigcluster_probs_dev(self, m, nLk, subOff, probOff, d_sub, d_probs, d_logZ=None, d_info=None, stream=None, reserve=True):
+        """kbest_bigcluster_probs_f64_dev, asynchronous on `stream`: m, nLk, subOff, probOff are HOST sequences (one entry per
+        cluster), d_sub / d_probs / d_logZ / d_info torch CUDA tensors: cluster k is the (nLk + m) x m column-major block at
+        d_sub[subOff[k]:] (the format the partial clustered kernel hands out) and gets [m][nLk + 1] probabilities at
+        d_probs[probOff[k]:], log Z_k and info (1 answered, 0 infeasible, -3 beyond the work cap)."""
+        def dp(t):
+            return None if t is None else C.c_void_p(t.data_ptr())
+        m = np.ascontiguousarray(m, dtype=np.int32)
+        nLk = np.ascontiguousarray(nLk, dtype=np.int32)
+        subOff = np.ascontiguousarray(subOff, dtype=np.int64)
+        probOff = np.ascontiguousarray(probOff, dtype=np.int64)
+        if reserve and len(m):
+            self.reserve_bigcluster(int(m.max()), int((m + nLk).max()))
+        self._check(self.lib.kbest_bigcluster_probs_f64_dev(self.ctx, len(m), _ptr(m), _ptr(nLk), _ptr(subOff), _ptr(probOff),
+                                                            dp(d_sub), dp(d_probs), dp(d_logZ), dp(d_info),
+                                                            C.c_void_p(stream) if stream else None))
 
     def set_clustered_slot_cap(self, nbytes=0):
         """For tests (kbest_set_clustered_slot_cap): the layers of one cluster at the most, 0 = KBEST_CLUSTER_SLOT_CAP again; a frame
@@ -842,4 +910,14 @@ def hybridProb(costMatrix, nL, nM, k):
     out, method, _, _ = _engine().hybrid_probs([costMatrix], [nL], [nM], k)
     if method[0] == -1:
         raise RuntimeError("hybridProb: frame refused: a cluster holds more rows >= nL than measurements")
+    return out[0]
+
+
+def hybridExactProb(costMatrix, nL, nM, k):
+    """Not in the reference: hybridProb with the exact tier for clusters of 17 .. 20 measurements in between: exact on every gated
+    cluster of at most 20 measurements, assignmentProb(k) on each larger one alone (k = 0: such a frame is refused).  Returns
+    probs[nM][nL+1]; raises RuntimeError only when the frame is refused; an infeasible frame comes back as all zeros."""
+    out, method, _, _, maxCluster, _ = _engine().hybrid_exact_probs([costMatrix], [nL], [nM], k)
+    if method[0] == -1:
+        raise RuntimeError(f"hybridExactProb: frame refused: its largest cluster has {int(maxCluster[0])} measurements")
     return out[0]
