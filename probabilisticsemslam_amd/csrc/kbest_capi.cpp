@@ -282,16 +282,19 @@ Shape choose_shape(const kbest_ctx *ctx, int B, int maxRow, int k)
 struct DevBuf {  // RAII device buffer of the host-pointer entry points, drawn from the context's block cache
     void *p = nullptr;
     kbest_ctx *owner = nullptr;
-    ~DevBuf()
+    ~DevBuf() { release(); }
+    void release()  // back to the cache, before the object's end where the next step of a call should find the block there
     {
         if (!p) return;
+        void *q = p;
+        p = nullptr;
         std::lock_guard<std::mutex> lock(owner->cacheMu);
         for (auto it = owner->cache.begin(); it != owner->cache.end(); ++it)
-            if (it->p == p) {
+            if (it->p == q) {
                 // one-off giants are not kept, and the cache as a whole stays below 4 GiB
                 if (it->n > ((size_t)256 << 20) || owner->cacheBytes > ((size_t)4 << 30)) {
                     owner->cacheBytes -= it->n;
-                    (void)hipFree(p);
+                    (void)hipFree(q);
                     owner->cache.erase(it);
                 } else {
                     it->used = false;
@@ -327,6 +330,113 @@ struct Sub {  // a slice of a DevBuf
     void *p;
     template <class T> T *as() { return static_cast<T *>(p); }
 };
+
+// What the host-pointer probability entries (permanent, belief, clustered, hybrid) share: the scan over the caller's frames, the
+// cost blocks, the meta block and the zeroed probabilities on the device, and the way back into the caller's buffer.  The only
+// place that knows the layout of meta.  An entry's own outputs, checks, reserve call and launch stay with the entry.
+struct FrameBatch {
+    struct Also { DevBuf *buf; size_t bytes; };  // a buffer of the entry's own, drawn in the same go (0 bytes: not drawn)
+    int B = 0, maxRawRow = 1, maxCol = 1;
+    size_t costN = 0, probN = 0;  // doubles up to the end of the last cost block / the last slice
+    const int32_t *nL = nullptr, *nM = nullptr;
+    const int64_t *costOff = nullptr, *probOff = nullptr;
+    DevBuf dCost, dMeta, dProbs;
+
+    int scan(kbest_ctx *ctx, const char *who, int B_, const int32_t *nL_, const int32_t *nM_, const int64_t *costOff_, const int64_t *probOff_)
+    {
+        B = B_;
+        nL = nL_;
+        nM = nM_;
+        costOff = costOff_;
+        probOff = probOff_;
+        for (int b = 0; b < B; b++) {
+            if (nL[b] < 0 || nM[b] < 1 || costOff[b] < 0 || probOff[b] < 0)
+                return fail(ctx, KBEST_ERR_BAD_ARG, (std::string(who) + ": a frame with nL < 0, nM < 1 or a negative offset").c_str());
+            const long long nr = (long long)nL[b] + nM[b];
+            if (nr > maxRawRow) maxRawRow = nr > (1 << 30) ? (1 << 30) : (int)nr;
+            if (nM[b] > maxCol) maxCol = nM[b];
+            const size_t ce = (size_t)costOff[b] + (size_t)nr * (size_t)nM[b], pe = (size_t)probOff[b] + slice(b);
+            if (ce > costN) costN = ce;
+            if (pe > probN) probN = pe;
+        }
+        return KBEST_OK;
+    }
+    size_t slice(int b) const { return (size_t)nM[b] * ((size_t)nL[b] + 1); }  // doubles of frame b's [nM][nL + 1] probabilities
+
+    // meta: costOff[B] | probOff[B] (int64) | nL[B] | nM[B] (int32).  The probabilities are zeroed with hipMemsetAsync on the
+    // context's stream (the note above DevBuf says why not hipMemset): the kernels write what is not zero.
+    int upload(kbest_ctx *ctx, const char *who, const double *cost, std::initializer_list<Also> also = {})
+    {
+        std::vector<unsigned char> meta((size_t)B * 24);
+        memcpy(meta.data(), costOff, (size_t)B * 8);
+        memcpy(meta.data() + (size_t)B * 8, probOff, (size_t)B * 8);
+        memcpy(meta.data() + (size_t)B * 16, nL, (size_t)B * 4);
+        memcpy(meta.data() + (size_t)B * 20, nM, (size_t)B * 4);
+        hipError_t e;
+        bool ok = (e = dCost.alloc(ctx, costN * 8)) == hipSuccess && (e = dMeta.alloc(ctx, meta.size())) == hipSuccess &&
+                  (e = dProbs.alloc(ctx, probN * 8)) == hipSuccess;
+        for (const Also &a : also)
+            ok = ok && (a.bytes == 0 || (e = a.buf->alloc(ctx, a.bytes)) == hipSuccess);
+        if (!ok) return fail(ctx, KBEST_ERR_NOMEM, (std::string(who) + ": device buffers").c_str(), e);
+        HIP_TRY(ctx, hipMemcpy(dCost.p, cost, costN * 8, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(dMeta.p, meta.data(), meta.size(), hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemsetAsync(dProbs.p, 0, probN * 8, ctx->stream));
+        return KBEST_OK;
+    }
+    const int64_t *d_costOff() { return dMeta.as<int64_t>(); }
+    const int64_t *d_probOff() { return dMeta.as<int64_t>() + B; }
+    const int32_t *d_nL() { return dMeta.as<int32_t>() + (size_t)B * 4; }
+    const int32_t *d_nM() { return dMeta.as<int32_t>() + (size_t)B * 5; }
+    const double *d_cost() { return dCost.as<double>(); }
+    double *d_probs() { return dProbs.as<double>(); }
+
+    int download(kbest_ctx *ctx, std::vector<double> &hp)  // (after the entry's hipStreamSynchronize)
+    {
+        hp.resize(probN);
+        HIP_TRY(ctx, hipMemcpy(hp.data(), dProbs.p, probN * 8, hipMemcpyDeviceToHost));
+        return KBEST_OK;
+    }
+    // every frame's own slice only: what lies between the slices in the caller's buffer is the caller's
+    void scatter(const std::vector<double> &hp, double *probs) const
+    {
+        for (int b = 0; b < B; b++) memcpy(probs + probOff[b], hp.data() + probOff[b], slice(b) * 8);
+    }
+    void release()  // (hybrid_impl: before its enumeration draws from the cache)
+    {
+        dProbs.release();
+        dMeta.release();
+        dCost.release();
+    }
+};
+
+// Workgroups of a launch = frames in flight: as many as the batch has, as the chip holds at a time (wavesPerCU: what the
+// kernel's VGPR count leaves of a CU's waves -- the caller says where its number comes from; the kernel's LDS the rest), and as
+// have a slot of the work space within `bytes` (at least one; slotDoubles = 0: a plan without work space).
+int frames_in_flight(const kbest_ctx *ctx, int wavesPerCU, int threads, int lds, long long slotDoubles, int B, size_t bytes)
+{
+    long long g = B;
+    int perCU = wavesPerCU / (threads / 64);
+    if (lds > 0 && perCU > ctx->ldsPerCU / lds) perCU = ctx->ldsPerCU / lds;
+    if (perCU < 1) perCU = 1;
+    const long long resident = (long long)ctx->nCU * perCU;
+    if (g > resident) g = resident;
+    if (slotDoubles > 0) {
+        long long fit = (long long)(bytes / ((size_t)slotDoubles * 8));
+        if (fit < 1) fit = 1;
+        if (g > fit) g = fit;
+    }
+    return (int)g;
+}
+
+// colLimitText: the entry's own "more than ... measurements ..." sentence (callers and tests read it in kbest_last_error)
+int check_frame_shape(kbest_ctx *ctx, const char *who, int B, int maxRawRow, int maxCol, int colLimit, const char *colLimitText)
+{
+    if (B < 0 || maxCol < 1 || maxRawRow < maxCol) return fail(ctx, KBEST_ERR_BAD_ARG, (std::string(who) + ": bad argument").c_str());
+    if (maxCol > colLimit) return fail(ctx, KBEST_ERR_UNSUPPORTED, (std::string(who) + colLimitText).c_str());
+    if (maxRawRow > KBEST_MAX_DIM_WIDE)
+        return fail(ctx, KBEST_ERR_UNSUPPORTED, (std::string(who) + ": more than KBEST_MAX_DIM_WIDE = 1024 rows (nL + nM) in a frame").c_str());
+    return KBEST_OK;
+}
 
 // State slots per matrix for children that are kept in full when they are found: the context's setting (1024), cut
 // down for very large batches so that the whole state work space stays within 16 GiB.  With fewer slots more
@@ -2633,35 +2743,10 @@ extern "C" int kbest_reserve_assoc(kbest_ctx *ctx, int B, int maxRawRow, int max
 }
 
 // ---- permanentProb (kbest_perm.hip) ------------------------------------------------------------------------------------------
-// Workgroups of a launch = frames in flight: as many as the batch has, as the chip holds at a time (the kernel's 105 VGPRs give
-// 4 waves per SIMD, 16 per CU; its LDS the rest), and as have a slice of the work space under the cap (at least one).
-static int perm_grid(const kbest_ctx *ctx, const kb::PermPlan &pl, int B, size_t bytes)
-{
-    long long g = B;
-    int perCU = 16 / (pl.threads / 64);
-    if (pl.lds > 0 && perCU > ctx->ldsPerCU / pl.lds) perCU = ctx->ldsPerCU / pl.lds;
-    if (perCU < 1) perCU = 1;
-    const long long resident = (long long)ctx->nCU * perCU;
-    if (g > resident) g = resident;
-    if (pl.slotDoubles > 0) {
-        const size_t cap = bytes < ctx->permCap ? bytes : ctx->permCap;
-        long long fit = (long long)(cap / ((size_t)pl.slotDoubles * 8));
-        if (fit < 1) fit = 1;
-        if (g > fit) g = fit;
-    }
-    return (int)g;
-}
-
-static int perm_check_shape(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, const char *who)
-{
-    if (B < 0 || maxCol < 1 || maxRawRow < maxCol) return fail(ctx, KBEST_ERR_BAD_ARG, (std::string(who) + ": bad argument").c_str());
-    if (maxCol > KBEST_PERM_MAX_COLS)
-        return fail(ctx, KBEST_ERR_UNSUPPORTED, (std::string(who) + ": more than KBEST_PERM_MAX_COLS = 16 measurements in a frame (the exact "
-                                                 "sums over column subsets stop there: products of 17 gated entries leave the normal doubles)").c_str());
-    if (maxRawRow > KBEST_MAX_DIM_WIDE)
-        return fail(ctx, KBEST_ERR_UNSUPPORTED, (std::string(who) + ": more than KBEST_MAX_DIM_WIDE = 1024 rows (nL + nM) in a frame").c_str());
-    return KBEST_OK;
-}
+// frames_in_flight: the kernel's 105 VGPRs give 4 waves per SIMD, 16 per CU; the work space stays under ctx->permCap
+static const int PERM_WAVES_PER_CU = 16;
+static const char PERM_COLS_TEXT[] = ": more than KBEST_PERM_MAX_COLS = 16 measurements in a frame (the exact "
+                                     "sums over column subsets stop there: products of 17 gated entries leave the normal doubles)";
 
 extern "C" int kbest_set_permanent_work_cap(kbest_ctx *ctx, size_t bytes)
 {
@@ -2674,14 +2759,14 @@ extern "C" int kbest_set_permanent_work_cap(kbest_ctx *ctx, size_t bytes)
 extern "C" int kbest_reserve_permanent(kbest_ctx *ctx, int B, int maxRawRow, int maxCol)
 {
     if (!ctx) return KBEST_ERR_BAD_ARG;
-    int rc = perm_check_shape(ctx, B, maxRawRow, maxCol, "kbest_reserve_permanent");
+    int rc = check_frame_shape(ctx, "kbest_reserve_permanent", B, maxRawRow, maxCol, KBEST_PERM_MAX_COLS, PERM_COLS_TEXT);
     if (rc != KBEST_OK || B == 0) return rc;
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const kb::PermPlan pl = kb::perm_plan(maxRawRow, maxCol, ctx->ldsLimit, ctx->ldsPerCU);
     if (pl.slotDoubles == 0) return KBEST_OK;
     const size_t slot = (size_t)pl.slotDoubles * 8;
-    const int g = perm_grid(ctx, pl, B, (size_t)-1);
+    const int g = frames_in_flight(ctx, PERM_WAVES_PER_CU, pl.threads, pl.lds, pl.slotDoubles, B, ctx->permCap);
     return raw_reserve(ctx, ctx->permBuf, slot * (size_t)g);
 }
 
@@ -2691,7 +2776,7 @@ extern "C" int kbest_permanent_probs_batch_f64_dev(kbest_ctx *ctx, int B, int ma
                                                    void *stream)
 {
     if (!ctx) return KBEST_ERR_BAD_ARG;
-    int rc = perm_check_shape(ctx, B, maxRawRow, maxCol, "kbest_permanent_probs_batch_f64_dev");
+    int rc = check_frame_shape(ctx, "kbest_permanent_probs_batch_f64_dev", B, maxRawRow, maxCol, KBEST_PERM_MAX_COLS, PERM_COLS_TEXT);
     if (rc != KBEST_OK) return rc;
     if (!d_nL || !d_nM || !d_cost || !d_costOff || !d_probs || !d_probOff)
         return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_permanent_probs_batch_f64_dev: bad argument");
@@ -2719,7 +2804,8 @@ extern "C" int kbest_permanent_probs_batch_f64_dev(kbest_ctx *ctx, int B, int ma
     pp.maxRawRow = maxRawRow;
     pp.maxCol = maxCol;
     pp.condition = condition ? 1 : 0;
-    ctx->permLastGrid = perm_grid(ctx, pl, B, ctx->permBuf.bytes);
+    ctx->permLastGrid = frames_in_flight(ctx, PERM_WAVES_PER_CU, pl.threads, pl.lds, pl.slotDoubles, B,
+                                         ctx->permBuf.bytes < ctx->permCap ? ctx->permBuf.bytes : ctx->permCap);
     const hipError_t e = kb::launch_kbest_perm(pp, pl, ctx->permLastGrid, s);
     if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "permanent kernel launch", e);
     return KBEST_OK;
@@ -2740,50 +2826,27 @@ extern "C" int kbest_permanent_probs_batch_f64(kbest_ctx *ctx, int B, const int3
     if (B < 0 || (B > 0 && (!nL || !nM || !cost || !costOff || !probs || !probOff)))
         return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_permanent_probs_batch_f64: bad argument");
     if (B == 0) return KBEST_OK;
-    int maxRawRow = 1, maxCol = 1;
-    size_t costN = 0, probN = 0;
-    for (int b = 0; b < B; b++) {
-        if (nL[b] < 0 || nM[b] < 1 || costOff[b] < 0 || probOff[b] < 0)
-            return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_permanent_probs_batch_f64: a frame with nL < 0, nM < 1 or a negative offset");
-        const long long nr = (long long)nL[b] + nM[b];
-        if (nr > maxRawRow) maxRawRow = nr > (1 << 30) ? (1 << 30) : (int)nr;
-        if (nM[b] > maxCol) maxCol = nM[b];
-        const size_t ce = (size_t)costOff[b] + (size_t)nr * (size_t)nM[b], pe = (size_t)probOff[b] + (size_t)nM[b] * ((size_t)nL[b] + 1);
-        if (ce > costN) costN = ce;
-        if (pe > probN) probN = pe;
-    }
-    int rc = perm_check_shape(ctx, B, maxRawRow, maxCol, "kbest_permanent_probs_batch_f64");
+    const char *who = "kbest_permanent_probs_batch_f64";
+    FrameBatch fb;
+    int rc = fb.scan(ctx, who, B, nL, nM, costOff, probOff);
+    if (rc != KBEST_OK) return rc;
+    rc = check_frame_shape(ctx, who, B, fb.maxRawRow, fb.maxCol, KBEST_PERM_MAX_COLS, PERM_COLS_TEXT);
     if (rc != KBEST_OK) return rc;
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    rc = kbest_reserve_permanent(ctx, B, maxRawRow, maxCol);
+    rc = kbest_reserve_permanent(ctx, B, fb.maxRawRow, fb.maxCol);
     if (rc != KBEST_OK) return rc;
-    DevBuf dCost, dMeta, dProbs, dPerm;
-    // meta: costOff[B] | probOff[B] (int64) | nL[B] | nM[B] (int32)
-    std::vector<unsigned char> meta((size_t)B * 24);
-    memcpy(meta.data(), costOff, (size_t)B * 8);
-    memcpy(meta.data() + (size_t)B * 8, probOff, (size_t)B * 8);
-    memcpy(meta.data() + (size_t)B * 16, nL, (size_t)B * 4);
-    memcpy(meta.data() + (size_t)B * 20, nM, (size_t)B * 4);
-    hipError_t e;
-    if ((e = dCost.alloc(ctx, costN * 8)) != hipSuccess || (e = dMeta.alloc(ctx, meta.size())) != hipSuccess ||
-        (e = dProbs.alloc(ctx, probN * 8)) != hipSuccess || (e = dPerm.alloc(ctx, (size_t)B * 8)) != hipSuccess)
-        return fail(ctx, KBEST_ERR_NOMEM, "kbest_permanent_probs_batch_f64: device buffers", e);
-    HIP_TRY(ctx, hipMemcpy(dCost.p, cost, costN * 8, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(dMeta.p, meta.data(), meta.size(), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemsetAsync(dProbs.p, 0, probN * 8, ctx->stream));  // (gaps between the frames' slices come back as they went in: see below)
-    unsigned char *m8 = dMeta.as<unsigned char>();
-    rc = kbest_permanent_probs_batch_f64_dev(ctx, B, maxRawRow, maxCol, reinterpret_cast<const int32_t *>(m8 + (size_t)B * 16),
-                                             reinterpret_cast<const int32_t *>(m8 + (size_t)B * 20), dCost.as<double>(),
-                                             reinterpret_cast<const int64_t *>(m8), condition, dProbs.as<double>(),
-                                             reinterpret_cast<const int64_t *>(m8 + (size_t)B * 8), dPerm.as<double>(), nullptr);
+    DevBuf dPerm;
+    rc = fb.upload(ctx, who, cost, {{&dPerm, (size_t)B * 8}});
+    if (rc != KBEST_OK) return rc;
+    rc = kbest_permanent_probs_batch_f64_dev(ctx, B, fb.maxRawRow, fb.maxCol, fb.d_nL(), fb.d_nM(), fb.d_cost(), fb.d_costOff(), condition,
+                                             fb.d_probs(), fb.d_probOff(), dPerm.as<double>(), nullptr);
     if (rc != KBEST_OK) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    // every frame's own slice only: what lies between the slices in the caller's buffer is the caller's
-    std::vector<double> hp(probN);
-    HIP_TRY(ctx, hipMemcpy(hp.data(), dProbs.p, probN * 8, hipMemcpyDeviceToHost));
-    for (int b = 0; b < B; b++)
-        memcpy(probs + probOff[b], hp.data() + probOff[b], (size_t)nM[b] * ((size_t)nL[b] + 1) * 8);
+    std::vector<double> hp;
+    rc = fb.download(ctx, hp);
+    if (rc != KBEST_OK) return rc;
+    fb.scatter(hp, probs);
     if (perm) HIP_TRY(ctx, hipMemcpy(perm, dPerm.p, (size_t)B * 8, hipMemcpyDeviceToHost));
     return KBEST_OK;
 }
@@ -2795,34 +2858,9 @@ static kb::LbpPlan lbp_plan_of(const kbest_ctx *ctx, int maxRawRow, int maxCol)
     return kb::lbp_plan(maxRawRow, maxCol, lim);
 }
 
-// Workgroups of a launch = frames in flight: as many as the batch has, as the chip holds at a time (32 waves per CU, the
-// kernel's LDS) and as have a slice of the work space (at most KBEST_LBP_WORK_CAP bytes, at least one).
-static int lbp_grid(const kbest_ctx *ctx, const kb::LbpPlan &pl, int B, size_t bytes)
-{
-    long long g = B;
-    int perCU = 32 / (pl.threads / 64);
-    if (pl.lds > 0 && perCU > ctx->ldsPerCU / pl.lds) perCU = ctx->ldsPerCU / pl.lds;
-    if (perCU < 1) perCU = 1;
-    const long long resident = (long long)ctx->nCU * perCU;
-    if (g > resident) g = resident;
-    if (pl.slotDoubles > 0) {
-        const size_t cap = bytes < KBEST_LBP_WORK_CAP ? bytes : KBEST_LBP_WORK_CAP;
-        long long fit = (long long)(cap / ((size_t)pl.slotDoubles * 8));
-        if (fit < 1) fit = 1;
-        if (g > fit) g = fit;
-    }
-    return (int)g;
-}
-
-static int lbp_check_shape(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, const char *who)
-{
-    if (B < 0 || maxCol < 1 || maxRawRow < maxCol) return fail(ctx, KBEST_ERR_BAD_ARG, (std::string(who) + ": bad argument").c_str());
-    if (maxCol > KBEST_LBP_MAX_COLS)
-        return fail(ctx, KBEST_ERR_UNSUPPORTED, (std::string(who) + ": more than KBEST_LBP_MAX_COLS = 128 measurements in a frame").c_str());
-    if (maxRawRow > KBEST_MAX_DIM_WIDE)
-        return fail(ctx, KBEST_ERR_UNSUPPORTED, (std::string(who) + ": more than KBEST_MAX_DIM_WIDE = 1024 rows (nL + nM) in a frame").c_str());
-    return KBEST_OK;
-}
+// frames_in_flight: 32 waves per CU; the work space stays under KBEST_LBP_WORK_CAP bytes
+static const int LBP_WAVES_PER_CU = 32;
+static const char LBP_COLS_TEXT[] = ": more than KBEST_LBP_MAX_COLS = 128 measurements in a frame";
 
 extern "C" int kbest_set_belief_lds_limit(kbest_ctx *ctx, size_t bytes)
 {
@@ -2835,13 +2873,13 @@ extern "C" int kbest_set_belief_lds_limit(kbest_ctx *ctx, size_t bytes)
 extern "C" int kbest_reserve_belief(kbest_ctx *ctx, int B, int maxRawRow, int maxCol)
 {
     if (!ctx) return KBEST_ERR_BAD_ARG;
-    int rc = lbp_check_shape(ctx, B, maxRawRow, maxCol, "kbest_reserve_belief");
+    int rc = check_frame_shape(ctx, "kbest_reserve_belief", B, maxRawRow, maxCol, KBEST_LBP_MAX_COLS, LBP_COLS_TEXT);
     if (rc != KBEST_OK || B == 0) return rc;
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const kb::LbpPlan pl = lbp_plan_of(ctx, maxRawRow, maxCol);
     if (pl.slotDoubles == 0) return KBEST_OK;
-    const int g = lbp_grid(ctx, pl, B, (size_t)-1);
+    const int g = frames_in_flight(ctx, LBP_WAVES_PER_CU, pl.threads, pl.lds, pl.slotDoubles, B, KBEST_LBP_WORK_CAP);
     return raw_reserve(ctx, ctx->lbpBuf, (size_t)pl.slotDoubles * 8 * (size_t)g);
 }
 
@@ -2851,7 +2889,7 @@ extern "C" int kbest_belief_probs_batch_f64_dev(kbest_ctx *ctx, int B, int maxRa
                                                 const int64_t *d_probOff, int32_t *d_iters, double *d_resid, void *stream)
 {
     if (!ctx) return KBEST_ERR_BAD_ARG;
-    int rc = lbp_check_shape(ctx, B, maxRawRow, maxCol, "kbest_belief_probs_batch_f64_dev");
+    int rc = check_frame_shape(ctx, "kbest_belief_probs_batch_f64_dev", B, maxRawRow, maxCol, KBEST_LBP_MAX_COLS, LBP_COLS_TEXT);
     if (rc != KBEST_OK) return rc;
     if (!d_nL || !d_nM || !d_cost || !d_costOff || !d_probs || !d_probOff || maxIter < 0 || tol != tol)
         return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_belief_probs_batch_f64_dev: bad argument");
@@ -2882,7 +2920,8 @@ extern "C" int kbest_belief_probs_batch_f64_dev(kbest_ctx *ctx, int B, int maxRa
     lp.maxRawRow = maxRawRow;
     lp.maxCol = maxCol;
     lp.condition = condition ? 1 : 0;
-    const hipError_t e = kb::launch_kbest_lbp(lp, pl, lbp_grid(ctx, pl, B, ctx->lbpBuf.bytes), s);
+    const size_t bytes = ctx->lbpBuf.bytes < KBEST_LBP_WORK_CAP ? ctx->lbpBuf.bytes : KBEST_LBP_WORK_CAP;
+    const hipError_t e = kb::launch_kbest_lbp(lp, pl, frames_in_flight(ctx, LBP_WAVES_PER_CU, pl.threads, pl.lds, pl.slotDoubles, B, bytes), s);
     if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "belief-propagation kernel launch", e);
     return KBEST_OK;
 }
@@ -2895,83 +2934,39 @@ extern "C" int kbest_belief_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t
     if (B < 0 || maxIter < 0 || tol != tol || (B > 0 && (!nL || !nM || !cost || !costOff || !probs || !probOff)))
         return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_belief_probs_batch_f64: bad argument");
     if (B == 0) return KBEST_OK;
-    int maxRawRow = 1, maxCol = 1;
-    size_t costN = 0, probN = 0;
-    for (int b = 0; b < B; b++) {
-        if (nL[b] < 0 || nM[b] < 1 || costOff[b] < 0 || probOff[b] < 0)
-            return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_belief_probs_batch_f64: a frame with nL < 0, nM < 1 or a negative offset");
-        const long long nr = (long long)nL[b] + nM[b];
-        if (nr > maxRawRow) maxRawRow = nr > (1 << 30) ? (1 << 30) : (int)nr;
-        if (nM[b] > maxCol) maxCol = nM[b];
-        const size_t ce = (size_t)costOff[b] + (size_t)nr * (size_t)nM[b], pe = (size_t)probOff[b] + (size_t)nM[b] * ((size_t)nL[b] + 1);
-        if (ce > costN) costN = ce;
-        if (pe > probN) probN = pe;
-    }
-    int rc = lbp_check_shape(ctx, B, maxRawRow, maxCol, "kbest_belief_probs_batch_f64");
+    const char *who = "kbest_belief_probs_batch_f64";
+    FrameBatch fb;
+    int rc = fb.scan(ctx, who, B, nL, nM, costOff, probOff);
+    if (rc != KBEST_OK) return rc;
+    rc = check_frame_shape(ctx, who, B, fb.maxRawRow, fb.maxCol, KBEST_LBP_MAX_COLS, LBP_COLS_TEXT);
     if (rc != KBEST_OK) return rc;
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    rc = kbest_reserve_belief(ctx, B, maxRawRow, maxCol);
+    rc = kbest_reserve_belief(ctx, B, fb.maxRawRow, fb.maxCol);
     if (rc != KBEST_OK) return rc;
-    DevBuf dCost, dMeta, dProbs, dOut;
-    // meta: costOff[B] | probOff[B] (int64) | nL[B] | nM[B] (int32);  out: resid[B] (double) | iters[B] (int32)
-    std::vector<unsigned char> meta((size_t)B * 24);
-    memcpy(meta.data(), costOff, (size_t)B * 8);
-    memcpy(meta.data() + (size_t)B * 8, probOff, (size_t)B * 8);
-    memcpy(meta.data() + (size_t)B * 16, nL, (size_t)B * 4);
-    memcpy(meta.data() + (size_t)B * 20, nM, (size_t)B * 4);
-    hipError_t e;
-    if ((e = dCost.alloc(ctx, costN * 8)) != hipSuccess || (e = dMeta.alloc(ctx, meta.size())) != hipSuccess ||
-        (e = dProbs.alloc(ctx, probN * 8)) != hipSuccess || (e = dOut.alloc(ctx, (size_t)B * 12)) != hipSuccess)
-        return fail(ctx, KBEST_ERR_NOMEM, "kbest_belief_probs_batch_f64: device buffers", e);
-    HIP_TRY(ctx, hipMemcpy(dCost.p, cost, costN * 8, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(dMeta.p, meta.data(), meta.size(), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemsetAsync(dProbs.p, 0, probN * 8, ctx->stream));
-    unsigned char *m8 = dMeta.as<unsigned char>(), *o8 = dOut.as<unsigned char>();
-    rc = kbest_belief_probs_batch_f64_dev(ctx, B, maxRawRow, maxCol, reinterpret_cast<const int32_t *>(m8 + (size_t)B * 16),
-                                          reinterpret_cast<const int32_t *>(m8 + (size_t)B * 20), dCost.as<double>(),
-                                          reinterpret_cast<const int64_t *>(m8), condition, tol, maxIter, dProbs.as<double>(),
-                                          reinterpret_cast<const int64_t *>(m8 + (size_t)B * 8),
-                                          reinterpret_cast<int32_t *>(o8 + (size_t)B * 8), reinterpret_cast<double *>(o8), nullptr);
+    DevBuf dOut;  // resid[B] (double) | iters[B] (int32)
+    rc = fb.upload(ctx, who, cost, {{&dOut, (size_t)B * 12}});
+    if (rc != KBEST_OK) return rc;
+    unsigned char *o8 = dOut.as<unsigned char>();
+    rc = kbest_belief_probs_batch_f64_dev(ctx, B, fb.maxRawRow, fb.maxCol, fb.d_nL(), fb.d_nM(), fb.d_cost(), fb.d_costOff(), condition, tol,
+                                          maxIter, fb.d_probs(), fb.d_probOff(), reinterpret_cast<int32_t *>(o8 + (size_t)B * 8),
+                                          reinterpret_cast<double *>(o8), nullptr);
     if (rc != KBEST_OK) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    // every frame's own slice only: what lies between the slices in the caller's buffer is the caller's
-    std::vector<double> hp(probN);
-    HIP_TRY(ctx, hipMemcpy(hp.data(), dProbs.p, probN * 8, hipMemcpyDeviceToHost));
-    for (int b = 0; b < B; b++)
-        memcpy(probs + probOff[b], hp.data() + probOff[b], (size_t)nM[b] * ((size_t)nL[b] + 1) * 8);
+    std::vector<double> hp;
+    rc = fb.download(ctx, hp);
+    if (rc != KBEST_OK) return rc;
+    fb.scatter(hp, probs);
     if (resid) HIP_TRY(ctx, hipMemcpy(resid, o8, (size_t)B * 8, hipMemcpyDeviceToHost));
     if (iters) HIP_TRY(ctx, hipMemcpy(iters, o8 + (size_t)B * 8, (size_t)B * 4, hipMemcpyDeviceToHost));
     return KBEST_OK;
 }
 
 // ---- clusterProb (kbest_cluster.hip) -----------------------------------------------------------------------------------------
-// Workgroups of a launch = frames in flight: as many as the batch has, as the chip holds at a time (the kernel's 155 VGPRs give
-// 3 waves per SIMD, 12 per CU; its LDS the rest), and as have a slot of the work space under the cap (at least one).
-static int cluster_grid(const kbest_ctx *ctx, const kb::ClusterPlan &pl, int B, size_t bytes)
-{
-    long long g = B;
-    int perCU = 12 / (pl.threads / 64);
-    if (pl.lds > 0 && perCU > ctx->ldsPerCU / pl.lds) perCU = ctx->ldsPerCU / pl.lds;
-    if (perCU < 1) perCU = 1;
-    const long long resident = (long long)ctx->nCU * perCU;
-    if (g > resident) g = resident;
-    const size_t cap = bytes < ctx->clusWorkCap ? bytes : ctx->clusWorkCap;
-    long long fit = (long long)(cap / ((size_t)pl.slotDoubles * 8));
-    if (fit < 1) fit = 1;
-    if (g > fit) g = fit;
-    return (int)g;
-}
-
-static int cluster_check_shape(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, const char *who)
-{
-    if (B < 0 || maxCol < 1 || maxRawRow < maxCol) return fail(ctx, KBEST_ERR_BAD_ARG, (std::string(who) + ": bad argument").c_str());
-    if (maxCol > KBEST_CLUSTER_MAX_COLS)
-        return fail(ctx, KBEST_ERR_UNSUPPORTED, (std::string(who) + ": more than KBEST_CLUSTER_MAX_COLS = 128 measurements in a frame").c_str());
-    if (maxRawRow > KBEST_MAX_DIM_WIDE)
-        return fail(ctx, KBEST_ERR_UNSUPPORTED, (std::string(who) + ": more than KBEST_MAX_DIM_WIDE = 1024 rows (nL + nM) in a frame").c_str());
-    return KBEST_OK;
-}
+// frames_in_flight: the kernel's 155 VGPRs give 3 waves per SIMD, 12 per CU; the work space stays under ctx->clusWorkCap.  (The
+// clustered plan's slot is never zero, so the rule's slotDoubles > 0 guard changes nothing here.)
+static const int CLUSTER_WAVES_PER_CU = 12;
+static const char CLUSTER_COLS_TEXT[] = ": more than KBEST_CLUSTER_MAX_COLS = 128 measurements in a frame";
 
 static int cluster_plan_of(kbest_ctx *ctx, int maxRawRow, int maxCol, kb::ClusterPlan &pl, const char *who)
 {
@@ -3006,14 +3001,14 @@ extern "C" int kbest_last_clustered_grid(kbest_ctx *ctx)
 extern "C" int kbest_reserve_clustered(kbest_ctx *ctx, int B, int maxRawRow, int maxCol)
 {
     if (!ctx) return KBEST_ERR_BAD_ARG;
-    int rc = cluster_check_shape(ctx, B, maxRawRow, maxCol, "kbest_reserve_clustered");
+    int rc = check_frame_shape(ctx, "kbest_reserve_clustered", B, maxRawRow, maxCol, KBEST_CLUSTER_MAX_COLS, CLUSTER_COLS_TEXT);
     if (rc != KBEST_OK || B == 0) return rc;
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     kb::ClusterPlan pl;
     rc = cluster_plan_of(ctx, maxRawRow, maxCol, pl, "kbest_reserve_clustered");
     if (rc != KBEST_OK) return rc;
-    const int g = cluster_grid(ctx, pl, B, (size_t)-1);
+    const int g = frames_in_flight(ctx, CLUSTER_WAVES_PER_CU, pl.threads, pl.lds, pl.slotDoubles, B, ctx->clusWorkCap);
     return raw_reserve(ctx, ctx->clusBuf, (size_t)pl.slotDoubles * 8 * (size_t)g);
 }
 
@@ -3031,7 +3026,7 @@ static int cluster_launch_dev(kbest_ctx *ctx, const char *who, const ClusterPart
                               int32_t *d_label, int labelStride, void *stream)
 {
     if (!ctx) return KBEST_ERR_BAD_ARG;
-    int rc = cluster_check_shape(ctx, B, maxRawRow, maxCol, who);
+    int rc = check_frame_shape(ctx, who, B, maxRawRow, maxCol, KBEST_CLUSTER_MAX_COLS, CLUSTER_COLS_TEXT);
     if (rc != KBEST_OK) return rc;
     if (!d_nL || !d_nM || !d_cost || !d_costOff || !d_probs || !d_probOff || (d_label && labelStride < maxCol))
         return fail(ctx, KBEST_ERR_BAD_ARG, (std::string(who) + ": bad argument").c_str());
@@ -3080,7 +3075,8 @@ static int cluster_launch_dev(kbest_ctx *ctx, const char *who, const ClusterPart
         op.openRows = part->d_openRows;
         op.sub = part->d_sub;
     }
-    ctx->clusLastGrid = cluster_grid(ctx, pl, B, ctx->clusBuf.bytes);
+    ctx->clusLastGrid = frames_in_flight(ctx, CLUSTER_WAVES_PER_CU, pl.threads, pl.lds, pl.slotDoubles, B,
+                                         ctx->clusBuf.bytes < ctx->clusWorkCap ? ctx->clusBuf.bytes : ctx->clusWorkCap);
     const hipError_t e = part ? kb::launch_kbest_cluster_partial(cp, op, pl, ctx->clusLastGrid, s)
                               : kb::launch_kbest_cluster(cp, pl, ctx->clusLastGrid, s);
     if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "clustered kernel launch", e);
@@ -3117,56 +3113,33 @@ extern "C" int kbest_clustered_probs_batch_f64(kbest_ctx *ctx, int B, const int3
     if (B < 0 || (B > 0 && (!nL || !nM || !cost || !costOff || !probs || !probOff)))
         return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_clustered_probs_batch_f64: bad argument");
     if (B == 0) return KBEST_OK;
-    int maxRawRow = 1, maxCol = 1;
-    size_t costN = 0, probN = 0;
-    for (int b = 0; b < B; b++) {
-        if (nL[b] < 0 || nM[b] < 1 || costOff[b] < 0 || probOff[b] < 0)
-            return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_clustered_probs_batch_f64: a frame with nL < 0, nM < 1 or a negative offset");
-        const long long nr = (long long)nL[b] + nM[b];
-        if (nr > maxRawRow) maxRawRow = nr > (1 << 30) ? (1 << 30) : (int)nr;
-        if (nM[b] > maxCol) maxCol = nM[b];
-        const size_t ce = (size_t)costOff[b] + (size_t)nr * (size_t)nM[b], pe = (size_t)probOff[b] + (size_t)nM[b] * ((size_t)nL[b] + 1);
-        if (ce > costN) costN = ce;
-        if (pe > probN) probN = pe;
-    }
-    int rc = cluster_check_shape(ctx, B, maxRawRow, maxCol, "kbest_clustered_probs_batch_f64");
+    const char *who = "kbest_clustered_probs_batch_f64";
+    FrameBatch fb;
+    int rc = fb.scan(ctx, who, B, nL, nM, costOff, probOff);
     if (rc != KBEST_OK) return rc;
-    if (label && labelStride < maxCol) return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_clustered_probs_batch_f64: labelStride below the largest nM");
+    rc = check_frame_shape(ctx, who, B, fb.maxRawRow, fb.maxCol, KBEST_CLUSTER_MAX_COLS, CLUSTER_COLS_TEXT);
+    if (rc != KBEST_OK) return rc;
+    if (label && labelStride < fb.maxCol) return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_clustered_probs_batch_f64: labelStride below the largest nM");
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    rc = kbest_reserve_clustered(ctx, B, maxRawRow, maxCol);
+    rc = kbest_reserve_clustered(ctx, B, fb.maxRawRow, fb.maxCol);
     if (rc != KBEST_OK) return rc;
-    DevBuf dCost, dMeta, dProbs, dOut, dLabel;
-    // meta: costOff[B] | probOff[B] (int64) | nL[B] | nM[B] (int32);  out: logPerm[B] (double) | info[B] | maxCluster[B] (int32)
-    std::vector<unsigned char> meta((size_t)B * 24);
-    memcpy(meta.data(), costOff, (size_t)B * 8);
-    memcpy(meta.data() + (size_t)B * 8, probOff, (size_t)B * 8);
-    memcpy(meta.data() + (size_t)B * 16, nL, (size_t)B * 4);
-    memcpy(meta.data() + (size_t)B * 20, nM, (size_t)B * 4);
+    DevBuf dOut, dLabel;  // out: logPerm[B] (double) | info[B] | maxCluster[B] (int32)
     const size_t labelBytes = label ? (size_t)B * (size_t)labelStride * 4 : 0;
-    hipError_t e;
-    if ((e = dCost.alloc(ctx, costN * 8)) != hipSuccess || (e = dMeta.alloc(ctx, meta.size())) != hipSuccess ||
-        (e = dProbs.alloc(ctx, probN * 8)) != hipSuccess || (e = dOut.alloc(ctx, (size_t)B * 16)) != hipSuccess ||
-        (labelBytes && (e = dLabel.alloc(ctx, labelBytes)) != hipSuccess))
-        return fail(ctx, KBEST_ERR_NOMEM, "kbest_clustered_probs_batch_f64: device buffers", e);
-    HIP_TRY(ctx, hipMemcpy(dCost.p, cost, costN * 8, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(dMeta.p, meta.data(), meta.size(), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemsetAsync(dProbs.p, 0, probN * 8, ctx->stream));
-    unsigned char *m8 = dMeta.as<unsigned char>(), *o8 = dOut.as<unsigned char>();
-    rc = kbest_clustered_probs_batch_f64_dev(ctx, B, maxRawRow, maxCol, reinterpret_cast<const int32_t *>(m8 + (size_t)B * 16),
-                                             reinterpret_cast<const int32_t *>(m8 + (size_t)B * 20), dCost.as<double>(),
-                                             reinterpret_cast<const int64_t *>(m8), condition, dProbs.as<double>(),
-                                             reinterpret_cast<const int64_t *>(m8 + (size_t)B * 8), reinterpret_cast<double *>(o8),
+    rc = fb.upload(ctx, who, cost, {{&dOut, (size_t)B * 16}, {&dLabel, labelBytes}});
+    if (rc != KBEST_OK) return rc;
+    unsigned char *o8 = dOut.as<unsigned char>();
+    rc = kbest_clustered_probs_batch_f64_dev(ctx, B, fb.maxRawRow, fb.maxCol, fb.d_nL(), fb.d_nM(), fb.d_cost(), fb.d_costOff(), condition,
+                                             fb.d_probs(), fb.d_probOff(), reinterpret_cast<double *>(o8),
                                              reinterpret_cast<int32_t *>(o8 + (size_t)B * 8),
                                              reinterpret_cast<int32_t *>(o8 + (size_t)B * 12),
                                              labelBytes ? dLabel.as<int32_t>() : nullptr, labelStride, nullptr);
     if (rc != KBEST_OK) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    // every frame's own slice only: what lies between the slices in the caller's buffer is the caller's
-    std::vector<double> hp(probN);
-    HIP_TRY(ctx, hipMemcpy(hp.data(), dProbs.p, probN * 8, hipMemcpyDeviceToHost));
-    for (int b = 0; b < B; b++)
-        memcpy(probs + probOff[b], hp.data() + probOff[b], (size_t)nM[b] * ((size_t)nL[b] + 1) * 8);
+    std::vector<double> hp;
+    rc = fb.download(ctx, hp);
+    if (rc != KBEST_OK) return rc;
+    fb.scatter(hp, probs);
     if (logPerm) HIP_TRY(ctx, hipMemcpy(logPerm, o8, (size_t)B * 8, hipMemcpyDeviceToHost));
     if (info) HIP_TRY(ctx, hipMemcpy(info, o8 + (size_t)B * 8, (size_t)B * 4, hipMemcpyDeviceToHost));
     if (maxCluster) HIP_TRY(ctx, hipMemcpy(maxCluster, o8 + (size_t)B * 12, (size_t)B * 4, hipMemcpyDeviceToHost));
@@ -3645,25 +3618,17 @@ static int hybrid_impl(kbest_ctx *ctx, const char *who, int B, const int32_t *nL
                        const int64_t *costOff, int condition, int k, int maxExact, int maxBig, double *probs, const int64_t *probOff,
                        double *logPerm, int32_t *method, int32_t *nOpen, int32_t *nBig, int32_t *maxCluster)
 {
-    int maxRawRow = 1, maxCol = 1;
-    size_t costN = 0, probN = 0;
-    for (int b = 0; b < B; b++) {
-        if (nL[b] < 0 || nM[b] < 1 || costOff[b] < 0 || probOff[b] < 0)
-            return fail(ctx, KBEST_ERR_BAD_ARG, (std::string(who) + ": a frame with nL < 0, nM < 1 or a negative offset").c_str());
-        const long long nr = (long long)nL[b] + nM[b];
-        if (nr > maxRawRow) maxRawRow = nr > (1 << 30) ? (1 << 30) : (int)nr;
-        if (nM[b] > maxCol) maxCol = nM[b];
-        const size_t ce = (size_t)costOff[b] + (size_t)nr * (size_t)nM[b], pe = (size_t)probOff[b] + (size_t)nM[b] * ((size_t)nL[b] + 1);
-        if (ce > costN) costN = ce;
-        if (pe > probN) probN = pe;
-    }
-    int rc = cluster_check_shape(ctx, B, maxRawRow, maxCol, who);
+    FrameBatch fb;
+    int rc = fb.scan(ctx, who, B, nL, nM, costOff, probOff);
+    if (rc != KBEST_OK) return rc;
+    const int maxRawRow = fb.maxRawRow, maxCol = fb.maxCol;
+    rc = check_frame_shape(ctx, who, B, maxRawRow, maxCol, KBEST_CLUSTER_MAX_COLS, CLUSTER_COLS_TEXT);
     if (rc != KBEST_OK) return rc;
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     rc = kbest_reserve_clustered(ctx, B, maxRawRow, maxCol);
     if (rc != KBEST_OK) return rc;
-    std::vector<double> hp(probN), hLp;
+    std::vector<double> hp, hLp;
     std::vector<int32_t> hInt((size_t)B * 3), hDesc, hRows, hLabel;  // info | maxCluster | nOpen
     struct Open { int b, root, m, cL; size_t rowAt; int big, at; };  // at: its place among the big / the enumerated clusters
     std::vector<Open> open;
@@ -3674,35 +3639,19 @@ static int hybrid_impl(kbest_ctx *ctx, const char *who, int B, const int32_t *nL
     std::vector<int64_t> bPo;
     const size_t descStride = (size_t)maxCol, rowStride = (size_t)maxRawRow;
     {
-        DevBuf dCost, dMeta, dProbs, dOut, dLabel, dDesc, dRows, dSub, dLp;
-        // meta: costOff[B] | probOff[B] (int64) | nL[B] | nM[B] (int32);  out: info[B] | maxCluster[B] | nOpen[B] (int32)
-        std::vector<unsigned char> meta((size_t)B * 24);
-        memcpy(meta.data(), costOff, (size_t)B * 8);
-        memcpy(meta.data() + (size_t)B * 8, probOff, (size_t)B * 8);
-        memcpy(meta.data() + (size_t)B * 16, nL, (size_t)B * 4);
-        memcpy(meta.data() + (size_t)B * 20, nM, (size_t)B * 4);
-        hipError_t e;
-        if ((e = dCost.alloc(ctx, costN * 8)) != hipSuccess || (e = dMeta.alloc(ctx, meta.size())) != hipSuccess ||
-            (e = dProbs.alloc(ctx, probN * 8)) != hipSuccess || (e = dOut.alloc(ctx, (size_t)B * 12)) != hipSuccess ||
-            (e = dLabel.alloc(ctx, (size_t)B * maxCol * 4)) != hipSuccess || (e = dDesc.alloc(ctx, (size_t)B * descStride * 16)) != hipSuccess ||
-            (e = dRows.alloc(ctx, (size_t)B * rowStride * 4)) != hipSuccess || (e = dSub.alloc(ctx, costN * 8)) != hipSuccess ||
-            (logPerm && (e = dLp.alloc(ctx, (size_t)B * 8)) != hipSuccess))
-            return fail(ctx, KBEST_ERR_NOMEM, (std::string(who) + ": device buffers").c_str(), e);
-        HIP_TRY(ctx, hipMemcpy(dCost.p, cost, costN * 8, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemcpy(dMeta.p, meta.data(), meta.size(), hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemsetAsync(dProbs.p, 0, probN * 8, ctx->stream));
-        unsigned char *m8 = dMeta.as<unsigned char>();
+        DevBuf dOut, dLabel, dDesc, dRows, dSub, dLp;  // out: info[B] | maxCluster[B] | nOpen[B] (int32)
+        rc = fb.upload(ctx, who, cost, {{&dOut, (size_t)B * 12}, {&dLabel, (size_t)B * maxCol * 4}, {&dDesc, (size_t)B * descStride * 16},
+                                        {&dRows, (size_t)B * rowStride * 4}, {&dSub, fb.costN * 8}, {&dLp, logPerm ? (size_t)B * 8 : 0}});
+        if (rc != KBEST_OK) return rc;
         int32_t *o4 = dOut.as<int32_t>();
-        rc = kbest_clustered_partial_batch_f64_dev(ctx, B, maxRawRow, maxCol, reinterpret_cast<const int32_t *>(m8 + (size_t)B * 16),
-                                                   reinterpret_cast<const int32_t *>(m8 + (size_t)B * 20), dCost.as<double>(),
-                                                   reinterpret_cast<const int64_t *>(m8), condition, maxExact, dProbs.as<double>(),
-                                                   reinterpret_cast<const int64_t *>(m8 + (size_t)B * 8),
-                                                   logPerm ? dLp.as<double>() : nullptr, o4, o4 + B,
+        rc = kbest_clustered_partial_batch_f64_dev(ctx, B, maxRawRow, maxCol, fb.d_nL(), fb.d_nM(), fb.d_cost(), fb.d_costOff(), condition,
+                                                   maxExact, fb.d_probs(), fb.d_probOff(), logPerm ? dLp.as<double>() : nullptr, o4, o4 + B,
                                                    dLabel.as<int32_t>(), maxCol, o4 + 2 * (size_t)B, dDesc.as<int32_t>(),
                                                    (int)descStride, dRows.as<int32_t>(), (int)rowStride, dSub.as<double>(), nullptr);
         if (rc != KBEST_OK) return rc;
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        HIP_TRY(ctx, hipMemcpy(hp.data(), dProbs.p, probN * 8, hipMemcpyDeviceToHost));
+        rc = fb.download(ctx, hp);
+        if (rc != KBEST_OK) return rc;
         HIP_TRY(ctx, hipMemcpy(hInt.data(), dOut.p, (size_t)B * 12, hipMemcpyDeviceToHost));
         if (logPerm) {
             hLp.resize(B);
@@ -3783,6 +3732,7 @@ static int hybrid_impl(kbest_ctx *ctx, const char *who, int B, const int32_t *nL
                 rc = big_reserve(ctx, bigLayers < ctx->bigWorkCap ? bigLayers : ctx->bigWorkCap, bigM, bigRows);
                 if (rc != KBEST_OK) return rc;
                 DevBuf dBigP, dBigOut;  // out: logZ[nb] (double) | info[nb] (int32)
+                hipError_t e;
                 if ((e = dBigP.alloc(ctx, bpat * 8)) != hipSuccess || (e = dBigOut.alloc(ctx, (size_t)nb * 12)) != hipSuccess)
                     return fail(ctx, KBEST_ERR_NOMEM, (std::string(who) + ": device buffers").c_str(), e);
                 unsigned char *b8 = dBigOut.as<unsigned char>();
@@ -3799,6 +3749,7 @@ static int hybrid_impl(kbest_ctx *ctx, const char *who, int B, const int32_t *nL
                 HIP_TRY(ctx, hipMemcpy(bigInfo.data(), b8 + (size_t)nb * 8, (size_t)nb * 4, hipMemcpyDeviceToHost));
             }
         }
+        fb.release();  // with the buffers above: the enumeration below draws from the same cache
     }
     const int32_t *hInfo = hInt.data(), *hOpen = hInt.data() + 2 * (size_t)B;
     for (int b = 0; b < B; b++) method[b] = hInfo[b] < 0 ? -1 : hInfo[b] == 0 ? -2 : 0;
@@ -3874,9 +3825,7 @@ static int hybrid_impl(kbest_ctx *ctx, const char *who, int B, const int32_t *nL
             if (method[b] == -1) logPerm[b] = std::numeric_limits<double>::quiet_NaN();
         }
     }
-    // every frame's own slice only: what lies between the slices in the caller's buffer is the caller's
-    for (int b = 0; b < B; b++)
-        memcpy(probs + probOff[b], hp.data() + probOff[b], (size_t)nM[b] * ((size_t)nL[b] + 1) * 8);
+    fb.scatter(hp, probs);
     if (nOpen) memcpy(nOpen, hOpen, (size_t)B * 4);
     if (maxCluster) memcpy(maxCluster, hInt.data() + B, (size_t)B * 4);
     return KBEST_OK;

@@ -72,6 +72,16 @@ size_t kbest_one(size_t k, size_t numRow, size_t numCol, bool maximize, const do
     return n;
 }
 
+// the entries' flat [nM][nL + 1] probabilities as the reference's vector of rows, each `width` long (nL + 1 but for the
+// single-column case of assignmentProb / bruteForceProb)
+std::vector<std::vector<double>> rows_of(const std::vector<double> &flat, size_t nL, size_t nM, size_t width)
+{
+    std::vector<std::vector<double>> probs(nM, std::vector<double>(width, 0.0));
+    for (size_t c = 0; c < nM; c++)
+        for (size_t j = 0; j <= nL; j++) probs[c][j] = flat[c * (nL + 1) + j];
+    return probs;
+}
+
 }  // namespace
 
 MurtyHyp::MurtyHyp(const size_t numRow, const size_t numCol)
@@ -184,10 +194,7 @@ std::vector<std::vector<double>> assignmentProb(const std::vector<double> &costM
     const size_t width = (nM == 1) ? costMatrix.size() : nL + 1;
     std::vector<double> flat(nM * (nL + 1), 0.0);
     check(ctx, kbest_weights_batch_f64(ctx, 1, &l, &m, costMatrix.data(), &zero, (int)k, flat.data(), &zero, nullptr));
-    std::vector<std::vector<double>> probs(nM, std::vector<double>(width, 0.0));
-    for (size_t c = 0; c < nM; c++)
-        for (size_t j = 0; j <= nL; j++) probs[c][j] = flat[c * (nL + 1) + j];
-    return probs;
+    return rows_of(flat, nL, nM, width);
 }
 
 std::vector<double> conditionCosts(const std::vector<double> &costs, size_t nRows, size_t nCols,
@@ -231,10 +238,7 @@ std::vector<std::vector<double>> bruteForceProb(const std::vector<double> &costM
     std::vector<double> flat(nM * (nL + 1), 0.0);
     check(ctx, kbest_bruteforce_probs_batch_f64(ctx, 1, &l, &m, costMatrix.data(), &zero, (int)upperK, flat.data(), &zero,
                                                 nullptr));
-    std::vector<std::vector<double>> probs(nM, std::vector<double>(width, 0.0));
-    for (size_t c = 0; c < nM; c++)
-        for (size_t j = 0; j <= nL; j++) probs[c][j] = flat[c * (nL + 1) + j];
-    return probs;
+    return rows_of(flat, nL, nM, width);
 }
 
 std::vector<std::vector<double>> permanentProb(std::vector<double> costMatrix, size_t nL, size_t nM, int permOpt)
@@ -247,10 +251,7 @@ std::vector<std::vector<double>> permanentProb(std::vector<double> costMatrix, s
     const int64_t zero = 0;
     std::vector<double> flat(nM * (nL + 1), 0.0);
     check(ctx, kbest_permanent_probs_batch_f64(ctx, 1, &l, &m, costMatrix.data(), &zero, 0, flat.data(), &zero, nullptr));
-    std::vector<std::vector<double>> probs(nM, std::vector<double>(nL + 1, 0.0));
-    for (size_t c = 0; c < nM; c++)
-        for (size_t j = 0; j <= nL; j++) probs[c][j] = flat[c * (nL + 1) + j];
-    return probs;
+    return rows_of(flat, nL, nM, nL + 1);
 }
 
 std::vector<std::vector<double>> beliefProb(const std::vector<double> &costMatrix, size_t nL, size_t nM)
@@ -261,10 +262,7 @@ std::vector<std::vector<double>> beliefProb(const std::vector<double> &costMatri
     std::vector<double> flat(nM * (nL + 1), 0.0);
     check(ctx, kbest_belief_probs_batch_f64(ctx, 1, &l, &m, costMatrix.data(), &zero, 0, 1e-12, 10000, flat.data(), &zero, nullptr,
                                             nullptr));
-    std::vector<std::vector<double>> probs(nM, std::vector<double>(nL + 1, 0.0));
-    for (size_t c = 0; c < nM; c++)
-        for (size_t j = 0; j <= nL; j++) probs[c][j] = flat[c * (nL + 1) + j];
-    return probs;
+    return rows_of(flat, nL, nM, nL + 1);
 }
 
 std::vector<std::vector<double>> clusterProb(const std::vector<double> &costMatrix, size_t nL, size_t nM)
@@ -279,10 +277,7 @@ std::vector<std::vector<double>> clusterProb(const std::vector<double> &costMatr
     if (info < 0)
         throw std::runtime_error("clusterProb: frame refused (info " + std::to_string(info) + "): its largest cluster has " +
                                  std::to_string(maxCluster) + " measurements");
-    std::vector<std::vector<double>> probs(nM, std::vector<double>(nL + 1, 0.0));
-    for (size_t c = 0; c < nM; c++)
-        for (size_t j = 0; j <= nL; j++) probs[c][j] = flat[c * (nL + 1) + j];
-    return probs;
+    return rows_of(flat, nL, nM, nL + 1);
 }
 
 std::vector<std::vector<double>> hybridProb(const std::vector<double> &costMatrix, size_t nL, size_t nM, size_t k)
@@ -295,10 +290,7 @@ std::vector<std::vector<double>> hybridProb(const std::vector<double> &costMatri
     check(ctx, kbest_hybrid_probs_batch_f64(ctx, 1, &l, &m, costMatrix.data(), &zero, 0, (int)k, 0, flat.data(), &zero, &method,
                                             nullptr, nullptr));
     if (method == -1) throw std::runtime_error("hybridProb: frame refused: a cluster holds more rows >= nL than measurements");
-    std::vector<std::vector<double>> probs(nM, std::vector<double>(nL + 1, 0.0));
-    for (size_t c = 0; c < nM; c++)
-        for (size_t j = 0; j <= nL; j++) probs[c][j] = flat[c * (nL + 1) + j];
-    return probs;
+    return rows_of(flat, nL, nM, nL + 1);
 }
 
 std::vector<std::vector<double>> hybridExactProb(const std::vector<double> &costMatrix, size_t nL, size_t nM, size_t k)
@@ -312,10 +304,7 @@ std::vector<std::vector<double>> hybridExactProb(const std::vector<double> &cost
                                                   flat.data(), &zero, nullptr, &method, nullptr, nullptr, &maxCluster));
     if (method == -1)
         throw std::runtime_error("hybridExactProb: frame refused: its largest cluster has " + std::to_string(maxCluster) + " measurements");
-    std::vector<std::vector<double>> probs(nM, std::vector<double>(nL + 1, 0.0));
-    for (size_t c = 0; c < nM; c++)
-        for (size_t j = 0; j <= nL; j++) probs[c][j] = flat[c * (nL + 1) + j];
-    return probs;
+    return rows_of(flat, nL, nM, nL + 1);
 }
 
 kbest_ctx *kbest_shims_context() { return global_ctx(); }

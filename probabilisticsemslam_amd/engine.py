@@ -193,6 +193,40 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _dptr(t):
+    """Device pointer of a torch CUDA tensor (or a raw address, or None)."""
+    return None if t is None else C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
+
+
+def _stream(s):
+    return C.c_void_p(s) if s else None
+
+
+def _pack_frames(costs, nL, nM, who):
+    """The frame batch of the probability entries: costs is a list of 1-D column-major (nL+nM) x nM blocks.  Returns (nL, nM
+    as int32 arrays, B, the blocks end to end, costOff[B], probOff[B], psizes[B]: doubles of every frame's [nM, nL+1] slice,
+    probs: the zeroed slices end to end)."""
+    nL = np.ascontiguousarray(nL, dtype=np.int32)
+    nM = np.ascontiguousarray(nM, dtype=np.int32)
+    B = len(nL)
+    sizes = (nL.astype(np.int64) + nM) * nM
+    psizes = nM.astype(np.int64) * (nL.astype(np.int64) + 1)
+    costOff = np.zeros(B, np.int64)
+    probOff = np.zeros(B, np.int64)
+    costOff[1:] = np.cumsum(sizes)[:-1]
+    probOff[1:] = np.cumsum(psizes)[:-1]
+    flat = np.concatenate([np.zeros(0, np.float64)] + [np.ascontiguousarray(c, dtype=np.float64).reshape(-1) for c in costs])
+    if flat.size != int(sizes.sum()):
+        raise KBestError(f"{who}: a cost block is not (nL + nM) x nM")
+    probs = np.zeros(int(psizes.sum()), np.float64)
+    return nL, nM, B, flat, costOff, probOff, psizes, probs
+
+
+def _split_probs(probs, probOff, psizes, nL, nM):
+    """The frames' [nM, nL+1] views of probs."""
+    return [probs[probOff[b]: probOff[b] + psizes[b]].reshape(int(nM[b]), int(nL[b]) + 1) for b in range(len(nL))]
+
+
 class KBestEngine:
     """One engine context = one GPU, one stream, one hypothesis-state workspace."""
 
@@ -341,46 +375,24 @@ class KBestEngine:
         """Batched assignmentProb (condition=False) or, with condition=True, the whole
         conditionCosts -> assignmentProb -> scatter chain of getAssignmentProbs on raw cost blocks.
         costs: list of 1-D column-major (nL+nM) x nM blocks.  Returns (list of [nM, nL+1] arrays, nf[B])."""
-        nL = np.ascontiguousarray(nL, dtype=np.int32)
-        nM = np.ascontiguousarray(nM, dtype=np.int32)
-        B = len(nL)
-        sizes = [(int(nL[b]) + int(nM[b])) * int(nM[b]) for b in range(B)]
-        psizes = [int(nM[b]) * (int(nL[b]) + 1) for b in range(B)]
-        costOff = np.zeros(B, np.int64)
-        probOff = np.zeros(B, np.int64)
-        costOff[1:] = np.cumsum(sizes)[:-1]
-        probOff[1:] = np.cumsum(psizes)[:-1]
-        flat = np.concatenate([np.ascontiguousarray(c, dtype=np.float64).reshape(-1) for c in costs])
-        probs = np.zeros(int(sum(psizes)), np.float64)
+        nL, nM, B, flat, costOff, probOff, psizes, probs = _pack_frames(costs, nL, nM, "weights")
         nf = np.zeros(B, np.int32)
         fn = (self.lib.kbest_bruteforce_probs_batch_f64 if brute_force else
               self.lib.kbest_assoc_probs_batch_f64 if condition else self.lib.kbest_weights_batch_f64)
         self._check(fn(self.ctx, B, _ptr(nL), _ptr(nM), _ptr(flat), _ptr(costOff), k, _ptr(probs), _ptr(probOff),
                        _ptr(nf)))
-        out = [probs[probOff[b]: probOff[b] + psizes[b]].reshape(int(nM[b]), int(nL[b]) + 1) for b in range(B)]
+        out = _split_probs(probs, probOff, psizes, nL, nM)
         return out, nf
 
     def permanent_probs(self, costs, nL, nM, condition=False):
         """Batched permanentProb (assignment.h:13): the EXACT association probabilities, nM <= 16 (kbest_perm.hip).  Packing as
         weights(); condition=True: raw blocks, conditionCosts -> permanentProb -> scatter back (getAssignmentProbs with usePerm).
         Returns (list of [nM, nL+1] arrays, perm[B]: the permanent of every frame's toProbs matrix, the normaliser)."""
-        nL = np.ascontiguousarray(nL, dtype=np.int32)
-        nM = np.ascontiguousarray(nM, dtype=np.int32)
-        B = len(nL)
-        sizes = [(int(nL[b]) + int(nM[b])) * int(nM[b]) for b in range(B)]
-        psizes = [int(nM[b]) * (int(nL[b]) + 1) for b in range(B)]
-        costOff = np.zeros(B, np.int64)
-        probOff = np.zeros(B, np.int64)
-        costOff[1:] = np.cumsum(sizes)[:-1]
-        probOff[1:] = np.cumsum(psizes)[:-1]
-        flat = np.concatenate([np.ascontiguousarray(c, dtype=np.float64).reshape(-1) for c in costs])
-        if flat.size != sum(sizes):
-            raise KBestError("permanent_probs: a cost block is not (nL + nM) x nM")
-        probs = np.zeros(int(sum(psizes)), np.float64)
+        nL, nM, B, flat, costOff, probOff, psizes, probs = _pack_frames(costs, nL, nM, "permanent_probs")
         perm = np.zeros(B, np.float64)
         self._check(self.lib.kbest_permanent_probs_batch_f64(self.ctx, B, _ptr(nL), _ptr(nM), _ptr(flat), _ptr(costOff),
                                                              int(bool(condition)), _ptr(probs), _ptr(probOff), _ptr(perm)))
-        out = [probs[probOff[b]: probOff[b] + psizes[b]].reshape(int(nM[b]), int(nL[b]) + 1) for b in range(B)]
+        out = _split_probs(probs, probOff, psizes, nL, nM)
         return out, perm
 
     def set_permanent_work_cap(self, nbytes=0):
@@ -397,25 +409,13 @@ class KBestEngine:
         nL + nM <= 1024.  Packing and condition as permanent_probs().  Stops after the sweep whose resid <= tol or after max_iter
         sweeps (tol <= 0: exactly max_iter).  Returns (list of [nM, nL+1] arrays, iters[B]: sweeps run, -2 for an infeasible frame
         (all zeros), resid[B]: the last sweep's max |nu' - nu|)."""
-        nL = np.ascontiguousarray(nL, dtype=np.int32)
-        nM = np.ascontiguousarray(nM, dtype=np.int32)
-        B = len(nL)
-        sizes = [(int(nL[b]) + int(nM[b])) * int(nM[b]) for b in range(B)]
-        psizes = [int(nM[b]) * (int(nL[b]) + 1) for b in range(B)]
-        costOff = np.zeros(B, np.int64)
-        probOff = np.zeros(B, np.int64)
-        costOff[1:] = np.cumsum(sizes)[:-1]
-        probOff[1:] = np.cumsum(psizes)[:-1]
-        flat = np.concatenate([np.ascontiguousarray(c, dtype=np.float64).reshape(-1) for c in costs])
-        if flat.size != sum(sizes):
-            raise KBestError("belief_probs: a cost block is not (nL + nM) x nM")
-        probs = np.zeros(int(sum(psizes)), np.float64)
+        nL, nM, B, flat, costOff, probOff, psizes, probs = _pack_frames(costs, nL, nM, "belief_probs")
         iters = np.zeros(B, np.int32)
         resid = np.zeros(B, np.float64)
         self._check(self.lib.kbest_belief_probs_batch_f64(self.ctx, B, _ptr(nL), _ptr(nM), _ptr(flat), _ptr(costOff),
                                                           int(bool(condition)), float(tol), int(max_iter), _ptr(probs),
                                                           _ptr(probOff), _ptr(iters), _ptr(resid)))
-        out = [probs[probOff[b]: probOff[b] + psizes[b]].reshape(int(nM[b]), int(nL[b]) + 1) for b in range(B)]
+        out = _split_probs(probs, probOff, psizes, nL, nM)
         return out, iters, resid
 
     def set_belief_lds_limit(self, nbytes=0):
@@ -429,19 +429,7 @@ class KBestEngine:
         [nM, nL+1] arrays, logPerm[B]: the sum of log Z_k over the clusters (-inf: infeasible, NaN: refused), info[B]: the number of
         clusters, 0 for an infeasible frame, -2 / -3 for a refused one (all zeros), maxCluster[B]: measurements of the largest
         cluster) and, with labels=True, label[B, max nM]: the lowest column of every column's cluster, -1 beyond the frame's nM."""
-        nL = np.ascontiguousarray(nL, dtype=np.int32)
-        nM = np.ascontiguousarray(nM, dtype=np.int32)
-        B = len(nL)
-        sizes = [(int(nL[b]) + int(nM[b])) * int(nM[b]) for b in range(B)]
-        psizes = [int(nM[b]) * (int(nL[b]) + 1) for b in range(B)]
-        costOff = np.zeros(B, np.int64)
-        probOff = np.zeros(B, np.int64)
-        costOff[1:] = np.cumsum(sizes)[:-1]
-        probOff[1:] = np.cumsum(psizes)[:-1]
-        flat = np.concatenate([np.ascontiguousarray(c, dtype=np.float64).reshape(-1) for c in costs])
-        if flat.size != sum(sizes):
-            raise KBestError("clustered_probs: a cost block is not (nL + nM) x nM")
-        probs = np.zeros(int(sum(psizes)), np.float64)
+        nL, nM, B, flat, costOff, probOff, psizes, probs = _pack_frames(costs, nL, nM, "clustered_probs")
         logPerm = np.zeros(B, np.float64)
         info = np.zeros(B, np.int32)
         maxCluster = np.zeros(B, np.int32)
@@ -450,7 +438,7 @@ class KBestEngine:
         self._check(self.lib.kbest_clustered_probs_batch_f64(self.ctx, B, _ptr(nL), _ptr(nM), _ptr(flat), _ptr(costOff),
                                                              int(bool(condition)), _ptr(probs), _ptr(probOff), _ptr(logPerm),
                                                              _ptr(info), _ptr(maxCluster), _ptr(lab), stride))
-        out = [probs[probOff[b]: probOff[b] + psizes[b]].reshape(int(nM[b]), int(nL[b]) + 1) for b in range(B)]
+        out = _split_probs(probs, probOff, psizes, nL, nM)
         return (out, logPerm, info, maxCluster, lab) if labels else (out, logPerm, info, maxCluster)
 
     def exact_or_belief_probs(self, costs, nL, nM, condition=False, tol=1e-12, max_iter=10000):
@@ -476,27 +464,14 @@ class KBestEngine:
         nL + nM <= 1024.  Packing and condition as permanent_probs().  Returns (list of [nM, nL+1] arrays, method[B]: 0 every
         cluster exact (the bits of clustered_probs), 1 some clusters enumerated and every enumeration ended before k, 2 some
         enumeration cut at k, -2 infeasible (all zeros), -1 refused (all zeros), nOpen[B]: clusters enumerated, maxCluster[B])."""
-        nL = np.ascontiguousarray(nL, dtype=np.int32)
-        nM = np.ascontiguousarray(nM, dtype=np.int32)
-        B = len(nL)
-        sizes = [(int(nL[b]) + int(nM[b])) * int(nM[b]) for b in range(B)]
-        psizes = [int(nM[b]) * (int(nL[b]) + 1) for b in range(B)]
-        costOff = np.zeros(B, np.int64)
-        probOff = np.zeros(B, np.int64)
-        costOff[1:] = np.cumsum(sizes)[:-1]
-        probOff[1:] = np.cumsum(psizes)[:-1]
-        flat = (np.concatenate([np.ascontiguousarray(c, dtype=np.float64).reshape(-1) for c in costs]) if B
-                else np.zeros(0, np.float64))
-        if flat.size != sum(sizes):
-            raise KBestError("hybrid_probs: a cost block is not (nL + nM) x nM")
-        probs = np.zeros(int(sum(psizes)), np.float64)
+        nL, nM, B, flat, costOff, probOff, psizes, probs = _pack_frames(costs, nL, nM, "hybrid_probs")
         method = np.zeros(B, np.int32)
         nOpen = np.zeros(B, np.int32)
         maxCluster = np.zeros(B, np.int32)
         self._check(self.lib.kbest_hybrid_probs_batch_f64(self.ctx, B, _ptr(nL), _ptr(nM), _ptr(flat), _ptr(costOff),
                                                           int(bool(condition)), int(k), int(max_exact), _ptr(probs), _ptr(probOff),
                                                           _ptr(method), _ptr(nOpen), _ptr(maxCluster)))
-        out = [probs[probOff[b]: probOff[b] + psizes[b]].reshape(int(nM[b]), int(nL[b]) + 1) for b in range(B)]
+        out = _split_probs(probs, probOff, psizes, nL, nM)
         return out, method, nOpen, maxCluster
 
     def hybrid_exact_probs(self, costs, nL, nM, k=0, condition=False, max_exact=16, max_big=20):
@@ -506,20 +481,7 @@ class KBestEngine:
         frame when k = 0.  Returns (list of [nM, nL+1] arrays, method[B]: 0 every cluster exact, 1 / 2 some cluster enumerated
         (complete / cut at k), -2 infeasible (all zeros), -1 refused (all zeros), nOpen[B]: clusters beyond max_exact, nBig[B]: those
         of them answered exactly, maxCluster[B], logPerm[B]: the sum of log Z_k over the exactly answered clusters)."""
-        nL = np.ascontiguousarray(nL, dtype=np.int32)
-        nM = np.ascontiguousarray(nM, dtype=np.int32)
-        B = len(nL)
-        sizes = [(int(nL[b]) + int(nM[b])) * int(nM[b]) for b in range(B)]
-        psizes = [int(nM[b]) * (int(nL[b]) + 1) for b in range(B)]
-        costOff = np.zeros(B, np.int64)
-        probOff = np.zeros(B, np.int64)
-        costOff[1:] = np.cumsum(sizes)[:-1]
-        probOff[1:] = np.cumsum(psizes)[:-1]
-        flat = (np.concatenate([np.ascontiguousarray(c, dtype=np.float64).reshape(-1) for c in costs]) if B
-                else np.zeros(0, np.float64))
-        if flat.size != sum(sizes):
-            raise KBestError("hybrid_exact_probs: a cost block is not (nL + nM) x nM")
-        probs = np.zeros(int(sum(psizes)), np.float64)
+        nL, nM, B, flat, costOff, probOff, psizes, probs = _pack_frames(costs, nL, nM, "hybrid_exact_probs")
         method = np.zeros(B, np.int32)
         nOpen = np.zeros(B, np.int32)
         nBig = np.zeros(B, np.int32)
@@ -529,7 +491,7 @@ class KBestEngine:
                                                                 int(bool(condition)), int(k), int(max_exact), int(max_big),
                                                                 _ptr(probs), _ptr(probOff), _ptr(logPerm), _ptr(method), _ptr(nOpen),
                                                                 _ptr(nBig), _ptr(maxCluster)))
-        out = [probs[probOff[b]: probOff[b] + psizes[b]].reshape(int(nM[b]), int(nL[b]) + 1) for b in range(B)]
+        out = _split_probs(probs, probOff, psizes, nL, nM)
         return out, method, nOpen, nBig, maxCluster, logPerm
 
     def reserve_bigcluster(self, maxM, maxRows):
@@ -546,8 +508,6 @@ class KBestEngine:
         cluster), d_sub / d_probs / d_logZ / d_info torch CUDA tensors: cluster k is the (nLk + m) x m column-major block at
         d_sub[subOff[k]:] (the format the partial clustered kernel hands out) and gets [m][nLk + 1] probabilities at
         d_probs[probOff[k]:], log Z_k and info (1 answered, 0 infeasible, -3 beyond the work cap)."""
-        def dp(t):
-            return None if t is None else C.c_void_p(t.data_ptr())
         m = np.ascontiguousarray(m, dtype=np.int32)
         nLk = np.ascontiguousarray(nLk, dtype=np.int32)
         subOff = np.ascontiguousarray(subOff, dtype=np.int64)
@@ -555,8 +515,8 @@ class KBestEngine:
         if reserve and len(m):
             self.reserve_bigcluster(int(m.max()), int((m + nLk).max()))
         self._check(self.lib.kbest_bigcluster_probs_f64_dev(self.ctx, len(m), _ptr(m), _ptr(nLk), _ptr(subOff), _ptr(probOff),
-                                                            dp(d_sub), dp(d_probs), dp(d_logZ), dp(d_info),
-                                                            C.c_void_p(stream) if stream else None))
+                                                            _dptr(d_sub), _dptr(d_probs), _dptr(d_logZ), _dptr(d_info),
+                                                            _stream(stream)))
 
     def set_clustered_slot_cap(self, nbytes=0):
         """For tests (kbest_set_clustered_slot_cap): the layers of one cluster at the most, 0 = KBEST_CLUSTER_SLOT_CAP again; a frame
@@ -646,12 +606,9 @@ class KBestEngine:
         else:
             self.reserve(B, N, k)
 
-        def dp(t):
-            return None if t is None else C.c_void_p(t.data_ptr())
-
-        self._check(self.lib.kbest_batch_f64_dev(self.ctx, C.byref(o), B, N, M, dp(d_nRow), dp(d_nCol), dp(d_cost),
-                                                 dp(d_costOff), k, dp(d_row4col), dp(d_col4row), dp(d_gain), dp(d_nf),
-                                                 dp(d_pushed), C.c_void_p(stream) if stream else None))
+        self._check(self.lib.kbest_batch_f64_dev(self.ctx, C.byref(o), B, N, M, _dptr(d_nRow), _dptr(d_nCol), _dptr(d_cost),
+                                                 _dptr(d_costOff), k, _dptr(d_row4col), _dptr(d_col4row), _dptr(d_gain), _dptr(d_nf),
+                                                 _dptr(d_pushed), _stream(stream)))
 
 
     def resolve_ties_dev(self, d_cost, B, N, M, k, d_row4col, d_col4row, d_gain, d_tie_flags, maximize=False, cutoff=None, stream=None,
@@ -663,32 +620,25 @@ class KBestEngine:
         the re-run's count (without it the launch's count stays, which a cutoff on gains that round apart can make stale)."""
         o = self._opts(maximize, cutoff, (KBEST_FLAG_TABLES_I8 if tables_i8 else 0) | (KBEST_FLAG_REFERENCE_TIES if reference_ties else 0) |
                        (KBEST_FLAG_CANONICAL_TIES if canonical_ties else 0))
-
-        def dp(t):
-            return None if t is None else C.c_void_p(t.data_ptr())
-        self._check(self.lib.kbest_resolve_ties_dev(self.ctx, C.byref(o), B, N, M, dp(d_nRow), dp(d_nCol), dp(d_cost), dp(d_costOff), k,
-                                                    dp(d_row4col), dp(d_col4row), dp(d_gain), dp(d_tie_flags), dp(d_nf),
-                                                    C.c_void_p(stream) if stream else None))
+        self._check(self.lib.kbest_resolve_ties_dev(self.ctx, C.byref(o), B, N, M, _dptr(d_nRow), _dptr(d_nCol), _dptr(d_cost),
+                                                    _dptr(d_costOff), k, _dptr(d_row4col), _dptr(d_col4row), _dptr(d_gain),
+                                                    _dptr(d_tie_flags), _dptr(d_nf), _stream(stream)))
 
     def merge_topk_dev(self, B, n_shard, k, M, d_gain, d_row4col, d_nf, shard_stride_bytes, d_out_gain, d_out_row4col, d_out_nf,
                        maximize=False, stream=None, tables_i8=False):
         """kbest_merge_topk_f64_dev (tables_i8: kbest_merge_topk_i8_f64_dev -- the shards' row4col tables are int8): k-way merge
         of per-shard k-best lists (torch tensors / device pointers)."""
-        def dp(t):
-            return None if t is None else C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
         fn = self.lib.kbest_merge_topk_i8_f64_dev if tables_i8 else self.lib.kbest_merge_topk_f64_dev
-        self._check(fn(self.ctx, B, n_shard, k, M, int(bool(maximize)), dp(d_gain), dp(d_row4col), dp(d_nf), int(shard_stride_bytes),
-                       dp(d_out_gain), dp(d_out_row4col), dp(d_out_nf), C.c_void_p(stream) if stream else None))
+        self._check(fn(self.ctx, B, n_shard, k, M, int(bool(maximize)), _dptr(d_gain), _dptr(d_row4col), _dptr(d_nf),
+                       int(shard_stride_bytes), _dptr(d_out_gain), _dptr(d_out_row4col), _dptr(d_out_nf), _stream(stream)))
 
     def merge_gains_dev(self, B, n_shard, k, M, d_gain, d_nf, own_shard, d_own_row4col8, d_out_gain, d_out_row4col8, d_out_nf, d_tied,
                         maximize=False, stream=None):
         """kbest_merge_gains_f64_dev: the global k-best heap from all shards' gains [S,B,k] / nf [S,B] and this rank's own
         rows (int8 [B,k,M]); d_out_row4col8 (zeroed by the caller) receives the own winners' rows, d_tied (zeroed) the tie word."""
-        def dp(t):
-            return None if t is None else C.c_void_p(t.data_ptr())
-        self._check(self.lib.kbest_merge_gains_f64_dev(self.ctx, B, n_shard, k, M, int(bool(maximize)), dp(d_gain), dp(d_nf), int(own_shard),
-                                                       dp(d_own_row4col8), dp(d_out_gain), dp(d_out_row4col8), dp(d_out_nf), dp(d_tied),
-                                                       C.c_void_p(stream) if stream else None))
+        self._check(self.lib.kbest_merge_gains_f64_dev(self.ctx, B, n_shard, k, M, int(bool(maximize)), _dptr(d_gain), _dptr(d_nf),
+                                                       int(own_shard), _dptr(d_own_row4col8), _dptr(d_out_gain), _dptr(d_out_row4col8),
+                                                       _dptr(d_out_nf), _dptr(d_tied), _stream(stream)))
 
     def reserve_assoc(self, B, maxRawRow, maxCol, k):
         self._check(self.lib.kbest_reserve_assoc(self.ctx, B, maxRawRow, maxCol, k))
@@ -696,11 +646,9 @@ class KBestEngine:
     def assoc_probs_dev(self, B, maxRawRow, maxCol, d_nL, d_nM, d_nRow, d_cost, d_costOff, k, d_probs, d_probOff, d_nf,
                         condition=True, stream=None):
         """Fused association on device buffers (torch CUDA tensors), asynchronous on `stream`: one launch."""
-        def dp(t):
-            return None if t is None else C.c_void_p(t.data_ptr())
-        self._check(self.lib.kbest_assoc_probs_batch_f64_dev(self.ctx, B, maxRawRow, maxCol, dp(d_nL), dp(d_nM), dp(d_nRow),
-                                                             dp(d_cost), dp(d_costOff), k, int(bool(condition)), dp(d_probs),
-                                                             dp(d_probOff), dp(d_nf), C.c_void_p(stream) if stream else None))
+        self._check(self.lib.kbest_assoc_probs_batch_f64_dev(self.ctx, B, maxRawRow, maxCol, _dptr(d_nL), _dptr(d_nM), _dptr(d_nRow),
+                                                             _dptr(d_cost), _dptr(d_costOff), k, int(bool(condition)), _dptr(d_probs),
+                                                             _dptr(d_probOff), _dptr(d_nf), _stream(stream)))
 
     def reserve_permanent(self, B, maxRawRow, maxCol):
         self._check(self.lib.kbest_reserve_permanent(self.ctx, B, maxRawRow, maxCol))
@@ -710,13 +658,11 @@ class KBestEngine:
         """kbest_permanent_probs_batch_f64_dev on torch CUDA tensors, asynchronous on `stream` (a raw hipStream_t integer): one
         launch.  The work space is sized here (a no-op once it is large enough): the C entry never allocates.  reserve=False: the
         caller has called reserve_permanent (timed loops: nothing but the C entry between two events)."""
-        def dp(t):
-            return None if t is None else C.c_void_p(t.data_ptr())
         if reserve:
             self.reserve_permanent(B, maxRawRow, maxCol)
-        self._check(self.lib.kbest_permanent_probs_batch_f64_dev(self.ctx, B, maxRawRow, maxCol, dp(d_nL), dp(d_nM), dp(d_cost),
-                                                                 dp(d_costOff), int(bool(condition)), dp(d_probs), dp(d_probOff),
-                                                                 dp(d_perm), C.c_void_p(stream) if stream else None))
+        self._check(self.lib.kbest_permanent_probs_batch_f64_dev(self.ctx, B, maxRawRow, maxCol, _dptr(d_nL), _dptr(d_nM), _dptr(d_cost),
+                                                                 _dptr(d_costOff), int(bool(condition)), _dptr(d_probs), _dptr(d_probOff),
+                                                                 _dptr(d_perm), _stream(stream)))
 
     def reserve_belief(self, B, maxRawRow, maxCol):
         self._check(self.lib.kbest_reserve_belief(self.ctx, B, maxRawRow, maxCol))
@@ -726,14 +672,12 @@ class KBestEngine:
         """kbest_belief_probs_batch_f64_dev on torch CUDA tensors, asynchronous on `stream` (a raw hipStream_t integer): one
         launch.  The work space is sized here (a no-op once it is large enough): the C entry never allocates.  reserve=False: the
         caller has called reserve_belief (timed loops: nothing but the C entry between two events)."""
-        def dp(t):
-            return None if t is None else C.c_void_p(t.data_ptr())
         if reserve:
             self.reserve_belief(B, maxRawRow, maxCol)
-        self._check(self.lib.kbest_belief_probs_batch_f64_dev(self.ctx, B, maxRawRow, maxCol, dp(d_nL), dp(d_nM), dp(d_cost),
-                                                              dp(d_costOff), int(bool(condition)), float(tol), int(max_iter),
-                                                              dp(d_probs), dp(d_probOff), dp(d_iters), dp(d_resid),
-                                                              C.c_void_p(stream) if stream else None))
+        self._check(self.lib.kbest_belief_probs_batch_f64_dev(self.ctx, B, maxRawRow, maxCol, _dptr(d_nL), _dptr(d_nM), _dptr(d_cost),
+                                                              _dptr(d_costOff), int(bool(condition)), float(tol), int(max_iter),
+                                                              _dptr(d_probs), _dptr(d_probOff), _dptr(d_iters), _dptr(d_resid),
+                                                              _stream(stream)))
 
     def reserve_clustered(self, B, maxRawRow, maxCol):
         self._check(self.lib.kbest_reserve_clustered(self.ctx, B, maxRawRow, maxCol))
@@ -744,14 +688,12 @@ class KBestEngine:
         """kbest_clustered_probs_batch_f64_dev on torch CUDA tensors, asynchronous on `stream` (a raw hipStream_t integer): one
         launch.  The work space is sized here (a no-op once it is large enough): the C entry never allocates.  reserve=False: the
         caller has called reserve_clustered (timed loops: nothing but the C entry between two events)."""
-        def dp(t):
-            return None if t is None else C.c_void_p(t.data_ptr())
         if reserve:
             self.reserve_clustered(B, maxRawRow, maxCol)
-        self._check(self.lib.kbest_clustered_probs_batch_f64_dev(self.ctx, B, maxRawRow, maxCol, dp(d_nL), dp(d_nM), dp(d_cost),
-                                                                 dp(d_costOff), int(bool(condition)), dp(d_probs), dp(d_probOff),
-                                                                 dp(d_logPerm), dp(d_info), dp(d_maxCluster), dp(d_label),
-                                                                 int(labelStride), C.c_void_p(stream) if stream else None))
+        self._check(self.lib.kbest_clustered_probs_batch_f64_dev(self.ctx, B, maxRawRow, maxCol, _dptr(d_nL), _dptr(d_nM), _dptr(d_cost),
+                                                                 _dptr(d_costOff), int(bool(condition)), _dptr(d_probs), _dptr(d_probOff),
+                                                                 _dptr(d_logPerm), _dptr(d_info), _dptr(d_maxCluster), _dptr(d_label),
+                                                                 int(labelStride), _stream(stream)))
 
     def clustered_partial_dev(self, B, maxRawRow, maxCol, d_nL, d_nM, d_cost, d_costOff, d_probs, d_probOff, d_nOpen, d_openDesc,
                               descStride, d_openRows, rowStride, d_sub, max_exact=16, d_logPerm=None, d_info=None,
@@ -760,16 +702,14 @@ class KBestEngine:
         mode -- clusters of more than max_exact measurements stay open (zeros) and come back as sub-problems: d_nOpen int32 [B],
         d_openDesc int32 [B, descStride, 4] (root, m_k, nL_k, R_k), d_openRows int32 [B, rowStride], d_sub doubles shaped like
         d_cost (include/kbest_c.h has the layout)."""
-        def dp(t):
-            return None if t is None else C.c_void_p(t.data_ptr())
         if reserve:
             self.reserve_clustered(B, maxRawRow, maxCol)
-        self._check(self.lib.kbest_clustered_partial_batch_f64_dev(self.ctx, B, maxRawRow, maxCol, dp(d_nL), dp(d_nM), dp(d_cost),
-                                                                   dp(d_costOff), int(bool(condition)), int(max_exact), dp(d_probs),
-                                                                   dp(d_probOff), dp(d_logPerm), dp(d_info), dp(d_maxCluster),
-                                                                   dp(d_label), int(labelStride), dp(d_nOpen), dp(d_openDesc),
-                                                                   int(descStride), dp(d_openRows), int(rowStride), dp(d_sub),
-                                                                   C.c_void_p(stream) if stream else None))
+        self._check(self.lib.kbest_clustered_partial_batch_f64_dev(self.ctx, B, maxRawRow, maxCol, _dptr(d_nL), _dptr(d_nM), _dptr(d_cost),
+                                                                   _dptr(d_costOff), int(bool(condition)), int(max_exact), _dptr(d_probs),
+                                                                   _dptr(d_probOff), _dptr(d_logPerm), _dptr(d_info), _dptr(d_maxCluster),
+                                                                   _dptr(d_label), int(labelStride), _dptr(d_nOpen), _dptr(d_openDesc),
+                                                                   int(descStride), _dptr(d_openRows), int(rowStride), _dptr(d_sub),
+                                                                   _stream(stream)))
 
 
 class KBestMulti:
