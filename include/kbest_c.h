@@ -29,6 +29,7 @@
  *   kbest_clustered_probs_batch_f64 / kbest_clustered_probs_batch_f64_dev
  *   kbest_hybrid_probs_batch_f64 / kbest_clustered_partial_batch_f64_dev
  *   kbest_hybrid_exact_probs_batch_f64 / kbest_bigcluster_probs_f64_dev
+ *   kbest_hybrid_frontier_probs_batch_f64 / kbest_frontier_probs_f64_dev
  *        the exact association probabilities by gated clusters, for frames of up to 128 measurements (not in the reference)
  *
  * Conventions kept from the reference: cost matrices are column-major
@@ -567,6 +568,54 @@ int kbest_hybrid_exact_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL,
                                        const int64_t *costOff, int condition, int k, int maxExact, int maxBig, double *probs,
                                        const int64_t *probOff, double *logPerm, int32_t *method, int32_t *nOpen, int32_t *nBig,
                                        int32_t *maxCluster);
+/*
+ * Exact association probabilities of sparse clusters of up to 64 measurements (kbest_frontier.hip; not in the reference): a fourth
+ * tier of the exact subset sums whose limit is a cluster's structure, not its column count.
+ *
+ * The clusters the gate opens are chains of overlapping neighbourhoods.  With the rows taken in a good order a column is a state
+ * bit only between its first and its last non-zero row: before, it is unused; after, it must be used.  The order is greedy and a
+ * pure function of the pattern: of the unprocessed rows the one that leaves the fewest columns open, then the one that opens the
+ * fewest, then the lowest (DESIGN.md section 14 has the two counts).  W is the largest number of columns open during a step; the
+ * sweep keeps sum_i 2^|open after i rows| doubles of forward layers and two buffers of 2^W.  Scaling as the big-cluster tier's:
+ * a'[r][c] = exp(colMin_c - x[r][c]), log Z_k = log Z'_k - sum_c colMin_c.
+ *
+ * kbest_frontier_probs_f64_dev: n clusters, arguments as kbest_bigcluster_probs_f64_dev with m[k] in 1 .. KBEST_FRONTIER_MAX_COLS
+ * and nLk[k] in 0 .. 1024, plus d_width[k] (may be NULL): the cluster's W, written for every cluster.  d_info[k]: 1 answered;
+ * 0: Z_k = 0 (zeros, log Z_k = -inf) -- fewer counting rows than columns, or two columns whose only row is the same row;
+ * -4: W > KBEST_FRONTIER_MAX_WIDTH;  -3: its layers exceed the slot (KBEST_FRONTIER_SLOT bytes).  A refused cluster's probabilities
+ * and log Z_k are untouched, and both refusals follow from the cluster alone -- never from the device, the batch or the cap.
+ * One workgroup takes a cluster at a time and the grid strides over the clusters: ONE launch per KB_FRONTIER_PACK = 128 clusters (the
+ * descriptors travel as a kernel argument), no workgroup waits for another, no floating-point atomics: a cluster gives the same bits
+ * alone, anywhere in a batch and under any work cap.  Asynchronous on `stream` (NULL: the context's), allocates nothing: needs
+ * kbest_reserve_frontier(ctx, n, maxM, maxRows) first -- a slot and a plan of maxRows (the largest nLk + m) steps for each of the
+ * clusters in flight, at most KBEST_FRONTIER_WORK_CAP bytes of slots -- else KBEST_ERR_NOT_RESERVED.  m outside 1 .. 64:
+ * KBEST_ERR_BAD_ARG.
+ *
+ * kbest_hybrid_frontier_probs_batch_f64 (host buffers, synchronous): kbest_hybrid_exact_probs_batch_f64 with this tier first among
+ * the open clusters.  The partial kernel runs as there; every open cluster of at most 64 measurements goes through the tier from
+ * the sub-block that already lies on the device; what it refuses (-3, -4, or W > maxWidth, 0 .. 16) goes to the big-cluster tier
+ * when it has at most maxBig measurements, the rest to the k-best path when k >= 1; with k = 0 a frame that has one is refused.
+ *   method[b], nOpen[b], nBig[b], maxCluster[b], logPerm[b]: as kbest_hybrid_exact_probs_batch_f64 (method 0: every cluster exact by
+ *       any tier; logPerm sums log Z_k over all exactly answered clusters);  nFrontier[b] (may be NULL): the clusters this tier answered.
+ * With maxWidth = 0 every common output carries the bits of kbest_hybrid_exact_probs_batch_f64.  maxWidth outside 0 .. 16 or an
+ * argument kbest_hybrid_exact_probs_batch_f64 refuses: KBEST_ERR_BAD_ARG.
+ */
+#define KBEST_FRONTIER_MAX_COLS 64
+#define KBEST_FRONTIER_MAX_WIDTH 16
+#define KBEST_FRONTIER_SLOT ((size_t)4 << 20)       /* the layers of one cluster */
+#define KBEST_FRONTIER_WORK_CAP ((size_t)1 << 30)   /* the slots of the clusters in flight */
+int kbest_reserve_frontier(kbest_ctx *ctx, int n, int maxM, int maxRows);
+/* For tests: the slots in flight at the most / the layers of one cluster at the most (0: the default again).  The results do not
+ * depend on the first, bit for bit; a cluster whose layers exceed the second is not answered (-3). */
+int kbest_set_frontier_work_cap(kbest_ctx *ctx, size_t bytes);
+int kbest_set_frontier_slot(kbest_ctx *ctx, size_t bytes);
+int kbest_frontier_probs_f64_dev(kbest_ctx *ctx, int n, const int32_t *m, const int32_t *nLk, const int64_t *subOff,
+                                 const int64_t *probOff, const double *d_sub, double *d_probs, double *d_logZ, int32_t *d_info,
+                                 int32_t *d_width, void *stream);
+int kbest_hybrid_frontier_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,
+                                          const int64_t *costOff, int condition, int k, int maxExact, int maxBig, int maxWidth,
+                                          double *probs, const int64_t *probOff, double *logPerm, int32_t *method, int32_t *nOpen,
+                                          int32_t *nBig, int32_t *maxCluster, int32_t *nFrontier);
 /* on = 1: the HOST-buffer association entries of this context (kbest_weights / assoc_probs / bruteforce / quadric_assoc) enumerate
  * their k best in the REFERENCE's own order of operations (the reference-order kernel, as KBEST_FLAG_REFERENCE_ORDER does for
  * kbest_batch_f64): where exactly equal gains straddle slot k the assignments that are weighed are the ones the reference's

@@ -143,6 +143,12 @@ std::vector<std::vector<double>> hybridProb(const std::vector<double> &costMatri
 // infeasible frame comes back as all zeros.
 std::vector<std::vector<double>> hybridExactProb(const std::vector<double> &costMatrix, size_t nL, size_t nM, size_t k);
 
+// Not in the reference: hybridExactProb with the frontier tier first (kbest_hybrid_frontier_probs_batch_f64): exact on every cluster
+// of at most 64 measurements whose rows, in the greedy order, keep at most 16 columns open, and on every other of at most 20;
+// assignmentProb(k) on what is left; k = 0: a frame with such a cluster is refused.  Throws std::runtime_error only when the frame
+// is refused (method -1); an infeasible frame comes back as all zeros.
+std::vector<std::vector<double>> hybridFrontierProb(const std::vector<double> &costMatrix, size_t nL, size_t nM, size_t k);
+
 // Not in the reference: the engine context behind the functions above (created on first use, GPU 0), for the entries of
 // kbest_c.h that take one -- e.g. kbest_last_tie_flags after a call.
 struct kbest_ctx;

@@ -152,6 +152,10 @@ struct kbest_ctx {
     DevBufRaw bigLayers;      // the big-cluster tier (kbest_bigcluster.hip): the layers of the clusters in flight
     DevBufRaw bigSmall;       // ... and their small arrays: a', row lists, per-workgroup partial sums
     size_t bigWorkCap = KBEST_BIGCLUSTER_WORK_CAP;  // ... the layers in flight at the most (kbest_set_bigcluster_work_cap)
+    DevBufRaw frLayers;       // the frontier tier (kbest_frontier.hip): one slot of layers per workgroup of a launch
+    DevBufRaw frPlan;         // ... and one plan (KB_FRONTIER_STEP_DOUBLES per row) per workgroup
+    size_t frSlot = KBEST_FRONTIER_SLOT;          // ... the layers of one cluster at the most (kbest_set_frontier_slot)
+    size_t frWorkCap = KBEST_FRONTIER_WORK_CAP;   // ... the slots in flight at the most (kbest_set_frontier_work_cap)
     DevBufRaw relayBuf;       // relay launches of the 64-row kernel: [B] LDS images (kbest_engine.hip)
     DevBufRaw relayFlags;     // ... and three words per matrix: claimed / done / gone (zeroed when the buffer is made, put back to zero by every launch)
     long long relayLaunches = 0;  // relay launches made (kbest_relay_launches)
@@ -614,6 +618,8 @@ int kbest_destroy(kbest_ctx *ctx)
     if (ctx->clusBuf.p) (void)hipFree(ctx->clusBuf.p);
     if (ctx->bigLayers.p) (void)hipFree(ctx->bigLayers.p);
     if (ctx->bigSmall.p) (void)hipFree(ctx->bigSmall.p);
+    if (ctx->frLayers.p) (void)hipFree(ctx->frLayers.p);
+    if (ctx->frPlan.p) (void)hipFree(ctx->frPlan.p);
     if (ctx->relayFlags.p) (void)hipFree(ctx->relayFlags.p);
     if (ctx->lastEvent) (void)hipEventDestroy(ctx->lastEvent);
     for (auto &a : ctx->aux)
@@ -3609,14 +3615,101 @@ int kbest_bigcluster_probs_f64_dev(kbest_ctx *ctx, int n, const int32_t *m, cons
     return KBEST_OK;
 }
 
+
+// ---- the frontier tier (kbest_frontier.hip): one workgroup per open cluster, a slot of layers and a plan each --------------------
+// frames_in_flight: the kernel's 151 VGPRs give 3 waves per SIMD, 12 per CU; the slots stay under ctx->frWorkCap
+static const int FRONTIER_WAVES_PER_CU = 12;
+static const int FRONTIER_LDS = 16384;
+
+int kbest_set_frontier_work_cap(kbest_ctx *ctx, size_t bytes)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    ctx->frWorkCap = bytes ? bytes : KBEST_FRONTIER_WORK_CAP;
+    return KBEST_OK;
+}
+
+int kbest_set_frontier_slot(kbest_ctx *ctx, size_t bytes)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    ctx->frSlot = bytes ? (bytes < 8 ? 8 : bytes / 8 * 8) : KBEST_FRONTIER_SLOT;
+    return KBEST_OK;
+}
+
+int kbest_reserve_frontier(kbest_ctx *ctx, int n, int maxM, int maxRows)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    if (n < 0 || maxM < 1 || maxM > KBEST_FRONTIER_MAX_COLS || maxRows < maxM || maxRows > KBEST_MAX_DIM_WIDE + KBEST_FRONTIER_MAX_COLS)
+        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_reserve_frontier: bad argument (n >= 0, maxM 1 .. 64, maxM <= maxRows <= 1088)");
+    if (n == 0) return KBEST_OK;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int g = frames_in_flight(ctx, FRONTIER_WAVES_PER_CU, kb::KB_FRONTIER_THREADS, FRONTIER_LDS, (long long)(ctx->frSlot / 8), n,
+                                   ctx->frWorkCap);
+    int rc = raw_reserve(ctx, ctx->frLayers, ctx->frSlot * (size_t)g);
+    if (rc != KBEST_OK) return rc;
+    return raw_reserve(ctx, ctx->frPlan, (size_t)g * (size_t)maxRows * kb::KB_FRONTIER_STEP_DOUBLES * 8);
+}
+
+int kbest_frontier_probs_f64_dev(kbest_ctx *ctx, int n, const int32_t *m, const int32_t *nLk, const int64_t *subOff,
+                                 const int64_t *probOff, const double *d_sub, double *d_probs, double *d_logZ, int32_t *d_info,
+                                 int32_t *d_width, void *stream)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    if (n < 0 || (n > 0 && (!m || !nLk || !subOff || !probOff || !d_sub || !d_probs)))
+        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_frontier_probs_f64_dev: bad argument");
+    if (n == 0) return KBEST_OK;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    int maxRows = 1;
+    for (int k = 0; k < n; k++) {  // everything is checked before anything is launched
+        if (m[k] < 1 || m[k] > KBEST_FRONTIER_MAX_COLS || nLk[k] < 0 || nLk[k] > KBEST_MAX_DIM_WIDE || subOff[k] < 0 || probOff[k] < 0)
+            return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_frontier_probs_f64_dev: a cluster with m outside 1 .. 64, nLk outside 0 .. 1024 or a negative offset");
+        if (nLk[k] + m[k] > maxRows) maxRows = nLk[k] + m[k];
+    }
+    // workgroups: as the chip holds, as have a slot under the cap -- and a slot and a plan in what was reserved
+    kb::FrontierWork w;
+    w.slotDoubles = (long long)(ctx->frSlot / 8);
+    w.planDoubles = (long long)maxRows * kb::KB_FRONTIER_STEP_DOUBLES;
+    long long g = frames_in_flight(ctx, FRONTIER_WAVES_PER_CU, kb::KB_FRONTIER_THREADS, FRONTIER_LDS, w.slotDoubles, n, ctx->frWorkCap);
+    const long long slots = (long long)(ctx->frLayers.bytes / ctx->frSlot), plans = (long long)(ctx->frPlan.bytes / ((size_t)w.planDoubles * 8));
+    if (g > slots) g = slots;
+    if (g > plans) g = plans;
+    if (g < 1) return fail(ctx, KBEST_ERR_NOT_RESERVED, "kbest_frontier_probs_f64_dev: call kbest_reserve_frontier first");
+    w.layers = static_cast<double *>(ctx->frLayers.p);
+    w.plan = static_cast<double *>(ctx->frPlan.p);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    int rc = order_behind_last(ctx, s);  // (one work space per context)
+    if (rc != KBEST_OK) return rc;
+    const Launched mark{ctx, s};
+    kb::FrontierPack pk;
+    for (int at = 0; at < n; at += kb::KB_FRONTIER_PACK) {  // (launches of one stream: the next pack takes the slots over)
+        pk.n = n - at < kb::KB_FRONTIER_PACK ? n - at : kb::KB_FRONTIER_PACK;
+        pk.base = at;
+        for (int j = 0; j < pk.n; j++) {
+            pk.c[j].subOff = subOff[at + j];
+            pk.c[j].probOff = probOff[at + j];
+            pk.c[j].m = m[at + j];
+            pk.c[j].nL = nLk[at + j];
+        }
+        const hipError_t e = kb::launch_frontier_pack(pk, d_sub, d_probs, d_logZ, d_info, d_width, w, (int)g, s);
+        if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "frontier kernel launch", e);
+    }
+    return KBEST_OK;
+}
+
 // hybridProb: the partial clustered kernel on the whole batch, then the open clusters of all frames as ONE batch through the
 // assignmentProb path (weights_entry, condition = false: kBest2DCutoff(k, 42) -> weights), scattered back on the host.
 // maxBig > 0 (kbest_hybrid_exact_probs_batch_f64): the open clusters of at most maxBig columns whose layers fit the work cap go
 // through the big-cluster tier first, from the sub-blocks that already lie on the device; k = 0: whatever else is open refuses
 // its frame.  maxBig = 0, k >= 1: kbest_hybrid_probs_batch_f64, step for step.
+// maxWidth > 0 (kbest_hybrid_frontier_probs_batch_f64): before that, every open cluster of at most 64 columns goes through the
+// frontier tier, again from the sub-blocks on the device; what it refuses (-3, -4, or a width beyond maxWidth) goes on as above.
 static int hybrid_impl(kbest_ctx *ctx, const char *who, int B, const int32_t *nL, const int32_t *nM, const double *cost,
-                       const int64_t *costOff, int condition, int k, int maxExact, int maxBig, double *probs, const int64_t *probOff,
-                       double *logPerm, int32_t *method, int32_t *nOpen, int32_t *nBig, int32_t *maxCluster)
+                       const int64_t *costOff, int condition, int k, int maxExact, int maxBig, int maxWidth, double *probs,
+                       const int64_t *probOff, double *logPerm, int32_t *method, int32_t *nOpen, int32_t *nBig, int32_t *nFrontier,
+                       int32_t *maxCluster)
 {
     FrameBatch fb;
     int rc = fb.scan(ctx, who, B, nL, nM, costOff, probOff);
@@ -3630,13 +3723,17 @@ static int hybrid_impl(kbest_ctx *ctx, const char *who, int B, const int32_t *nL
     if (rc != KBEST_OK) return rc;
     std::vector<double> hp, hLp;
     std::vector<int32_t> hInt((size_t)B * 3), hDesc, hRows, hLabel;  // info | maxCluster | nOpen
-    struct Open { int b, root, m, cL; size_t rowAt; int big, at; };  // at: its place among the big / the enumerated clusters
+    // tier: 0 enumerated, 1 big-cluster, 2 frontier; at: its place among the clusters of its tier; from: its sub-block in the frame's
+    struct Open { int b, root, m, cL; size_t rowAt, from; int tier, at; };
     std::vector<Open> open;
     std::vector<double> sub;      // the enumerated clusters' sub-blocks, packed
     std::vector<int64_t> sCo, sPo;
     std::vector<double> bigP, bigLogZ;  // the big clusters' [m][nL_k + 1] probabilities, packed, and their log Z_k
     std::vector<int32_t> bigInfo;
     std::vector<int64_t> bPo;
+    std::vector<double> frP, frLogZ;    // the same of the frontier tier
+    std::vector<int32_t> frInfo;
+    std::vector<int64_t> fPo;
     const size_t descStride = (size_t)maxCol, rowStride = (size_t)maxRawRow;
     {
         DevBuf dOut, dLabel, dDesc, dRows, dSub, dLp;  // out: info[B] | maxCluster[B] | nOpen[B] (int32)
@@ -3667,65 +3764,116 @@ static int hybrid_impl(kbest_ctx *ctx, const char *who, int B, const int32_t *nL
             HIP_TRY(ctx, hipMemcpy(hDesc.data(), dDesc.p, hDesc.size() * 4, hipMemcpyDeviceToHost));
             HIP_TRY(ctx, hipMemcpy(hRows.data(), dRows.p, hRows.size() * 4, hipMemcpyDeviceToHost));
             HIP_TRY(ctx, hipMemcpy(hLabel.data(), dLabel.p, hLabel.size() * 4, hipMemcpyDeviceToHost));
-            auto is_big = [&](const int32_t *d) {
-                return maxBig > 0 && d[1] <= maxBig && big_layers_bytes(d[1], d[2] + d[1]) <= ctx->bigWorkCap;
-            };
-            size_t total = 0;
-            for (int b = 0; b < B; b++)
+            for (int b = 0; b < B; b++) {  // every open cluster, in frame and label order
+                size_t n = 0, rowAt = (size_t)b * rowStride;
                 for (int j = 0; j < hOpen[b]; j++) {
                     const int32_t *d = hDesc.data() + ((size_t)b * descStride + j) * 4;
-                    if (!is_big(d)) total += (size_t)(d[2] + d[1]) * d[1];
+                    open.push_back(Open{b, d[0], d[1], d[2], rowAt, n, 0, -1});
+                    n += (size_t)(d[2] + d[1]) * d[1];
+                    rowAt += (size_t)d[2];
                 }
+            }
+            if (maxWidth > 0) {  // the frontier tier first: the open clusters of all frames in one call
+                std::vector<int32_t> fM, fL;
+                std::vector<int64_t> fSo;
+                std::vector<size_t> fWho;
+                size_t fpat = 0;
+                int frM = 1, frRows = 1;
+                for (size_t i = 0; i < open.size(); i++) {
+                    const Open &o = open[i];
+                    if (o.m > KBEST_FRONTIER_MAX_COLS) continue;
+                    fWho.push_back(i);
+                    fM.push_back(o.m);
+                    fL.push_back(o.cL);
+                    fSo.push_back(costOff[o.b] + (int64_t)o.from);
+                    fPo.push_back((int64_t)fpat);
+                    fpat += (size_t)o.m * ((size_t)o.cL + 1);
+                    if (o.m > frM) frM = o.m;
+                    if (o.cL + o.m > frRows) frRows = o.cL + o.m;
+                }
+                if (!fM.empty()) {
+                    const int nf = (int)fM.size();
+                    rc = kbest_reserve_frontier(ctx, nf, frM, frRows);
+                    if (rc != KBEST_OK) return rc;
+                    DevBuf dFrP, dFrOut;  // out: logZ[nf] (double) | info[nf] | width[nf] (int32)
+                    hipError_t e;
+                    if ((e = dFrP.alloc(ctx, fpat * 8)) != hipSuccess || (e = dFrOut.alloc(ctx, (size_t)nf * 16)) != hipSuccess)
+                        return fail(ctx, KBEST_ERR_NOMEM, (std::string(who) + ": device buffers").c_str(), e);
+                    unsigned char *f8 = dFrOut.as<unsigned char>();
+                    int32_t *f4 = reinterpret_cast<int32_t *>(f8 + (size_t)nf * 8);
+                    rc = kbest_frontier_probs_f64_dev(ctx, nf, fM.data(), fL.data(), fSo.data(), fPo.data(), dSub.as<double>(),
+                                                      dFrP.as<double>(), reinterpret_cast<double *>(f8), f4, f4 + nf, nullptr);
+                    if (rc != KBEST_OK) return rc;
+                    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+                    std::vector<int32_t> frWidth(nf);
+                    frP.resize(fpat);
+                    frLogZ.resize(nf);
+                    frInfo.resize(nf);
+                    HIP_TRY(ctx, hipMemcpy(frP.data(), dFrP.p, fpat * 8, hipMemcpyDeviceToHost));
+                    HIP_TRY(ctx, hipMemcpy(frLogZ.data(), f8, (size_t)nf * 8, hipMemcpyDeviceToHost));
+                    HIP_TRY(ctx, hipMemcpy(frInfo.data(), f4, (size_t)nf * 4, hipMemcpyDeviceToHost));
+                    HIP_TRY(ctx, hipMemcpy(frWidth.data(), f4 + nf, (size_t)nf * 4, hipMemcpyDeviceToHost));
+                    for (int t = 0; t < nf; t++)
+                        if (frInfo[t] >= 0 && frWidth[t] <= maxWidth) {
+                            open[fWho[t]].tier = 2;
+                            open[fWho[t]].at = t;
+                        }
+                }
+            }
+            size_t total = 0;
+            for (Open &o : open) {
+                if (o.tier != 0) continue;
+                if (maxBig > 0 && o.m <= maxBig && big_layers_bytes(o.m, o.cL + o.m) <= ctx->bigWorkCap) o.tier = 1;
+                else total += (size_t)(o.cL + o.m) * o.m;
+            }
             sub.resize(total);
             std::vector<int32_t> bM, bL;
             std::vector<int64_t> bSo;
             size_t at = 0, pat = 0, bpat = 0, bigLayers = 0;
             int bigM = 1, bigRows = 1;
-            for (int b = 0; b < B; b++) {
-                if (hOpen[b] <= 0) continue;
-                size_t n = 0, nKeep = 0, rowAt = (size_t)b * rowStride;
-                bool bigHere = false;
-                for (int j = 0; j < hOpen[b]; j++) {
-                    const int32_t *d = hDesc.data() + ((size_t)b * descStride + j) * 4;
-                    const size_t sz = (size_t)(d[2] + d[1]) * d[1];
-                    if (is_big(d)) {
-                        open.push_back(Open{b, d[0], d[1], d[2], rowAt, 1, (int)bM.size()});
-                        bM.push_back(d[1]);
-                        bL.push_back(d[2]);
-                        bSo.push_back(costOff[b] + (int64_t)n);
+            for (size_t i = 0; i < open.size();) {  // frame by frame
+                size_t e = i;
+                while (e < open.size() && open[e].b == open[i].b) e++;
+                const int b = open[i].b;
+                size_t n = 0, nKeep = 0;
+                bool onlyEnumerated = true;
+                for (size_t t = i; t < e; t++) {
+                    Open &o = open[t];
+                    const size_t sz = (size_t)(o.cL + o.m) * o.m;
+                    n += sz;
+                    if (o.tier == 1) {
+                        o.at = (int)bM.size();
+                        bM.push_back(o.m);
+                        bL.push_back(o.cL);
+                        bSo.push_back(costOff[b] + (int64_t)o.from);
                         bPo.push_back((int64_t)bpat);
-                        bpat += (size_t)d[1] * ((size_t)d[2] + 1);
-                        bigLayers += big_layers_bytes(d[1], d[2] + d[1]);
-                        if (d[1] > bigM) bigM = d[1];
-                        if (d[2] + d[1] > bigRows) bigRows = d[2] + d[1];
-                        bigHere = true;
-                    } else {
-                        open.push_back(Open{b, d[0], d[1], d[2], rowAt, 0, (int)sCo.size()});
+                        bpat += (size_t)o.m * ((size_t)o.cL + 1);
+                        bigLayers += big_layers_bytes(o.m, o.cL + o.m);
+                        if (o.m > bigM) bigM = o.m;
+                        if (o.cL + o.m > bigRows) bigRows = o.cL + o.m;
+                    } else if (o.tier == 0) {
+                        o.at = (int)sCo.size();
                         sCo.push_back((int64_t)(at + nKeep));
                         sPo.push_back((int64_t)pat);
-                        pat += (size_t)d[1] * ((size_t)d[2] + 1);
+                        pat += (size_t)o.m * ((size_t)o.cL + 1);
                         nKeep += sz;
                     }
-                    n += sz;
-                    rowAt += (size_t)d[2];
+                    onlyEnumerated = onlyEnumerated && o.tier == 0;
                 }
                 if (k >= 1 && nKeep > 0) {
-                    if (!bigHere) {
+                    if (onlyEnumerated) {
                         HIP_TRY(ctx, hipMemcpy(sub.data() + at, dSub.as<double>() + costOff[b], n * 8, hipMemcpyDeviceToHost));
-                    } else {  // the enumerated clusters of a frame that has big ones too: one by one
-                        size_t from = 0, to = at;
-                        for (int j = 0; j < hOpen[b]; j++) {
-                            const int32_t *d = hDesc.data() + ((size_t)b * descStride + j) * 4;
-                            const size_t sz = (size_t)(d[2] + d[1]) * d[1];
-                            if (!is_big(d)) {
-                                HIP_TRY(ctx, hipMemcpy(sub.data() + to, dSub.as<double>() + costOff[b] + from, sz * 8, hipMemcpyDeviceToHost));
-                                to += sz;
-                            }
-                            from += sz;
+                    } else {  // the enumerated clusters of a frame that has exactly answered ones too: one by one
+                        for (size_t t = i; t < e; t++) {
+                            const Open &o = open[t];
+                            if (o.tier != 0) continue;
+                            HIP_TRY(ctx, hipMemcpy(sub.data() + sCo[o.at], dSub.as<double>() + costOff[b] + o.from,
+                                                   (size_t)(o.cL + o.m) * o.m * 8, hipMemcpyDeviceToHost));
                         }
                     }
                 }
                 at += nKeep;
+                i = e;
             }
             if (!bM.empty()) {  // the big clusters of all frames: from the sub-blocks where they lie
                 const int nb = (int)bM.size();
@@ -3755,12 +3903,14 @@ static int hybrid_impl(kbest_ctx *ctx, const char *who, int B, const int32_t *nL
     for (int b = 0; b < B; b++) method[b] = hInfo[b] < 0 ? -1 : hInfo[b] == 0 ? -2 : 0;
     if (nBig)
         for (int b = 0; b < B; b++) nBig[b] = 0;
+    if (nFrontier)
+        for (int b = 0; b < B; b++) nFrontier[b] = 0;
     if (!open.empty()) {
         const int S = (int)sCo.size();
         std::vector<int32_t> sL(S), sM(S), sNf(S, 0);
         size_t pn = 0;
         for (const Open &o : open)
-            if (!o.big) {
+            if (o.tier == 0) {
                 sL[o.at] = o.cL;
                 sM[o.at] = o.m;
                 pn += (size_t)o.m * ((size_t)o.cL + 1);
@@ -3774,7 +3924,11 @@ static int hybrid_impl(kbest_ctx *ctx, const char *who, int B, const int32_t *nL
         for (const Open &o : open) {  // slot nL_k -> slot nL, landmark rows through the row list, columns through the labels
             const int b = o.b;
             const double *q;
-            if (o.big) {
+            if (o.tier == 2) {
+                if (frInfo[o.at] <= 0) method[b] = -2;
+                else if (nFrontier) nFrontier[b]++;
+                q = frP.data() + fPo[o.at];
+            } else if (o.tier == 1) {
                 if (bigInfo[o.at] <= 0) method[b] = -2;
                 else if (nBig) nBig[b]++;
                 q = bigP.data() + bPo[o.at];
@@ -3802,6 +3956,7 @@ static int hybrid_impl(kbest_ctx *ctx, const char *who, int B, const int32_t *nL
             if ((method[b] == -2 || method[b] == -1) && hOpen[b] > 0) {  // an open cluster without a feasible assignment (or without
                 std::fill(hp.begin() + probOff[b], hp.begin() + probOff[b] + (size_t)nM[b] * ((size_t)nL[b] + 1), 0.0);  // an answer):
                 if (nBig) nBig[b] = 0;                                                                              // the whole frame is zeros
+                if (nFrontier) nFrontier[b] = 0;
             }
         }
     }
@@ -3810,7 +3965,7 @@ static int hybrid_impl(kbest_ctx *ctx, const char *who, int B, const int32_t *nL
         // units a = exp(-x): m_k times the frame's block minimum (0 after conditionCosts) brings them to the frame's a = exp(min - x)
         for (int b = 0; b < B; b++) logPerm[b] = hLp[b];
         for (const Open &o : open) {
-            if (!o.big || method[o.b] < 0) continue;
+            if (o.tier == 0 || method[o.b] < 0) continue;
             double mn = 0.0;
             if (!condition) {
                 const double *x = cost + costOff[o.b];
@@ -3818,7 +3973,7 @@ static int hybrid_impl(kbest_ctx *ctx, const char *who, int B, const int32_t *nL
                 mn = x[0];
                 for (size_t i = 1; i < cnt; i++) mn = x[i] < mn ? x[i] : mn;
             }
-            logPerm[o.b] = logPerm[o.b] + (bigLogZ[o.at] + (double)o.m * mn);
+            logPerm[o.b] = logPerm[o.b] + ((o.tier == 2 ? frLogZ[o.at] : bigLogZ[o.at]) + (double)o.m * mn);
         }
         for (int b = 0; b < B; b++) {
             if (method[b] == -2) logPerm[b] = -std::numeric_limits<double>::infinity();
@@ -3840,8 +3995,8 @@ int kbest_hybrid_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const
         (B > 0 && (!nL || !nM || !cost || !costOff || !probs || !probOff || !method)))
         return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_hybrid_probs_batch_f64: bad argument (k >= 1, maxExact 0 .. 16)");
     if (B == 0) return KBEST_OK;
-    return hybrid_impl(ctx, "kbest_hybrid_probs_batch_f64", B, nL, nM, cost, costOff, condition, k, maxExact, 0, probs, probOff, nullptr,
-                       method, nOpen, nullptr, maxCluster);
+    return hybrid_impl(ctx, "kbest_hybrid_probs_batch_f64", B, nL, nM, cost, costOff, condition, k, maxExact, 0, 0, probs, probOff, nullptr,
+                       method, nOpen, nullptr, nullptr, maxCluster);
 }
 
 int kbest_hybrid_exact_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,
@@ -3854,8 +4009,23 @@ int kbest_hybrid_exact_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL,
         (B > 0 && (!nL || !nM || !cost || !costOff || !probs || !probOff || !method)))
         return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_hybrid_exact_probs_batch_f64: bad argument (k >= 0, maxExact 0 .. 16, maxBig 0 .. 20)");
     if (B == 0) return KBEST_OK;
-    return hybrid_impl(ctx, "kbest_hybrid_exact_probs_batch_f64", B, nL, nM, cost, costOff, condition, k, maxExact, maxBig, probs, probOff,
-                       logPerm, method, nOpen, nBig, maxCluster);
+    return hybrid_impl(ctx, "kbest_hybrid_exact_probs_batch_f64", B, nL, nM, cost, costOff, condition, k, maxExact, maxBig, 0, probs, probOff,
+                       logPerm, method, nOpen, nBig, nullptr, maxCluster);
+}
+
+int kbest_hybrid_frontier_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,
+                                          const int64_t *costOff, int condition, int k, int maxExact, int maxBig, int maxWidth,
+                                          double *probs, const int64_t *probOff, double *logPerm, int32_t *method, int32_t *nOpen,
+                                          int32_t *nBig, int32_t *maxCluster, int32_t *nFrontier)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    if (B < 0 || k < 0 || maxExact < 0 || maxExact > KBEST_CLUSTER_MAX_SIZE || maxBig < 0 || maxBig > KBEST_BIGCLUSTER_MAX_SIZE ||
+        maxWidth < 0 || maxWidth > KBEST_FRONTIER_MAX_WIDTH || (B > 0 && (!nL || !nM || !cost || !costOff || !probs || !probOff || !method)))
+        return fail(ctx, KBEST_ERR_BAD_ARG,
+                    "kbest_hybrid_frontier_probs_batch_f64: bad argument (k >= 0, maxExact 0 .. 16, maxBig 0 .. 20, maxWidth 0 .. 16)");
+    if (B == 0) return KBEST_OK;
+    return hybrid_impl(ctx, "kbest_hybrid_frontier_probs_batch_f64", B, nL, nM, cost, costOff, condition, k, maxExact, maxBig, maxWidth,
+                       probs, probOff, logPerm, method, nOpen, nBig, nFrontier, maxCluster);
 }
 
 int kbest_bruteforce_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,

@@ -646,6 +646,30 @@ hipError_t launch_bigcluster_pack(const BigClusterPack &p, const double *sub, do
                                   double *small, hipStream_t stream);
 hipError_t launch_bigcluster_flag(int *info, int idx, int value, hipStream_t stream);
 
+// kbest_frontier.hip: an open cluster of up to 64 measurements by a frontier sweep, one workgroup per cluster (kbest_c.h, "Exact
+// association probabilities of sparse clusters").  The descriptors travel as a kernel argument: nothing is staged or allocated.
+constexpr int KB_FRONTIER_PACK = 128;          // clusters of one launch
+constexpr int KB_FRONTIER_MAX_COLS = 64;       // KBEST_FRONTIER_MAX_COLS
+constexpr int KB_FRONTIER_MAX_WIDTH = 16;      // KBEST_FRONTIER_MAX_WIDTH
+constexpr int KB_FRONTIER_MAX_ROWS = 1024 + 64;  // nL_k + m_k
+constexpr int KB_FRONTIER_THREADS = 256;
+constexpr int KB_FRONTIER_STEP_DOUBLES = 10;   // one step of the plan (FrontierStep, 80 bytes)
+struct FrontierDesc {
+    long long subOff, probOff;  // the cluster's sub-block / its [m][nL + 1] probabilities, in doubles from the caller's buffers
+    int m, nL;                  // columns, landmark rows
+};
+struct FrontierPack {
+    FrontierDesc c[KB_FRONTIER_PACK];
+    int n, base;                // clusters; the place of the first one in logZ / info / width
+};
+struct FrontierWork {
+    double *layers;             // slotDoubles per workgroup: the forward layers, then two buffers of 2^W for the backward sweep
+    double *plan;               // planDoubles per workgroup: KB_FRONTIER_STEP_DOUBLES per row of the largest cluster
+    long long slotDoubles, planDoubles;
+};
+hipError_t launch_frontier_pack(const FrontierPack &p, const double *sub, double *probs, double *logZ, int *info, int *width,
+                                const FrontierWork &w, int grid, hipStream_t stream);
+
 }  // namespace kb
 
 // kbest_capi.cpp: completes the gain levels that straddle slot k in the caller's HOST tables (see there)

@@ -307,4 +307,19 @@ std::vector<std::vector<double>> hybridExactProb(const std::vector<double> &cost
     return rows_of(flat, nL, nM, nL + 1);
 }
 
+std::vector<std::vector<double>> hybridFrontierProb(const std::vector<double> &costMatrix, size_t nL, size_t nM, size_t k)
+{
+    kbest_ctx *ctx = global_ctx();
+    const int32_t l = (int32_t)nL, m = (int32_t)nM;
+    const int64_t zero = 0;
+    int32_t method = 0, maxCluster = 0;
+    std::vector<double> flat(nM * (nL + 1), 0.0);
+    check(ctx, kbest_hybrid_frontier_probs_batch_f64(ctx, 1, &l, &m, costMatrix.data(), &zero, 0, (int)k, 0, KBEST_BIGCLUSTER_MAX_SIZE,
+                                                     KBEST_FRONTIER_MAX_WIDTH, flat.data(), &zero, nullptr, &method, nullptr, nullptr,
+                                                     &maxCluster, nullptr));
+    if (method == -1)
+        throw std::runtime_error("hybridFrontierProb: frame refused: its largest cluster has " + std::to_string(maxCluster) + " measurements");
+    return rows_of(flat, nL, nM, nL + 1);
+}
+
 kbest_ctx *kbest_shims_context() { return global_ctx(); }

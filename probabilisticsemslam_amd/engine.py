@@ -34,6 +34,9 @@ KBEST_LBP_MAX_COLS = 128     # measurements per frame of the belief-propagation 
 KBEST_CLUSTER_MAX_COLS = 128  # measurements per frame of the clustered exact association probabilities
 KBEST_CLUSTER_MAX_SIZE = 16   # ... and per cluster
 KBEST_BIGCLUSTER_MAX_SIZE = 20  # ... and per cluster of the big-cluster tier (one cluster over the whole chip)
+KBEST_FRONTIER_MAX_COLS = 64    # ... and per cluster of the frontier tier (one workgroup per cluster)
+KBEST_FRONTIER_MAX_WIDTH = 16   # ... whose rows, in the greedy order, keep at most this many columns open
+KBEST_FRONTIER_SLOT = 4 << 20   # ... and whose layers fit this many bytes
 
 # every symbol include/kbest_c.h declares
 C_ABI_SYMBOLS = (
@@ -56,6 +59,8 @@ C_ABI_SYMBOLS = (
     "kbest_clustered_partial_batch_f64_dev", "kbest_hybrid_probs_batch_f64",
     "kbest_reserve_bigcluster", "kbest_set_bigcluster_work_cap", "kbest_bigcluster_probs_f64_dev",
     "kbest_hybrid_exact_probs_batch_f64",
+    "kbest_reserve_frontier", "kbest_set_frontier_work_cap", "kbest_set_frontier_slot", "kbest_frontier_probs_f64_dev",
+    "kbest_hybrid_frontier_probs_batch_f64",
 )
 KBEST_MULTI_STAMPS = 6
 KBEST_MULTI_BATCH, KBEST_MULTI_SUBTREE = 0, 1
@@ -183,6 +188,13 @@ def load_library():
         lib.kbest_bigcluster_probs_f64_dev.argtypes = [vp, C.c_int, i32p, i32p, i64p, i64p, dp, dp, dp, i32p, vp]
         lib.kbest_hybrid_exact_probs_batch_f64.argtypes = [vp, C.c_int, i32p, i32p, dp, i64p, C.c_int, C.c_int, C.c_int, C.c_int, dp,
                                                            i64p, dp, i32p, i32p, i32p, i32p]
+    if hasattr(lib, "kbest_hybrid_frontier_probs_batch_f64"):
+        lib.kbest_reserve_frontier.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+        lib.kbest_set_frontier_work_cap.argtypes = [vp, C.c_size_t]
+        lib.kbest_set_frontier_slot.argtypes = [vp, C.c_size_t]
+        lib.kbest_frontier_probs_f64_dev.argtypes = [vp, C.c_int, i32p, i32p, i64p, i64p, dp, dp, dp, i32p, i32p, vp]
+        lib.kbest_hybrid_frontier_probs_batch_f64.argtypes = [vp, C.c_int, i32p, i32p, dp, i64p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                              C.c_int, dp, i64p, dp, i32p, i32p, i32p, i32p, i32p]
     lib.kbest_register_host_buffer.argtypes = [vp, vp, C.c_size_t]
     lib.kbest_unregister_host_buffer.argtypes = [vp, vp]
     _lib = lib
@@ -518,6 +530,57 @@ class KBestEngine:
                                                             _dptr(d_sub), _dptr(d_probs), _dptr(d_logZ), _dptr(d_info),
                                                             _stream(stream)))
 
+    def hybrid_frontier_probs(self, costs, nL, nM, k=0, condition=False, max_exact=16, max_big=20, max_width=16):
+        """Batched hybridFrontierProb (kbest_hybrid_frontier_probs_batch_f64): hybrid_exact_probs() with the frontier tier first
+        among the open clusters -- every cluster of more than max_exact and at most 64 measurements whose rows, in the greedy
+        order, keep at most max_width (0 .. 16; 0: the tier is off) columns open is answered EXACTLY, one workgroup per cluster in
+        one launch; what the tier refuses goes to the big-cluster tier (at most max_big measurements), then to assignmentProb(k)
+        when k >= 1, and refuses its frame when k = 0.  Returns (list of [nM, nL+1] arrays, method[B], nOpen[B], nBig[B],
+        maxCluster[B], logPerm[B] as hybrid_exact_probs(), nFrontier[B]: the open clusters this tier answered)."""
+        nL, nM, B, flat, costOff, probOff, psizes, probs = _pack_frames(costs, nL, nM, "hybrid_frontier_probs")
+        method = np.zeros(B, np.int32)
+        nOpen = np.zeros(B, np.int32)
+        nBig = np.zeros(B, np.int32)
+        nFrontier = np.zeros(B, np.int32)
+        maxCluster = np.zeros(B, np.int32)
+        logPerm = np.zeros(B, np.float64)
+        self._check(self.lib.kbest_hybrid_frontier_probs_batch_f64(self.ctx, B, _ptr(nL), _ptr(nM), _ptr(flat), _ptr(costOff),
+                                                                   int(bool(condition)), int(k), int(max_exact), int(max_big),
+                                                                   int(max_width), _ptr(probs), _ptr(probOff), _ptr(logPerm),
+                                                                   _ptr(method), _ptr(nOpen), _ptr(nBig), _ptr(maxCluster),
+                                                                   _ptr(nFrontier)))
+        out = _split_probs(probs, probOff, psizes, nL, nM)
+        return out, method, nOpen, nBig, maxCluster, logPerm, nFrontier
+
+    def reserve_frontier(self, n, maxM, maxRows):
+        """kbest_reserve_frontier: the work space of frontier_probs_dev for n clusters of up to maxM measurements and maxRows
+        (nL_k + m_k) rows."""
+        self._check(self.lib.kbest_reserve_frontier(self.ctx, int(n), int(maxM), int(maxRows)))
+
+    def set_frontier_work_cap(self, nbytes=0):
+        """For tests (kbest_set_frontier_work_cap): the slots of the frontier tier in flight at the most, 0 = the default again."""
+        self._check(self.lib.kbest_set_frontier_work_cap(self.ctx, int(nbytes)))
+
+    def set_frontier_slot(self, nbytes=0):
+        """For tests (kbest_set_frontier_slot): the layers of one cluster of the frontier tier at the most, 0 = KBEST_FRONTIER_SLOT
+        again; a cluster that needs more is refused (info = -3)."""
+        self._check(self.lib.kbest_set_frontier_slot(self.ctx, int(nbytes)))
+
+    def frontier_probs_dev(self, m, nLk, subOff, probOff, d_sub, d_probs, d_logZ=None, d_info=None, d_width=None, stream=None,
+                           reserve=True):
+        """kbest_frontier_probs_f64_dev, asynchronous on `stream`: arguments as bigcluster_probs_dev() with up to 64 measurements a
+        cluster, plus d_width (the cluster's frontier width W).  info: 1 answered, 0 infeasible, -4 W > 16, -3 layers beyond the
+        slot (refused: probabilities and log Z untouched)."""
+        m = np.ascontiguousarray(m, dtype=np.int32)
+        nLk = np.ascontiguousarray(nLk, dtype=np.int32)
+        subOff = np.ascontiguousarray(subOff, dtype=np.int64)
+        probOff = np.ascontiguousarray(probOff, dtype=np.int64)
+        if reserve and len(m):
+            self.reserve_frontier(len(m), int(m.max()), int((m + nLk).max()))
+        self._check(self.lib.kbest_frontier_probs_f64_dev(self.ctx, len(m), _ptr(m), _ptr(nLk), _ptr(subOff), _ptr(probOff),
+                                                          _dptr(d_sub), _dptr(d_probs), _dptr(d_logZ), _dptr(d_info),
+                                                          _dptr(d_width), _stream(stream)))
+
     def set_clustered_slot_cap(self, nbytes=0):
         """For tests (kbest_set_clustered_slot_cap): the layers of one cluster at the most, 0 = KBEST_CLUSTER_SLOT_CAP again; a frame
         with a cluster that needs more is refused (info = -3)."""
@@ -850,6 +913,17 @@ def hybridProb(costMatrix, nL, nM, k):
     out, method, _, _ = _engine().hybrid_probs([costMatrix], [nL], [nM], k)
     if method[0] == -1:
         raise RuntimeError("hybridProb: frame refused: a cluster holds more rows >= nL than measurements")
+    return out[0]
+
+
+def hybridFrontierProb(costMatrix, nL, nM, k):
+    """Not in the reference: hybridExactProb with the frontier tier first: exact on every gated cluster of at most 64 measurements
+    whose rows, in the greedy order, keep at most 16 columns open, and on every other of at most 20; assignmentProb(k) on what is
+    left (k = 0: such a frame is refused).  Returns probs[nM][nL+1]; raises RuntimeError only when the frame is refused; an
+    infeasible frame comes back as all zeros."""
+    out, method, _, _, maxCluster, _, _ = _engine().hybrid_frontier_probs([costMatrix], [nL], [nM], k)
+    if method[0] == -1:
+        raise RuntimeError(f"hybridFrontierProb: frame refused: its largest cluster has {int(maxCluster[0])} measurements")
     return out[0]
 
 
