@@ -30,6 +30,7 @@
  *   kbest_hybrid_probs_batch_f64 / kbest_clustered_partial_batch_f64_dev
  *   kbest_hybrid_exact_probs_batch_f64 / kbest_bigcluster_probs_f64_dev
  *   kbest_hybrid_frontier_probs_batch_f64 / kbest_frontier_probs_f64_dev
+ *   kbest_hybrid_frontier_probs_batch_f64_dev / kbest_reserve_hybrid_dev
  *        the exact association probabilities by gated clusters, for frames of up to 128 measurements (not in the reference)
  *
  * Conventions kept from the reference: cost matrices are column-major
@@ -616,6 +617,40 @@ int kbest_hybrid_frontier_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *
                                           const int64_t *costOff, int condition, int k, int maxExact, int maxBig, int maxWidth,
                                           double *probs, const int64_t *probOff, double *logPerm, int32_t *method, int32_t *nOpen,
                                           int32_t *nBig, int32_t *maxCluster, int32_t *nFrontier);
+/*
+ * Asynchronous exact hybrid probabilities (kbest_hybrid.hip; not in the reference): the whole exact path of
+ * kbest_hybrid_frontier_probs_batch_f64(k = 0, maxBig = 0) on buffers that already lie on the device, on ONE stream -- the partial
+ * clustered kernel, a gather of the open clusters of all frames into one list (frame order, then label order: a prefix sum, no
+ * atomics), the frontier sweep over that list in one launch, and the scatter of every cluster's [m_k][nL_k + 1] block into its
+ * frame.  No host read, no synchronise, no allocation; stream order between the four launches is the only synchronisation.  Every
+ * output carries the bits of that host entry.  The big-cluster tier and the k-best leg stay host-only: a frame that holds a cluster
+ * the frontier tier does not take is refused here, as there, and may be sent to the host entry.
+ *
+ * kbest_hybrid_frontier_probs_batch_f64_dev: frames, d_cost, d_costOff, d_probs, d_probOff, condition and d_sub (the caller's work
+ * buffer, sized and addressed like d_cost: the host does not know the extent of the cost buffer) as in
+ * kbest_clustered_partial_batch_f64_dev.  maxExact 0 .. 16 (0 = 16), maxWidth 1 .. 16: maxWidth = 0 would turn the tier off, which
+ * with k = 0 answers nothing new -- KBEST_ERR_BAD_ARG, as everything outside those ranges.
+ *   d_method[b] (required):  0: every cluster exact;  -2: an answered or frontier cluster with Z = 0: the frame is zeros, logPerm
+ *       -inf;  -1: the partial kernel's d_info < 0, or an open cluster nobody took (more than 64 measurements, frontier info -3 or
+ *       -4, or W > maxWidth): a frame with open clusters is zeros, nFrontier 0, logPerm NaN;
+ *   d_logPerm[b], d_nOpen[b], d_nFrontier[b], d_maxCluster[b] (each may be NULL): as kbest_hybrid_frontier_probs_batch_f64.
+ * d_probs: the entry writes EVERY element of the slice of every frame within the launch bounds (the partial kernel zeroes the slice
+ * before anything else), and nothing outside the slices.  A frame beyond the bounds (nM < 1, nM > maxCol, nL < 0 or
+ * nL + nM > maxRawRow: method -1) is not touched at all -- neither its slice nor d_maxCluster[b]; a caller that wants zeros there,
+ * as the host entry's zeroed buffer gives, zeroes d_probs before the call.
+ * The context holds everything else: kbest_reserve_hybrid_dev(ctx, B, maxRawRow, maxCol) sizes, from those three alone, the
+ * clustered work space (kbest_reserve_clustered), the frontier slots and plans (clusters of up to min(maxCol, 64) measurements and
+ * maxRawRow rows, as many in flight as KBEST_FRONTIER_WORK_CAP and the chip allow), labels, descriptors and row lists, the list of
+ * up to B * maxCol clusters, their log Z_k | info | width, and maxCol * maxRawRow packed probabilities per frame.  Without it, or
+ * with a call beyond what was reserved: KBEST_ERR_NOT_RESERVED.  B = 0: KBEST_OK, nothing launched.  Asynchronous on `stream` (NULL:
+ * the context's); takes the context's lock like the other _dev entries; two calls on one stream need no synchronise between them.
+ */
+int kbest_reserve_hybrid_dev(kbest_ctx *ctx, int B, int maxRawRow, int maxCol);
+int kbest_hybrid_frontier_probs_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, const int32_t *d_nL,
+                                              const int32_t *d_nM, const double *d_cost, const int64_t *d_costOff, int condition,
+                                              int maxExact, int maxWidth, double *d_sub, double *d_probs, const int64_t *d_probOff,
+                                              double *d_logPerm, int32_t *d_method, int32_t *d_nOpen, int32_t *d_nFrontier,
+                                              int32_t *d_maxCluster, void *stream);
 /* on = 1: the HOST-buffer association entries of this context (kbest_weights / assoc_probs / bruteforce / quadric_assoc) enumerate
  * their k best in the REFERENCE's own order of operations (the reference-order kernel, as KBEST_FLAG_REFERENCE_ORDER does for
  * kbest_batch_f64): where exactly equal gains straddle slot k the assignments that are weighed are the ones the reference's

@@ -156,6 +156,8 @@ struct kbest_ctx {
     DevBufRaw frPlan;         // ... and one plan (KB_FRONTIER_STEP_DOUBLES per row) per workgroup
     size_t frSlot = KBEST_FRONTIER_SLOT;          // ... the layers of one cluster at the most (kbest_set_frontier_slot)
     size_t frWorkCap = KBEST_FRONTIER_WORK_CAP;   // ... the slots in flight at the most (kbest_set_frontier_work_cap)
+    DevBufRaw hybBuf;         // kbest_hybrid_frontier_probs_batch_f64_dev: labels, descriptors, row lists, the cluster list, the
+                              // per-cluster outputs and the packed probabilities (kbest_reserve_hybrid_dev; HybridLayout)
     DevBufRaw relayBuf;       // relay launches of the 64-row kernel: [B] LDS images (kbest_engine.hip)
     DevBufRaw relayFlags;     // ... and three words per matrix: claimed / done / gone (zeroed when the buffer is made, put back to zero by every launch)
     long long relayLaunches = 0;  // relay launches made (kbest_relay_launches)
@@ -620,6 +622,7 @@ int kbest_destroy(kbest_ctx *ctx)
     if (ctx->bigSmall.p) (void)hipFree(ctx->bigSmall.p);
     if (ctx->frLayers.p) (void)hipFree(ctx->frLayers.p);
     if (ctx->frPlan.p) (void)hipFree(ctx->frPlan.p);
+    if (ctx->hybBuf.p) (void)hipFree(ctx->hybBuf.p);
     if (ctx->relayFlags.p) (void)hipFree(ctx->relayFlags.p);
     if (ctx->lastEvent) (void)hipEventDestroy(ctx->lastEvent);
     for (auto &a : ctx->aux)
@@ -3696,6 +3699,143 @@ int kbest_frontier_probs_f64_dev(kbest_ctx *ctx, int n, const int32_t *m, const 
         const hipError_t e = kb::launch_frontier_pack(pk, d_sub, d_probs, d_logZ, d_info, d_width, w, (int)g, s);
         if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "frontier kernel launch", e);
     }
+    return KBEST_OK;
+}
+
+// ---- the exact hybrid path on the device (kbest_hybrid.hip): partial kernel, gather, frontier sweep, scatter, on one stream ------
+// Where everything lies in ctx->hybBuf for a call of (B, maxRawRow, maxCol), in bytes; every part is 16-byte aligned.  Each
+// size grows with each of the three, so a call within what was reserved fits.
+struct HybridLayout {
+    size_t info, nOpen, first, count, label, desc, rows, list, logZ, finfo, width, packed, total;
+    long long packStride, cap;  // doubles of packed probabilities per frame; clusters the list holds
+};
+static HybridLayout hybrid_layout(int B, int maxRawRow, int maxCol)
+{
+    HybridLayout L;
+    size_t at = 0;
+    auto take = [&at](size_t bytes) { const size_t here = at; at += (bytes + 15) & ~(size_t)15; return here; };
+    const size_t b = (size_t)B;
+    L.cap = (long long)B * maxCol;                       // a frame has at most nM clusters
+    L.packStride = (long long)maxCol * maxRawRow;        // a frame's clusters: sum m_k (nL_k + 1) <= nM (nL + 1) <= maxCol maxRawRow
+    L.info = take(b * 4);
+    L.nOpen = take(b * 4);
+    L.first = take(b * 4);
+    L.count = take(4);
+    L.label = take(b * (size_t)maxCol * 4);
+    L.desc = take(b * (size_t)maxCol * 16);
+    L.rows = take(b * (size_t)maxRawRow * 4);
+    L.list = take((size_t)L.cap * sizeof(kb::HybridItem));
+    L.logZ = take((size_t)L.cap * 8);
+    L.finfo = take((size_t)L.cap * 4);
+    L.width = take((size_t)L.cap * 4);
+    L.packed = take(b * (size_t)L.packStride * 8);
+    L.total = at;
+    return L;
+}
+
+// workgroups of the sweep: as the chip holds and as have a slot under the cap (frames_in_flight), a slot and a plan of
+// planDoubles in what was reserved.  0: nothing reserved
+static long long frontier_grid(const kbest_ctx *ctx, long long n, long long planDoubles)
+{
+    long long g = frames_in_flight(ctx, FRONTIER_WAVES_PER_CU, kb::KB_FRONTIER_THREADS, FRONTIER_LDS, (long long)(ctx->frSlot / 8),
+                                   n > (1 << 30) ? (1 << 30) : (int)n, ctx->frWorkCap);
+    const long long slots = (long long)(ctx->frLayers.bytes / ctx->frSlot), plans = (long long)(ctx->frPlan.bytes / ((size_t)planDoubles * 8));
+    if (g > slots) g = slots;
+    if (g > plans) g = plans;
+    return g;
+}
+
+int kbest_reserve_hybrid_dev(kbest_ctx *ctx, int B, int maxRawRow, int maxCol)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    int rc = check_frame_shape(ctx, "kbest_reserve_hybrid_dev", B, maxRawRow, maxCol, KBEST_CLUSTER_MAX_COLS, CLUSTER_COLS_TEXT);
+    if (rc != KBEST_OK || B == 0) return rc;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = kbest_reserve_clustered(ctx, B, maxRawRow, maxCol);
+    if (rc != KBEST_OK) return rc;
+    const HybridLayout L = hybrid_layout(B, maxRawRow, maxCol);
+    rc = kbest_reserve_frontier(ctx, L.cap > (1 << 30) ? (1 << 30) : (int)L.cap, maxCol < KBEST_FRONTIER_MAX_COLS ? maxCol : KBEST_FRONTIER_MAX_COLS,
+                                maxRawRow);
+    if (rc != KBEST_OK) return rc;
+    return raw_reserve(ctx, ctx->hybBuf, L.total);
+}
+
+int kbest_hybrid_frontier_probs_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, const int32_t *d_nL,
+                                              const int32_t *d_nM, const double *d_cost, const int64_t *d_costOff, int condition,
+                                              int maxExact, int maxWidth, double *d_sub, double *d_probs, const int64_t *d_probOff,
+                                              double *d_logPerm, int32_t *d_method, int32_t *d_nOpen, int32_t *d_nFrontier,
+                                              int32_t *d_maxCluster, void *stream)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    const char *who = "kbest_hybrid_frontier_probs_batch_f64_dev";
+    int rc = check_frame_shape(ctx, who, B, maxRawRow, maxCol, KBEST_CLUSTER_MAX_COLS, CLUSTER_COLS_TEXT);
+    if (rc != KBEST_OK) return rc;
+    if (maxExact < 0 || maxExact > KBEST_CLUSTER_MAX_SIZE || maxWidth < 1 || maxWidth > KBEST_FRONTIER_MAX_WIDTH)
+        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_hybrid_frontier_probs_batch_f64_dev: bad argument (maxExact 0 .. 16, maxWidth 1 .. 16; "
+                                            "maxWidth = 0 would turn the frontier tier off, and nothing else answers an open cluster here)");
+    if (B == 0) return KBEST_OK;
+    if (!d_nL || !d_nM || !d_cost || !d_costOff || !d_sub || !d_probs || !d_probOff || !d_method)
+        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_hybrid_frontier_probs_batch_f64_dev: bad argument");
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // everything is checked before anything is launched; an asynchronous entry never allocates
+    const HybridLayout L = hybrid_layout(B, maxRawRow, maxCol);
+    kb::FrontierWork w;
+    w.slotDoubles = (long long)(ctx->frSlot / 8);
+    w.planDoubles = (long long)maxRawRow * kb::KB_FRONTIER_STEP_DOUBLES;
+    const long long g = frontier_grid(ctx, L.cap, w.planDoubles);
+    kb::ClusterPlan pl;
+    rc = cluster_plan_of(ctx, maxRawRow, maxCol, pl, who);
+    if (rc != KBEST_OK) return rc;
+    if (ctx->hybBuf.bytes < L.total || g < 1 || ctx->clusBuf.bytes < (size_t)pl.slotDoubles * 8)
+        return fail(ctx, KBEST_ERR_NOT_RESERVED, "kbest_hybrid_frontier_probs_batch_f64_dev: call kbest_reserve_hybrid_dev first");
+    w.layers = static_cast<double *>(ctx->frLayers.p);
+    w.plan = static_cast<double *>(ctx->frPlan.p);
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    unsigned char *h8 = static_cast<unsigned char *>(ctx->hybBuf.p);
+    auto i32 = [h8](size_t off) { return reinterpret_cast<int32_t *>(h8 + off); };
+    // the partial kernel: orders the stream behind the context's last launch and marks its own
+    rc = kbest_clustered_partial_batch_f64_dev(ctx, B, maxRawRow, maxCol, d_nL, d_nM, d_cost, d_costOff, condition, maxExact, d_probs,
+                                               d_probOff, d_logPerm, i32(L.info), d_maxCluster, i32(L.label), maxCol, i32(L.nOpen),
+                                               i32(L.desc), maxCol, i32(L.rows), maxRawRow, d_sub, stream);
+    if (rc != KBEST_OK) return rc;
+    const Launched mark{ctx, s};
+    kb::HybridParams hp;
+    hp.nL = d_nL;
+    hp.nM = d_nM;
+    hp.costOff = reinterpret_cast<const long long *>(d_costOff);
+    hp.probOff = reinterpret_cast<const long long *>(d_probOff);
+    hp.cost = d_cost;
+    hp.probs = d_probs;
+    hp.logPerm = d_logPerm;
+    hp.method = d_method;
+    hp.nOpenOut = d_nOpen;
+    hp.nFrontier = d_nFrontier;
+    hp.info = i32(L.info);
+    hp.nOpen = i32(L.nOpen);
+    hp.label = i32(L.label);
+    hp.openDesc = i32(L.desc);
+    hp.openRows = i32(L.rows);
+    hp.list = reinterpret_cast<kb::HybridItem *>(h8 + L.list);
+    hp.count = i32(L.count);
+    hp.first = i32(L.first);
+    double *packed = reinterpret_cast<double *>(h8 + L.packed), *logZ = reinterpret_cast<double *>(h8 + L.logZ);
+    hp.packed = packed;
+    hp.logZ = logZ;
+    hp.finfo = i32(L.finfo);
+    hp.width = i32(L.width);
+    hp.packStride = L.packStride;
+    hp.B = B;
+    hp.maxRawRow = maxRawRow;
+    hp.maxCol = maxCol;
+    hp.condition = condition ? 1 : 0;
+    hp.maxWidth = maxWidth;
+    hipError_t e = kb::launch_hybrid_gather(hp, s);
+    if (e == hipSuccess)
+        e = kb::launch_frontier_list(hp.list, hp.count, d_sub, packed, logZ, i32(L.finfo), i32(L.width), w, (int)g, s);
+    if (e == hipSuccess) e = kb::launch_hybrid_scatter(hp, s);
+    if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "hybrid kernel launch", e);
     return KBEST_OK;
 }
 

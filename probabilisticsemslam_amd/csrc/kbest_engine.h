@@ -670,6 +670,34 @@ struct FrontierWork {
 hipError_t launch_frontier_pack(const FrontierPack &p, const double *sub, double *probs, double *logZ, int *info, int *width,
                                 const FrontierWork &w, int grid, hipStream_t stream);
 
+// kbest_hybrid.hip: the exact hybrid path on the device (kbest_c.h, "Asynchronous exact hybrid probabilities").  One open cluster
+// of the flat list hybrid_gather_kernel makes of the partial kernel's descriptors, in frame order, then label order.
+struct HybridItem {
+    long long subOff, probOff;  // its sub-block in sub / its [m][nL + 1] probabilities in the packed buffer, in doubles
+    long long rowAt;            // its landmark rows in openRows
+    int b, root, m, nL;         // frame, root label, columns, landmark rows
+    int idx, sent;              // its place in the list (and in logZ / info / width); 0: more than 64 columns, the sweep skips it
+};
+struct HybridParams {
+    const int *nL, *nM;                        // [B]
+    const long long *costOff, *probOff;        // [B]
+    const double *cost;
+    double *probs, *logPerm;                   // logPerm: the partial kernel's sums in, the frames' out (or nullptr)
+    int *method, *nOpenOut, *nFrontier;        // [B]; nOpenOut, nFrontier may be nullptr
+    const int *info, *nOpen, *label, *openDesc, *openRows;  // the partial kernel's outputs: [B], [B], [B][maxCol], [B][maxCol][4], [B][maxRawRow]
+    HybridItem *list;                          // [B * maxCol]
+    int *count, *first;                        // clusters in the list; [B]: the first cluster of every frame
+    const double *packed, *logZ;               // the sweep's outputs per cluster of the list
+    const int *finfo, *width;
+    long long packStride;                      // doubles of the packed buffer per frame
+    int B, maxRawRow, maxCol, condition, maxWidth;
+};
+// the sweep of kbest_frontier.hip on the gathered list: `grid` workgroups, each with a slot and a plan of w
+hipError_t launch_frontier_list(const HybridItem *list, const int *count, const double *sub, double *probs, double *logZ, int *info,
+                                int *width, const FrontierWork &w, int grid, hipStream_t stream);
+hipError_t launch_hybrid_gather(const HybridParams &p, hipStream_t stream);
+hipError_t launch_hybrid_scatter(const HybridParams &p, hipStream_t stream);
+
 }  // namespace kb
 
 // kbest_capi.cpp: completes the gain levels that straddle slot k in the caller's HOST tables (see there)

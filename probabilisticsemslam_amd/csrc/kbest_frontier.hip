@@ -26,6 +26,8 @@
 // order of every sum depends on the cluster alone, so a cluster gives the same bits alone, anywhere in a batch and under any cap.
 // info: 1 answered; 0: Z' = 0 (zeros, log Z = -inf); -4: W > 16; -3: the layers sum_i 2^|Phi_i| + 2 2^W doubles exceed the
 // slot -- both from the cluster alone, and a refused cluster's outputs are not touched.
+// Two entry points, one sweep (frontier_sweep<Source>): frontier_kernel takes its clusters from a kernel-argument pack,
+// frontier_list_kernel from the list kbest_hybrid.hip gathers on the device.
 #include <hip/hip_runtime.h>
 
 #include "kbest_engine.h"
@@ -131,18 +133,44 @@ __device__ __forceinline__ void load_step(FrShared &sh, const FrontierStep *plan
     }
 }
 
-__global__ void __launch_bounds__(FR_THREADS)
-frontier_kernel(FrontierPack p, const double *sub, double *probs, double *logZ, int *info, int *width, FrontierWork wk)
+// Where the clusters of a launch come from: the kernel-argument pack of kbest_frontier_probs_f64_dev, or the list
+// hybrid_gather_kernel (kbest_hybrid.hip) left in HBM with its count word.  The sweep below is the same code for both.
+struct PackSource {
+    const FrontierPack &p;
+    __device__ __forceinline__ int n() const { return p.n; }
+    __device__ __forceinline__ bool sent(int) const { return true; }
+    __device__ __forceinline__ int m(int k) const { return p.c[k].m; }
+    __device__ __forceinline__ int nL(int k) const { return p.c[k].nL; }
+    __device__ __forceinline__ long long subOff(int k) const { return p.c[k].subOff; }
+    __device__ __forceinline__ long long probOff(int k) const { return p.c[k].probOff; }
+    __device__ __forceinline__ int idx(int k) const { return p.base + k; }
+};
+struct ListSource {
+    const HybridItem *list;
+    const int *count;
+    __device__ __forceinline__ int n() const { return *count; }
+    __device__ __forceinline__ bool sent(int k) const { return list[k].sent != 0; }
+    __device__ __forceinline__ int m(int k) const { return list[k].m; }
+    __device__ __forceinline__ int nL(int k) const { return list[k].nL; }
+    __device__ __forceinline__ long long subOff(int k) const { return list[k].subOff; }
+    __device__ __forceinline__ long long probOff(int k) const { return list[k].probOff; }
+    __device__ __forceinline__ int idx(int k) const { return k; }
+};
+
+template <class Source>
+__device__ __forceinline__ void frontier_sweep(FrShared &sh, const Source &src, const double *sub, double *probs, double *logZ,
+                                               int *info, int *width, const FrontierWork &wk)
 {
-    __shared__ FrShared sh;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     double *slot = wk.layers + (long long)blockIdx.x * wk.slotDoubles;
     FrontierStep *plan = reinterpret_cast<FrontierStep *>(wk.plan + (long long)blockIdx.x * wk.planDoubles);
     const double INF = d_inf();
-    for (int k = blockIdx.x; k < p.n; k += gridDim.x) {
-        const int m = p.c[k].m, nL = p.c[k].nL, nr = nL + m, idx = p.base + k;
-        const double *x = sub + p.c[k].subOff;
-        double *out = probs + p.c[k].probOff;
+    const int n = src.n();
+    for (int k = blockIdx.x; k < n; k += gridDim.x) {
+        if (!src.sent(k)) continue;  // (uniform)
+        const int m = src.m(k), nL = src.nL(k), nr = nL + m, idx = src.idx(k);
+        const double *x = sub + src.subOff(k);
+        double *out = probs + src.probOff(k);
         __syncthreads();  // (the previous cluster is done with the shared arrays)
         if ((long long)nr * KB_FRONTIER_STEP_DOUBLES > wk.planDoubles || nr > FR_ROWS || m > KB_FRONTIER_MAX_COLS) {
             if (tid == 0 && info) info[idx] = -3;  // (the host entry never lets this happen)
@@ -357,6 +385,22 @@ frontier_kernel(FrontierPack p, const double *sub, double *probs, double *logZ, 
     }
 }
 
+__global__ void __launch_bounds__(FR_THREADS)
+frontier_kernel(FrontierPack p, const double *sub, double *probs, double *logZ, int *info, int *width, FrontierWork wk)
+{
+    __shared__ FrShared sh;
+    frontier_sweep(sh, PackSource{p}, sub, probs, logZ, info, width, wk);
+}
+
+// a workgroup without a cluster (blockIdx.x >= *count) returns at once
+__global__ void __launch_bounds__(FR_THREADS)
+frontier_list_kernel(const HybridItem *list, const int *count, const double *sub, double *probs, double *logZ, int *info, int *width,
+                     FrontierWork wk)
+{
+    __shared__ FrShared sh;
+    frontier_sweep(sh, ListSource{list, count}, sub, probs, logZ, info, width, wk);
+}
+
 }  // namespace
 
 hipError_t launch_frontier_pack(const FrontierPack &p, const double *sub, double *probs, double *logZ, int *info, int *width,
@@ -366,6 +410,14 @@ hipError_t launch_frontier_pack(const FrontierPack &p, const double *sub, double
     if (grid > p.n) grid = p.n;
     if (grid < 1) grid = 1;
     hipLaunchKernelGGL(frontier_kernel, dim3(grid), dim3(FR_THREADS), 0, stream, p, sub, probs, logZ, info, width, w);
+    return hipGetLastError();
+}
+
+hipError_t launch_frontier_list(const HybridItem *list, const int *count, const double *sub, double *probs, double *logZ, int *info,
+                                int *width, const FrontierWork &w, int grid, hipStream_t stream)
+{
+    if (grid < 1) return hipSuccess;
+    hipLaunchKernelGGL(frontier_list_kernel, dim3(grid), dim3(FR_THREADS), 0, stream, list, count, sub, probs, logZ, info, width, w);
     return hipGetLastError();
 }
 

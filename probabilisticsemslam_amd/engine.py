@@ -61,6 +61,7 @@ C_ABI_SYMBOLS = (
     "kbest_hybrid_exact_probs_batch_f64",
     "kbest_reserve_frontier", "kbest_set_frontier_work_cap", "kbest_set_frontier_slot", "kbest_frontier_probs_f64_dev",
     "kbest_hybrid_frontier_probs_batch_f64",
+    "kbest_reserve_hybrid_dev", "kbest_hybrid_frontier_probs_batch_f64_dev",
 )
 KBEST_MULTI_STAMPS = 6
 KBEST_MULTI_BATCH, KBEST_MULTI_SUBTREE = 0, 1
@@ -195,6 +196,10 @@ def load_library():
         lib.kbest_frontier_probs_f64_dev.argtypes = [vp, C.c_int, i32p, i32p, i64p, i64p, dp, dp, dp, i32p, i32p, vp]
         lib.kbest_hybrid_frontier_probs_batch_f64.argtypes = [vp, C.c_int, i32p, i32p, dp, i64p, C.c_int, C.c_int, C.c_int, C.c_int,
                                                               C.c_int, dp, i64p, dp, i32p, i32p, i32p, i32p, i32p]
+    if hasattr(lib, "kbest_hybrid_frontier_probs_batch_f64_dev"):
+        lib.kbest_reserve_hybrid_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+        lib.kbest_hybrid_frontier_probs_batch_f64_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int, i32p, i32p, dp, i64p, C.c_int, C.c_int,
+                                                                  C.c_int, dp, dp, i64p, dp, i32p, i32p, i32p, i32p, vp]
     lib.kbest_register_host_buffer.argtypes = [vp, vp, C.c_size_t]
     lib.kbest_unregister_host_buffer.argtypes = [vp, vp]
     _lib = lib
@@ -773,6 +778,27 @@ class KBestEngine:
                                                                    _dptr(d_label), int(labelStride), _dptr(d_nOpen), _dptr(d_openDesc),
                                                                    int(descStride), _dptr(d_openRows), int(rowStride), _dptr(d_sub),
                                                                    _stream(stream)))
+
+    def reserve_hybrid_dev(self, B, maxRawRow, maxCol):
+        """kbest_reserve_hybrid_dev: everything hybrid_frontier_probs_dev needs besides the caller's buffers, sized from the
+        three numbers alone."""
+        self._check(self.lib.kbest_reserve_hybrid_dev(self.ctx, int(B), int(maxRawRow), int(maxCol)))
+
+    def hybrid_frontier_probs_dev(self, B, maxRawRow, maxCol, d_nL, d_nM, d_cost, d_costOff, d_sub, d_probs, d_probOff, d_method,
+                                  d_logPerm=None, d_nOpen=None, d_nFrontier=None, d_maxCluster=None, condition=False, max_exact=16,
+                                  max_width=16, stream=None, reserve=True):
+        """kbest_hybrid_frontier_probs_batch_f64_dev on torch CUDA tensors, asynchronous on `stream` (a raw hipStream_t integer):
+        hybrid_frontier_probs(k=0, max_big=0) -- the partial clustered kernel, the frontier tier on every open cluster, the scatter
+        into the frames -- without a host read, a synchronise or an allocation, and with that entry's bits.  d_sub: a work buffer
+        shaped like d_cost.  d_method int32 [B] is required; d_logPerm (float64), d_nOpen, d_nFrontier, d_maxCluster (int32) may be
+        None.  A frame beyond (maxRawRow, maxCol) is not touched (method -1): zero d_probs first for zeros there.  reserve=False:
+        the caller has called reserve_hybrid_dev (timed loops; the C entry never allocates)."""
+        if reserve:
+            self.reserve_hybrid_dev(B, maxRawRow, maxCol)
+        self._check(self.lib.kbest_hybrid_frontier_probs_batch_f64_dev(
+            self.ctx, int(B), int(maxRawRow), int(maxCol), _dptr(d_nL), _dptr(d_nM), _dptr(d_cost), _dptr(d_costOff),
+            int(bool(condition)), int(max_exact), int(max_width), _dptr(d_sub), _dptr(d_probs), _dptr(d_probOff), _dptr(d_logPerm),
+            _dptr(d_method), _dptr(d_nOpen), _dptr(d_nFrontier), _dptr(d_maxCluster), _stream(stream)))
 
 
 class KBestMulti:
