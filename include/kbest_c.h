@@ -24,6 +24,8 @@
  *        batched form of  asgnBB (assignment.cpp:724-797; k = 1, maximize)
  *   kbest_permanent_probs_batch_f64 / kbest_permanent_probs_batch_f64_dev
  *        batched form of  permanentProb (assignment.h:13, assignment.cpp:145-290), exact for every permOpt
+ *   kbest_sample_assoc_batch_f64 / kbest_sample_assoc_batch_f64_dev
+ *        joint associations drawn from the exact posterior those probabilities are the marginals of (not in the reference)
  *   kbest_belief_probs_batch_f64 / kbest_belief_probs_batch_f64_dev
  *        the association probabilities by loopy belief propagation, for frames of any size (not in the reference)
  *   kbest_clustered_probs_batch_f64 / kbest_clustered_probs_batch_f64_dev
@@ -392,6 +394,47 @@ int kbest_reserve_permanent(kbest_ctx *ctx, int B, int maxRawRow, int maxCol);
 int kbest_set_permanent_work_cap(kbest_ctx *ctx, size_t bytes);
 /* Diagnostic, for tests: workgroups -- frames in flight -- of the context's last permanent launch (-1: null context). */
 int kbest_last_permanent_grid(kbest_ctx *ctx);
+
+/*
+ * Joint associations DRAWN from the exact posterior (kbest_sample.hip; not in the reference, whose permOpt 0 only estimates the
+ * permanent by sampling): nSample independent draws per frame, each a whole consistent hypothesis -- no two measurements on one
+ * landmark -- with probability (product of its toProbs entries) / perm exactly.  Frames, layout and conditioning of
+ * kbest_permanent_probs_batch_f64; the forward sums over column subsets are that entry's, and perm[b] (may be NULL) carries the
+ * bits of its perm[b].  Outputs per frame b:
+ *   assign   int32 [nSample][nM] at asgOff[b] (in int32s): assign[s][c] is the RAW row of the caller's block that measurement c
+ *            takes in draw s, in the caller's numbering before any conditioning; a miss is the measurement's own row >= nL (with
+ *            the block-diagonal miss rows of this project: nL + c), it is not folded into nL.
+ *   logProb  double [nSample] at lpOff[b] (in doubles): log(product of the chosen toProbs entries) - log(perm[b]).
+ * A frame whose permanent is 0 comes back with every assign -1, every logProb NaN and perm[b] = 0.
+ * The uniforms -- this definition is the contract; a caller can reproduce every draw from it: row i of the frame's ACTIVE rows
+ * (the rows that are not all zero after conditioning and toProbs, in order, i counted from 0) uses, for draw s of the launch,
+ *   Philox4x32-10 with key (seed low word, seed high word) and counter (sampleBase + s, i >> 1, frameKey[b] low word,
+ *   frameKey[b] high word); output words 0, 1 serve even i and words 2, 3 serve odd i;
+ *   u = (((hi << 32) | lo) >> 11) * 2^-53, lo the first and hi the second word of the pair.
+ * The walk runs over the active rows from the last to the first with S = all measurements: tot = F[i+1][S], T = u * tot,
+ * acc = F[i][S]; T < acc: row i takes nothing; else for the measurements c of S in ascending order with a non-zero entry:
+ * acc = acc + a[i][c] * F[i][S without c], and the first c with T < acc is taken (none, by rounding: the last c whose term was
+ * > 0).  F[i][S]: the sum over the ways rows 0 .. i-1 fill exactly S.  frameKey (may be NULL: frame b has key b) makes a frame's
+ * draws independent of the batch it travels in, bit for bit; counting the active rows makes them the same on a raw block with
+ * condition = 1 and on its conditioned block with condition = 0.  sampleBase continues a sequence: draws sampleBase .. sampleBase +
+ * nSample - 1 are what one larger call returns at those places.
+ * Limits: those of the permanent entry, 1 <= nSample, sampleBase + nSample <= 2^32.  Host buffers; stages, reserves and runs the
+ * device entry below.
+ */
+int kbest_sample_assoc_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,
+                                 const int64_t *costOff, int condition, int nSample, uint64_t seed, uint32_t sampleBase,
+                                 const uint64_t *frameKey, int32_t *assign, const int64_t *asgOff, double *logProb,
+                                 const int64_t *lpOff, double *perm);
+/* The same on device buffers, asynchronous on `stream` (NULL: the context's): one launch, no allocation.  maxRawRow / maxCol as
+ * for the permanent entry (a frame beyond them gets perm = 0, its assign and logProb are left alone).  Needs kbest_reserve_sample
+ * first (KBEST_ERR_NOT_RESERVED) where the subset layers do not fit LDS: the work space, its size and its cap are the permanent
+ * entry's, and kbest_reserve_sample reserves exactly what kbest_reserve_permanent does. */
+int kbest_sample_assoc_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, const int32_t *d_nL,
+                                     const int32_t *d_nM, const double *d_cost, const int64_t *d_costOff, int condition,
+                                     int nSample, uint64_t seed, uint32_t sampleBase, const uint64_t *d_frameKey,
+                                     int32_t *d_assign, const int64_t *d_asgOff, double *d_logProb, const int64_t *d_lpOff,
+                                     double *d_perm, void *stream);
+int kbest_reserve_sample(kbest_ctx *ctx, int B, int maxRawRow, int maxCol);
 
 /*
  * Association probabilities by loopy belief propagation on the assignment model (kbest_lbp.hip; not in the reference): the

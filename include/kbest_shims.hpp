@@ -42,6 +42,7 @@
 #define KBEST_SHIMS_HPP
 
 #include <cstddef>
+#include <cstdint>
 #include <vector>
 
 class MurtyHyp {
@@ -120,6 +121,12 @@ std::vector<double> conditionCosts(const std::vector<double> &costs, size_t nRow
 // (kbest_permanent_probs_batch_f64: sums over column subsets, nM <= 16); any other value throws std::runtime_error
 // (assignment.cpp:344, 406).
 std::vector<std::vector<double>> permanentProb(std::vector<double> costMatrix, size_t nL, size_t nM, int permOpt);
+
+// Not in the reference: nSample joint associations drawn from the exact posterior permanentProb gives the marginals of
+// (kbest_sample_assoc_batch_f64, nM <= 16; frame key 0, draws 0 .. nSample-1 of `seed`): [nSample][nM], entry [s][c] the row of
+// costMatrix that measurement c takes in draw s (a row >= nL: unassigned).  A frame without any consistent association (permanent
+// 0) throws std::runtime_error.
+std::vector<std::vector<int>> sampleAssoc(const std::vector<double> &costMatrix, size_t nL, size_t nM, size_t nSample, uint64_t seed);
 
 // Not in the reference: the association probabilities by loopy belief propagation (kbest_belief_probs_batch_f64, tol 1e-12, at most
 // 10 000 sweeps), [nM][nL+1] like assignmentProb, for frames of up to 128 measurements and 1 024 rows -- the frames permanentProb

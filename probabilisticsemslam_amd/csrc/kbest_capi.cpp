@@ -348,6 +348,7 @@ struct FrameBatch {
     const int64_t *costOff = nullptr, *probOff = nullptr;
     DevBuf dCost, dMeta, dProbs;
 
+    // (probOff_ = nullptr: an entry without probabilities, the sampler)
     int scan(kbest_ctx *ctx, const char *who, int B_, const int32_t *nL_, const int32_t *nM_, const int64_t *costOff_, const int64_t *probOff_)
     {
         B = B_;
@@ -356,12 +357,12 @@ struct FrameBatch {
         costOff = costOff_;
         probOff = probOff_;
         for (int b = 0; b < B; b++) {
-            if (nL[b] < 0 || nM[b] < 1 || costOff[b] < 0 || probOff[b] < 0)
+            if (nL[b] < 0 || nM[b] < 1 || costOff[b] < 0 || (probOff && probOff[b] < 0))
                 return fail(ctx, KBEST_ERR_BAD_ARG, (std::string(who) + ": a frame with nL < 0, nM < 1 or a negative offset").c_str());
             const long long nr = (long long)nL[b] + nM[b];
             if (nr > maxRawRow) maxRawRow = nr > (1 << 30) ? (1 << 30) : (int)nr;
             if (nM[b] > maxCol) maxCol = nM[b];
-            const size_t ce = (size_t)costOff[b] + (size_t)nr * (size_t)nM[b], pe = (size_t)probOff[b] + slice(b);
+            const size_t ce = (size_t)costOff[b] + (size_t)nr * (size_t)nM[b], pe = probOff ? (size_t)probOff[b] + slice(b) : 0;
             if (ce > costN) costN = ce;
             if (pe > probN) probN = pe;
         }
@@ -375,7 +376,7 @@ struct FrameBatch {
     {
         std::vector<unsigned char> meta((size_t)B * 24);
         memcpy(meta.data(), costOff, (size_t)B * 8);
-        memcpy(meta.data() + (size_t)B * 8, probOff, (size_t)B * 8);
+        if (probOff) memcpy(meta.data() + (size_t)B * 8, probOff, (size_t)B * 8);
         memcpy(meta.data() + (size_t)B * 16, nL, (size_t)B * 4);
         memcpy(meta.data() + (size_t)B * 20, nM, (size_t)B * 4);
         hipError_t e;
@@ -386,7 +387,7 @@ struct FrameBatch {
         if (!ok) return fail(ctx, KBEST_ERR_NOMEM, (std::string(who) + ": device buffers").c_str(), e);
         HIP_TRY(ctx, hipMemcpy(dCost.p, cost, costN * 8, hipMemcpyHostToDevice));
         HIP_TRY(ctx, hipMemcpy(dMeta.p, meta.data(), meta.size(), hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemsetAsync(dProbs.p, 0, probN * 8, ctx->stream));
+        if (probN) HIP_TRY(ctx, hipMemsetAsync(dProbs.p, 0, probN * 8, ctx->stream));
         return KBEST_OK;
     }
     const int64_t *d_costOff() { return dMeta.as<int64_t>(); }
@@ -2856,6 +2857,113 @@ extern "C" int kbest_permanent_probs_batch_f64(kbest_ctx *ctx, int B, const int3
     rc = fb.download(ctx, hp);
     if (rc != KBEST_OK) return rc;
     fb.scatter(hp, probs);
+    if (perm) HIP_TRY(ctx, hipMemcpy(perm, dPerm.p, (size_t)B * 8, hipMemcpyDeviceToHost));
+    return KBEST_OK;
+}
+
+// ---- draws from the exact posterior (kbest_sample.hip): the permanent kernel's plan, work space and frames in flight ------------
+extern "C" int kbest_reserve_sample(kbest_ctx *ctx, int B, int maxRawRow, int maxCol)
+{
+    return kbest_reserve_permanent(ctx, B, maxRawRow, maxCol);
+}
+
+extern "C" int kbest_sample_assoc_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, const int32_t *d_nL,
+                                                const int32_t *d_nM, const double *d_cost, const int64_t *d_costOff, int condition,
+                                                int nSample, uint64_t seed, uint32_t sampleBase, const uint64_t *d_frameKey,
+                                                int32_t *d_assign, const int64_t *d_asgOff, double *d_logProb, const int64_t *d_lpOff,
+                                                double *d_perm, void *stream)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    const char *who = "kbest_sample_assoc_batch_f64_dev";
+    int rc = check_frame_shape(ctx, who, B, maxRawRow, maxCol, KBEST_PERM_MAX_COLS, PERM_COLS_TEXT);
+    if (rc != KBEST_OK) return rc;
+    if (!d_nL || !d_nM || !d_cost || !d_costOff || !d_assign || !d_asgOff || !d_logProb || !d_lpOff || nSample < 1 ||
+        (uint64_t)sampleBase + (uint64_t)nSample > ((uint64_t)1 << 32))
+        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_sample_assoc_batch_f64_dev: bad argument");
+    if (B == 0) return KBEST_OK;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const kb::PermPlan pl = kb::perm_plan(maxRawRow, maxCol, ctx->ldsLimit, ctx->ldsPerCU);
+    if (pl.slotDoubles > 0 && ctx->permBuf.bytes < (size_t)pl.slotDoubles * 8)  // asynchronous entry: never allocates
+        return fail(ctx, KBEST_ERR_NOT_RESERVED, "kbest_sample_assoc_batch_f64_dev: call kbest_reserve_sample first");
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = order_behind_last(ctx, s);  // (one work space per context)
+    if (rc != KBEST_OK) return rc;
+    const Launched mark{ctx, s};
+    kb::SampleParams sp;
+    sp.cost = d_cost;
+    sp.costOff = reinterpret_cast<const long long *>(d_costOff);
+    sp.nL = d_nL;
+    sp.nM = d_nM;
+    sp.frameKey = reinterpret_cast<const kb::u64 *>(d_frameKey);
+    sp.assign = d_assign;
+    sp.asgOff = reinterpret_cast<const long long *>(d_asgOff);
+    sp.logProb = d_logProb;
+    sp.lpOff = reinterpret_cast<const long long *>(d_lpOff);
+    sp.perm = d_perm;
+    sp.work = static_cast<double *>(ctx->permBuf.p);
+    sp.slotStride = pl.slotDoubles;
+    sp.seed = seed;
+    sp.sampleBase = sampleBase;
+    sp.nSample = nSample;
+    sp.B = B;
+    sp.maxRawRow = maxRawRow;
+    sp.maxCol = maxCol;
+    sp.condition = condition ? 1 : 0;
+    // (the kernel's 109 VGPRs give 4 waves per SIMD, as the permanent kernel's: profiles/sample_resource_usage.txt)
+    const int grid = frames_in_flight(ctx, PERM_WAVES_PER_CU, pl.threads, pl.lds, pl.slotDoubles, B,
+                                      ctx->permBuf.bytes < ctx->permCap ? ctx->permBuf.bytes : ctx->permCap);
+    const hipError_t e = kb::launch_kbest_sample(sp, pl, grid, s);
+    if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "sampling kernel launch", e);
+    return KBEST_OK;
+}
+
+extern "C" int kbest_sample_assoc_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,
+                                            const int64_t *costOff, int condition, int nSample, uint64_t seed, uint32_t sampleBase,
+                                            const uint64_t *frameKey, int32_t *assign, const int64_t *asgOff, double *logProb,
+                                            const int64_t *lpOff, double *perm)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    if (B < 0 || nSample < 1 || (B > 0 && (!nL || !nM || !cost || !costOff || !assign || !asgOff || !logProb || !lpOff)))
+        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_sample_assoc_batch_f64: bad argument");
+    if (B == 0) return KBEST_OK;
+    const char *who = "kbest_sample_assoc_batch_f64";
+    FrameBatch fb;
+    int rc = fb.scan(ctx, who, B, nL, nM, costOff, nullptr);
+    if (rc != KBEST_OK) return rc;
+    rc = check_frame_shape(ctx, who, B, fb.maxRawRow, fb.maxCol, KBEST_PERM_MAX_COLS, PERM_COLS_TEXT);
+    if (rc != KBEST_OK) return rc;
+    size_t asgN = 0, lpN = 0;  // int32s / doubles up to the end of the last frame's draws
+    for (int b = 0; b < B; b++) {
+        if (asgOff[b] < 0 || lpOff[b] < 0) return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_sample_assoc_batch_f64: a negative offset");
+        asgN = std::max(asgN, (size_t)asgOff[b] + (size_t)nSample * (size_t)nM[b]);
+        lpN = std::max(lpN, (size_t)lpOff[b] + (size_t)nSample);
+    }
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = kbest_reserve_sample(ctx, B, fb.maxRawRow, fb.maxCol);
+    if (rc != KBEST_OK) return rc;
+    DevBuf dPerm, dAsg, dLp, dOff;  // off: asgOff[B] | lpOff[B] | frameKey[B] (8 bytes each)
+    rc = fb.upload(ctx, who, cost, {{&dPerm, (size_t)B * 8}, {&dAsg, asgN * 4}, {&dLp, lpN * 8}, {&dOff, (size_t)B * 24}});
+    if (rc != KBEST_OK) return rc;
+    HIP_TRY(ctx, hipMemcpy(dOff.p, asgOff, (size_t)B * 8, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(dOff.as<int64_t>() + B, lpOff, (size_t)B * 8, hipMemcpyHostToDevice));
+    if (frameKey) HIP_TRY(ctx, hipMemcpy(dOff.as<int64_t>() + 2 * (size_t)B, frameKey, (size_t)B * 8, hipMemcpyHostToDevice));
+    rc = kbest_sample_assoc_batch_f64_dev(ctx, B, fb.maxRawRow, fb.maxCol, fb.d_nL(), fb.d_nM(), fb.d_cost(), fb.d_costOff(), condition,
+                                          nSample, seed, sampleBase, frameKey ? dOff.as<uint64_t>() + 2 * (size_t)B : nullptr,
+                                          dAsg.as<int32_t>(), dOff.as<int64_t>(), dLp.as<double>(), dOff.as<int64_t>() + B,
+                                          dPerm.as<double>(), nullptr);
+    if (rc != KBEST_OK) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    // every frame's own draws only: what lies between them in the caller's buffers is the caller's
+    std::vector<int32_t> hAsg(asgN);
+    std::vector<double> hLp(lpN);
+    HIP_TRY(ctx, hipMemcpy(hAsg.data(), dAsg.p, asgN * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(hLp.data(), dLp.p, lpN * 8, hipMemcpyDeviceToHost));
+    for (int b = 0; b < B; b++) {
+        memcpy(assign + asgOff[b], hAsg.data() + asgOff[b], (size_t)nSample * (size_t)nM[b] * 4);
+        memcpy(logProb + lpOff[b], hLp.data() + lpOff[b], (size_t)nSample * 8);
+    }
     if (perm) HIP_TRY(ctx, hipMemcpy(perm, dPerm.p, (size_t)B * 8, hipMemcpyDeviceToHost));
     return KBEST_OK;
 }

@@ -557,6 +557,26 @@ struct PermPlan {
 PermPlan perm_plan(int maxRawRow, int maxCol, int ldsLimit, int ldsPerCU);
 hipError_t launch_kbest_perm(const PermParams &p, const PermPlan &pl, int grid, hipStream_t stream);
 
+// kbest_sample.hip: joint associations drawn from the exact posterior, on the forward layers of the permanent kernel (its plan)
+struct SampleParams {
+    const double *cost;        // packed column-major (nL + nM) x nM blocks
+    const long long *costOff;  // [B]
+    const int *nL, *nM;        // [B]
+    const u64 *frameKey;       // [B] or nullptr (frame b: b): words 2 and 3 of the generator's counter
+    int *assign;               // [nSample][nM] per frame at asgOff[b]: the raw row every column takes
+    const long long *asgOff;   // [B]
+    double *logProb;           // [nSample] per frame at lpOff[b]
+    const long long *lpOff;    // [B]
+    double *perm;              // [B] or nullptr: the permanent of the frame's toProbs matrix
+    double *work;              // work space: slotStride doubles per workgroup of the launch (modes 1, 2)
+    long long slotStride;
+    u64 seed;                  // the generator's key
+    u32 sampleBase;            // sample s of the launch is draw sampleBase + s of the frame
+    int nSample;
+    int B, maxRawRow, maxCol, condition;
+};
+hipError_t launch_kbest_sample(const SampleParams &p, const PermPlan &pl, int grid, hipStream_t stream);
+
 // kbest_lbp.hip: beliefProb, the association probabilities by loopy belief propagation on the assignment model (any frame size)
 struct LbpParams {
     const double *cost;        // packed column-major (nL + nM) x nM blocks

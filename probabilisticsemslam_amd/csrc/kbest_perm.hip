@@ -33,25 +33,12 @@
 #include <atomic>
 
 #include "kbest_engine.h"
+#include "kbest_perm_plan.h"
 #include "kbest_wave.h"
 
 namespace kb {
 
 namespace {
-
-constexpr double PM_GATE = 42.0;  // assignment.cpp:9
-
-// threads that accumulate the marginals of a frame of M columns: 4 subsets each, whole waves, at most the largest workgroup.
-// (The reduction over the workgroup costs 6 M DPP steps per thread and row whatever the thread has added up before, so fewer,
-//  busier threads do less work in all -- but a row is a chain of dependent LDS / L2 reads, and more waves hide it.  Measured in one
-//  run, 8 against 4 subsets per thread: profiles/permanent_spt_ab.json, NOTES.md section 13.  The rule is part of the result's
-//  bits: the order of the sums follows from it.)
-constexpr int PM_SPT = 4;
-__host__ __device__ inline int perm_threads(int M)
-{
-    const int t = (1 << M) / PM_SPT;
-    return t < 64 ? 64 : t > 1024 ? 1024 : t;
-}
 
 // fp64 sum over the 64 lanes in ONE fixed order; valid in lane 63 only.  All lanes must be active.
 __device__ __forceinline__ double wave_sum63_f64(double x)
@@ -63,29 +50,6 @@ __device__ __forceinline__ double wave_sum63_f64(double x)
     x = x + dpp_f64<0x142, 0xA>(x);  // row_bcast:15 -> rows 1,3
     x = x + dpp_f64<0x143, 0xC>(x);  // row_bcast:31 -> rows 2,3
     return x;
-}
-
-struct PermLds {  // byte offsets into the dynamic LDS
-    int red, colMin, waveMin, ctl, rawRow, mask, act, a, g, hist, total;
-};
-
-__host__ __device__ inline PermLds perm_lds(int mode, int maxRawRow, int maxCol)
-{
-    PermLds l;
-    int o = 0;
-    l.red = o;     o += 2 * 16 * 16 * 8;  // [2][wave][column]
-    l.colMin = o;  o += 16 * 8;
-    l.waveMin = o; o += 16 * 8;
-    l.ctl = o;     o += 16;               // double blockMin; int nKept; int nAct
-    const int rows2 = (2 * maxRawRow + 7) & ~7;
-    l.rawRow = o;  o += rows2;            // u16: raw row of every kept row
-    l.mask = o;    o += rows2;            // u16: non-zero columns of every kept row
-    l.act = o;     o += rows2;            // u16: kept index of every active (non-zero) row
-    l.a = o;       if (mode < 2) o += maxRawRow * maxCol * 8;
-    l.g = o;       if (mode < 2) o += (2 << maxCol) * 8;
-    l.hist = o;    if (mode < 1) o += (maxRawRow << maxCol) * 8;
-    l.total = (o + 15) & ~15;
-    return l;
 }
 
 // MODE 0: a, the F layers and the two G layers in LDS; 1: the F layers in the HBM work space; 2: everything there.

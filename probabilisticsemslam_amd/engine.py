@@ -53,6 +53,7 @@ C_ABI_SYMBOLS = (
     "kbest_last_route", "kbest_resolve_ties_dev", "kbest_multi_last_tie_flags", "kbest_reserve_exact",
     "kbest_set_reference_order", "kbest_permanent_probs_batch_f64", "kbest_permanent_probs_batch_f64_dev",
     "kbest_reserve_permanent", "kbest_set_permanent_work_cap", "kbest_last_permanent_grid",
+    "kbest_sample_assoc_batch_f64", "kbest_sample_assoc_batch_f64_dev", "kbest_reserve_sample",
     "kbest_belief_probs_batch_f64", "kbest_belief_probs_batch_f64_dev", "kbest_reserve_belief", "kbest_set_belief_lds_limit",
     "kbest_clustered_probs_batch_f64", "kbest_clustered_probs_batch_f64_dev", "kbest_reserve_clustered",
     "kbest_set_clustered_slot_cap", "kbest_set_clustered_work_cap", "kbest_last_clustered_grid",
@@ -162,6 +163,12 @@ def load_library():
         lib.kbest_reserve_permanent.argtypes = [vp, C.c_int, C.c_int, C.c_int]
         lib.kbest_set_permanent_work_cap.argtypes = [vp, C.c_size_t]
         lib.kbest_last_permanent_grid.argtypes = [vp]
+    if hasattr(lib, "kbest_sample_assoc_batch_f64"):
+        lib.kbest_sample_assoc_batch_f64.argtypes = [vp, C.c_int, i32p, i32p, dp, i64p, C.c_int, C.c_int, C.c_uint64, C.c_uint32, i64p,
+                                                     i32p, i64p, dp, i64p, dp]
+        lib.kbest_sample_assoc_batch_f64_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int, i32p, i32p, dp, i64p, C.c_int, C.c_int,
+                                                         C.c_uint64, C.c_uint32, i64p, i32p, i64p, dp, i64p, dp, vp]
+        lib.kbest_reserve_sample.argtypes = [vp, C.c_int, C.c_int, C.c_int]
     if hasattr(lib, "kbest_belief_probs_batch_f64"):
         lib.kbest_belief_probs_batch_f64.argtypes = [vp, C.c_int, i32p, i32p, dp, i64p, C.c_int, C.c_double, C.c_int, dp, i64p, i32p, dp]
         lib.kbest_belief_probs_batch_f64_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int, i32p, i32p, dp, i64p, C.c_int, C.c_double,
@@ -420,6 +427,29 @@ class KBestEngine:
     def last_permanent_grid(self):
         """Diagnostic (kbest_last_permanent_grid): workgroups -- frames in flight -- of this context's last permanent launch."""
         return int(self.lib.kbest_last_permanent_grid(self.ctx))
+
+    def sample_assoc(self, costs, nL, nM, n_sample, seed=0, condition=False, frame_key=None, sample_base=0):
+        """Joint associations drawn from the exact posterior, nM <= 16 (kbest_sample.hip): n_sample independent draws per frame.
+        Packing and condition as permanent_probs().  frame_key: one uint64 per frame (None: the frame's index) -- with it a frame's
+        draws do not depend on the batch; sample_base: the index of the first draw.  Returns (list of int32 [n_sample, nM] arrays:
+        the raw row of the frame's block every measurement takes, a row >= nL is a miss; list of logProb [n_sample] arrays; perm[B]).
+        A frame whose permanent is 0 has assign -1 and logProb NaN."""
+        nL, nM, B, flat, costOff, _, _, _ = _pack_frames(costs, nL, nM, "sample_assoc")
+        n_sample = int(n_sample)
+        asgOff = np.zeros(B, np.int64)
+        asgOff[1:] = np.cumsum(nM.astype(np.int64) * n_sample)[:-1]
+        lpOff = np.arange(B, dtype=np.int64) * n_sample
+        assign = np.zeros(int(nM.astype(np.int64).sum()) * max(n_sample, 0), np.int32)
+        logp = np.zeros(B * max(n_sample, 0), np.float64)
+        perm = np.zeros(B, np.float64)
+        key = None if frame_key is None else np.ascontiguousarray(frame_key, dtype=np.uint64)
+        if key is not None and key.shape != (B,):
+            raise KBestError("sample_assoc: frame_key must hold one key per frame")
+        self._check(self.lib.kbest_sample_assoc_batch_f64(self.ctx, B, _ptr(nL), _ptr(nM), _ptr(flat), _ptr(costOff), int(bool(condition)),
+                                                          n_sample, int(seed), int(sample_base), _ptr(key), _ptr(assign), _ptr(asgOff),
+                                                          _ptr(logp), _ptr(lpOff), _ptr(perm)))
+        return ([assign[asgOff[b]: asgOff[b] + n_sample * int(nM[b])].reshape(n_sample, int(nM[b])) for b in range(B)],
+                [logp[lpOff[b]: lpOff[b] + n_sample] for b in range(B)], perm)
 
     def belief_probs(self, costs, nL, nM, condition=False, tol=1e-12, max_iter=10000):
         """Batched beliefProb (kbest_lbp.hip): the association probabilities by loopy belief propagation, nM <= 128 and
@@ -732,6 +762,21 @@ class KBestEngine:
                                                                  _dptr(d_costOff), int(bool(condition)), _dptr(d_probs), _dptr(d_probOff),
                                                                  _dptr(d_perm), _stream(stream)))
 
+    def reserve_sample(self, B, maxRawRow, maxCol):
+        self._check(self.lib.kbest_reserve_sample(self.ctx, B, maxRawRow, maxCol))
+
+    def sample_assoc_dev(self, B, maxRawRow, maxCol, d_nL, d_nM, d_cost, d_costOff, n_sample, d_assign, d_asgOff, d_logProb, d_lpOff,
+                         d_perm=None, seed=0, sample_base=0, d_frameKey=None, condition=False, stream=None, reserve=True):
+        """kbest_sample_assoc_batch_f64_dev on torch CUDA tensors, asynchronous on `stream` (a raw hipStream_t integer): one
+        launch.  d_frameKey: int64 / uint64 [B] or None.  The work space is sized here (a no-op once it is large enough): the C entry
+        never allocates.  reserve=False: the caller has called reserve_sample."""
+        if reserve:
+            self.reserve_sample(B, maxRawRow, maxCol)
+        self._check(self.lib.kbest_sample_assoc_batch_f64_dev(self.ctx, B, maxRawRow, maxCol, _dptr(d_nL), _dptr(d_nM), _dptr(d_cost),
+                                                              _dptr(d_costOff), int(bool(condition)), int(n_sample), int(seed),
+                                                              int(sample_base), _dptr(d_frameKey), _dptr(d_assign), _dptr(d_asgOff),
+                                                              _dptr(d_logProb), _dptr(d_lpOff), _dptr(d_perm), _stream(stream)))
+
     def reserve_belief(self, B, maxRawRow, maxCol):
         self._check(self.lib.kbest_reserve_belief(self.ctx, B, maxRawRow, maxCol))
 
@@ -911,6 +956,16 @@ def permanentProb(costMatrix, nL, nM, permOpt=1):
     if permOpt not in (0, 1, 2):
         raise RuntimeError("Unknown permanent option passed!")
     out, _ = _engine().permanent_probs([costMatrix], [nL], [nM])
+    return out[0]
+
+
+def sampleAssoc(costMatrix, nL, nM, nSample, seed=0):
+    """Not in the reference: nSample joint associations drawn from the exact posterior permanentProb gives the marginals of
+    (frame key 0).  Returns int32 [nSample][nM]: the row every measurement takes (a row >= nL: unassigned); raises RuntimeError
+    when the frame has no consistent association."""
+    out, _, perm = _engine().sample_assoc([costMatrix], [nL], [nM], nSample, seed=seed, frame_key=[0])
+    if not perm[0] > 0.0:
+        raise RuntimeError("sampleAssoc: the frame has no consistent association (permanent 0)")
     return out[0]
 
 
