@@ -34,6 +34,8 @@
  *   kbest_hybrid_frontier_probs_batch_f64 / kbest_frontier_probs_f64_dev
  *   kbest_hybrid_frontier_probs_batch_f64_dev / kbest_reserve_hybrid_dev
  *        the exact association probabilities by gated clusters, for frames of up to 128 measurements (not in the reference)
+ *   kbest_clustered_sample_assoc_batch_f64 / kbest_clustered_sample_assoc_batch_f64_dev
+ *        joint associations drawn from the exact posterior of such frames, one walk per cluster (not in the reference)
  *
  * Conventions kept from the reference: cost matrices are column-major
  * C[row + col*numRow] with numRow >= numCol (shortestPathCPP.hpp:185-190);
@@ -517,6 +519,59 @@ int kbest_set_clustered_slot_cap(kbest_ctx *ctx, size_t bytes);
 int kbest_set_clustered_work_cap(kbest_ctx *ctx, size_t bytes);
 /* Diagnostic, for tests: workgroups -- frames in flight -- of the context's last clustered launch (-1: null context). */
 int kbest_last_clustered_grid(kbest_ctx *ctx);
+
+/*
+ * Joint associations DRAWN from the exact posterior by gated clusters (kbest_cluster_sample.hip; not in the reference): what
+ * kbest_sample_assoc_batch_f64 does, for the frames kbest_clustered_probs_batch_f64 takes -- up to KBEST_CLUSTER_MAX_COLS
+ * measurements and KBEST_MAX_DIM_WIDE rows, clusters of at most KBEST_CLUSTER_MAX_SIZE measurements.  The posterior of a gated frame
+ * is the product of its clusters' posteriors: one backward walk per cluster on the cluster's own forward sums F_k, the joints
+ * concatenated, is an exact, independent draw of the whole frame, with probability (product of its toProbs entries) / (product of
+ * the Z_k).  Frames, layout, conditioning, clusters, their order (by label) and the refusals of kbest_clustered_probs_batch_f64;
+ * seed, sampleBase, frameKey, assign, asgOff, logProb and lpOff of kbest_sample_assoc_batch_f64.  Outputs per frame b:
+ *   assign   int32 [nSample][nM] at asgOff[b] (in int32s): assign[s][c] is the RAW row of the caller's block that measurement c
+ *            takes in draw s, in the caller's numbering before any conditioning; a miss is the measurement's own row >= nL, it is
+ *            not folded into nL.
+ *   logProb  double [nSample] at lpOff[b] (in doubles): sum_k (log(product of the entries chosen in cluster k) - log Z_k), one
+ *            term per cluster, added left to right in cluster order starting from 0.0 (no product over the whole frame is formed:
+ *            that of 128 gated entries leaves the doubles).
+ *   logPerm, info, maxCluster (each may be NULL): those of kbest_clustered_probs_batch_f64, logPerm and maxCluster with its bits.
+ * info = -2 (a cluster of more than KBEST_CLUSTER_MAX_SIZE measurements) and info = -3 (layers beyond the slot cap) refuse the FRAME,
+ * not the call: every assign -1, every logProb NaN, logPerm NaN.  An infeasible frame (some Z_k = 0): every assign -1, every logProb
+ * NaN, logPerm = -inf, info = 0.
+ * The uniforms -- this definition is the contract; a caller can reproduce every draw from it: for a row of a cluster, u(s, i) takes
+ * i as that row's index among the frame's ACTIVE rows (the rows that are not all zero after conditioning and toProbs, in order, i
+ * counted from 0 over the WHOLE frame, not inside the cluster); for draw s of the launch,
+ *   Philox4x32-10 with key (seed low word, seed high word) and counter (sampleBase + s, i >> 1, frameKey[b] low word,
+ *   frameKey[b] high word); output words 0, 1 serve even i and words 2, 3 serve odd i;
+ *   u = (((hi << 32) | lo) >> 11) * 2^-53, lo the first and hi the second word of the pair.
+ * The walk of a cluster runs over the cluster's rows from the last to the first (ascending row order inside a cluster) with S = all
+ * measurements of the cluster: tot = F_k[i+1][S] (Z_k at the cluster's last row), T = u * tot, acc = F_k[i][S]; T < acc: the row
+ * takes nothing; else for the measurements c of S in ascending order with a non-zero entry: acc = acc + a[i][c] * F_k[i][S without
+ * c], and the first c with T < acc is taken (none, by rounding: the last c whose term was > 0).  The whole-frame sums factorise,
+ * F[i+1][S] = product over the clusters of F_k[.][S_k], so the ratio that decides row i in the whole-frame walk is the ratio inside
+ * its cluster: on a frame that kbest_sample_assoc_batch_f64 takes, the decisions are the same function of the same uniforms.
+ * (They are made on sums that differ in their last bits; a draw differs only where a uniform falls within those bits of a boundary.)
+ * A frame's outputs are a function of (seed, frame key, draw index, frame) alone: the same bits alone, anywhere in a batch, under any
+ * slot cap or work cap that still takes the frame, and for condition = 1 on the raw block against condition = 0 on its conditioned
+ * block.  sampleBase continues a sequence, as in kbest_sample_assoc_batch_f64.
+ * Limits: those of the clustered entry, 1 <= nSample, sampleBase + nSample <= 2^32.  Host buffers; stages, reserves and runs the
+ * device entry below.
+ */
+int kbest_clustered_sample_assoc_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,
+                                           const int64_t *costOff, int condition, int nSample, uint64_t seed, uint32_t sampleBase,
+                                           const uint64_t *frameKey, int32_t *assign, const int64_t *asgOff, double *logProb,
+                                           const int64_t *lpOff, double *logPerm, int32_t *info, int32_t *maxCluster);
+/* The same on device buffers, asynchronous on `stream` (NULL: the context's): one launch, no allocation.  maxRawRow / maxCol as
+ * for the clustered entry (a frame beyond them gets info = -1 and nothing else of it is touched).  Needs
+ * kbest_reserve_clustered_sample first (KBEST_ERR_NOT_RESERVED): the work space, its size, kbest_set_clustered_slot_cap and
+ * kbest_set_clustered_work_cap are the clustered entry's, and kbest_reserve_clustered_sample reserves exactly what
+ * kbest_reserve_clustered does. */
+int kbest_clustered_sample_assoc_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, const int32_t *d_nL,
+                                               const int32_t *d_nM, const double *d_cost, const int64_t *d_costOff, int condition,
+                                               int nSample, uint64_t seed, uint32_t sampleBase, const uint64_t *d_frameKey,
+                                               int32_t *d_assign, const int64_t *d_asgOff, double *d_logProb, const int64_t *d_lpOff,
+                                               double *d_logPerm, int32_t *d_info, int32_t *d_maxCluster, void *stream);
+int kbest_reserve_clustered_sample(kbest_ctx *ctx, int B, int maxRawRow, int maxCol);
 
 /*
  * Hybrid association probabilities (not in the reference): every gated frame of up to KBEST_CLUSTER_MAX_COLS measurements is

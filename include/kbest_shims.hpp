@@ -138,6 +138,14 @@ std::vector<std::vector<double>> beliefProb(const std::vector<double> &costMatri
 // std::runtime_error naming the largest cluster when the frame is refused; an infeasible frame comes back as all zeros.
 std::vector<std::vector<double>> clusterProb(const std::vector<double> &costMatrix, size_t nL, size_t nM);
 
+// Not in the reference: sampleAssoc for the frames clusterProb takes (kbest_clustered_sample_assoc_batch_f64: up to 128
+// measurements and 1 024 rows, clusters of at most 16 measurements; frame key 0, draws 0 .. nSample-1 of `seed`): [nSample][nM],
+// entry [s][c] the row of costMatrix that measurement c takes in draw s (a row >= nL: unassigned).  On a frame sampleAssoc takes the
+// draws are sampleAssoc's.  Throws std::runtime_error naming the largest cluster when the frame is refused, and when the frame has no
+// consistent association.
+std::vector<std::vector<int>> clusterSampleAssoc(const std::vector<double> &costMatrix, size_t nL, size_t nM, size_t nSample,
+                                                 uint64_t seed);
+
 // Not in the reference: the hybrid association probabilities (kbest_hybrid_probs_batch_f64), [nM][nL+1] like assignmentProb, for
 // frames of up to 128 measurements and 1 024 rows: exact on every cluster of at most 16 measurements, assignmentProb(k) on the
 // larger ones alone.  Throws std::runtime_error only when the frame is refused (method -1: not the reference's layout of miss

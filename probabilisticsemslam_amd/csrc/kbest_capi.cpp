@@ -3264,6 +3264,127 @@ extern "C" int kbest_clustered_probs_batch_f64(kbest_ctx *ctx, int B, const int3
     return KBEST_OK;
 }
 
+// ---- draws from the exact posterior by gated clusters (kbest_cluster_sample.hip): the clustered kernel's plan, work space, caps
+//      and frames in flight ------------------------------------------------------------------------------------------------------
+extern "C" int kbest_reserve_clustered_sample(kbest_ctx *ctx, int B, int maxRawRow, int maxCol)
+{
+    return kbest_reserve_clustered(ctx, B, maxRawRow, maxCol);
+}
+
+extern "C" int kbest_clustered_sample_assoc_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, const int32_t *d_nL,
+                                                          const int32_t *d_nM, const double *d_cost, const int64_t *d_costOff,
+                                                          int condition, int nSample, uint64_t seed, uint32_t sampleBase,
+                                                          const uint64_t *d_frameKey, int32_t *d_assign, const int64_t *d_asgOff,
+                                                          double *d_logProb, const int64_t *d_lpOff, double *d_logPerm,
+                                                          int32_t *d_info, int32_t *d_maxCluster, void *stream)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    const char *who = "kbest_clustered_sample_assoc_batch_f64_dev";
+    int rc = check_frame_shape(ctx, who, B, maxRawRow, maxCol, KBEST_CLUSTER_MAX_COLS, CLUSTER_COLS_TEXT);
+    if (rc != KBEST_OK) return rc;
+    if (!d_nL || !d_nM || !d_cost || !d_costOff || !d_assign || !d_asgOff || !d_logProb || !d_lpOff || nSample < 1 ||
+        (uint64_t)sampleBase + (uint64_t)nSample > ((uint64_t)1 << 32))
+        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_clustered_sample_assoc_batch_f64_dev: bad argument");
+    if (B == 0) return KBEST_OK;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    kb::ClusterPlan pl;
+    rc = cluster_plan_of(ctx, maxRawRow, maxCol, pl, who);
+    if (rc != KBEST_OK) return rc;
+    if (ctx->clusBuf.bytes < (size_t)pl.slotDoubles * 8)  // asynchronous entry: never allocates
+        return fail(ctx, KBEST_ERR_NOT_RESERVED, "kbest_clustered_sample_assoc_batch_f64_dev: call kbest_reserve_clustered_sample first");
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = order_behind_last(ctx, s);  // (one work space per context)
+    if (rc != KBEST_OK) return rc;
+    const Launched mark{ctx, s};
+    kb::ClusterSampleParams sp;
+    sp.cost = d_cost;
+    sp.costOff = reinterpret_cast<const long long *>(d_costOff);
+    sp.nL = d_nL;
+    sp.nM = d_nM;
+    sp.frameKey = reinterpret_cast<const kb::u64 *>(d_frameKey);
+    sp.assign = d_assign;
+    sp.asgOff = reinterpret_cast<const long long *>(d_asgOff);
+    sp.logProb = d_logProb;
+    sp.lpOff = reinterpret_cast<const long long *>(d_lpOff);
+    sp.logPerm = d_logPerm;
+    sp.info = d_info;
+    sp.maxCluster = d_maxCluster;
+    sp.work = static_cast<double *>(ctx->clusBuf.p);
+    sp.slotStride = pl.slotDoubles;
+    sp.slotBytes = pl.slotBytes;
+    sp.seed = seed;
+    sp.sampleBase = sampleBase;
+    sp.nSample = nSample;
+    sp.arenaBytes = pl.arena;
+    sp.B = B;
+    sp.maxRawRow = maxRawRow;
+    sp.maxCol = maxCol;
+    sp.condition = condition ? 1 : 0;
+    // (frames in flight as the clustered entry counts them: the same slots of the same work space)
+    ctx->clusLastGrid = frames_in_flight(ctx, CLUSTER_WAVES_PER_CU, pl.threads, pl.lds, pl.slotDoubles, B,
+                                         ctx->clusBuf.bytes < ctx->clusWorkCap ? ctx->clusBuf.bytes : ctx->clusWorkCap);
+    const hipError_t e = kb::launch_kbest_cluster_sample(sp, pl, ctx->clusLastGrid, s);
+    if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "clustered sampling kernel launch", e);
+    return KBEST_OK;
+}
+
+extern "C" int kbest_clustered_sample_assoc_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,
+                                                      const int64_t *costOff, int condition, int nSample, uint64_t seed,
+                                                      uint32_t sampleBase, const uint64_t *frameKey, int32_t *assign,
+                                                      const int64_t *asgOff, double *logProb, const int64_t *lpOff, double *logPerm,
+                                                      int32_t *info, int32_t *maxCluster)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    if (B < 0 || nSample < 1 || (B > 0 && (!nL || !nM || !cost || !costOff || !assign || !asgOff || !logProb || !lpOff)))
+        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_clustered_sample_assoc_batch_f64: bad argument");
+    if (B == 0) return KBEST_OK;
+    const char *who = "kbest_clustered_sample_assoc_batch_f64";
+    FrameBatch fb;
+    int rc = fb.scan(ctx, who, B, nL, nM, costOff, nullptr);
+    if (rc != KBEST_OK) return rc;
+    rc = check_frame_shape(ctx, who, B, fb.maxRawRow, fb.maxCol, KBEST_CLUSTER_MAX_COLS, CLUSTER_COLS_TEXT);
+    if (rc != KBEST_OK) return rc;
+    size_t asgN = 0, lpN = 0;  // int32s / doubles up to the end of the last frame's draws
+    for (int b = 0; b < B; b++) {
+        if (asgOff[b] < 0 || lpOff[b] < 0) return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_clustered_sample_assoc_batch_f64: a negative offset");
+        asgN = std::max(asgN, (size_t)asgOff[b] + (size_t)nSample * (size_t)nM[b]);
+        lpN = std::max(lpN, (size_t)lpOff[b] + (size_t)nSample);
+    }
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = kbest_reserve_clustered_sample(ctx, B, fb.maxRawRow, fb.maxCol);
+    if (rc != KBEST_OK) return rc;
+    DevBuf dOut, dAsg, dLp, dOff;  // out: logPerm[B] (double) | info[B] | maxCluster[B] (int32); off: asgOff[B] | lpOff[B] | frameKey[B]
+    rc = fb.upload(ctx, who, cost, {{&dOut, (size_t)B * 16}, {&dAsg, asgN * 4}, {&dLp, lpN * 8}, {&dOff, (size_t)B * 24}});
+    if (rc != KBEST_OK) return rc;
+    HIP_TRY(ctx, hipMemcpy(dOff.p, asgOff, (size_t)B * 8, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(dOff.as<int64_t>() + B, lpOff, (size_t)B * 8, hipMemcpyHostToDevice));
+    if (frameKey) HIP_TRY(ctx, hipMemcpy(dOff.as<int64_t>() + 2 * (size_t)B, frameKey, (size_t)B * 8, hipMemcpyHostToDevice));
+    unsigned char *o8 = dOut.as<unsigned char>();
+    rc = kbest_clustered_sample_assoc_batch_f64_dev(ctx, B, fb.maxRawRow, fb.maxCol, fb.d_nL(), fb.d_nM(), fb.d_cost(), fb.d_costOff(),
+                                                    condition, nSample, seed, sampleBase,
+                                                    frameKey ? dOff.as<uint64_t>() + 2 * (size_t)B : nullptr, dAsg.as<int32_t>(),
+                                                    dOff.as<int64_t>(), dLp.as<double>(), dOff.as<int64_t>() + B,
+                                                    reinterpret_cast<double *>(o8), reinterpret_cast<int32_t *>(o8 + (size_t)B * 8),
+                                                    reinterpret_cast<int32_t *>(o8 + (size_t)B * 12), nullptr);
+    if (rc != KBEST_OK) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    // every frame's own draws only: what lies between them in the caller's buffers is the caller's
+    std::vector<int32_t> hAsg(asgN);
+    std::vector<double> hLp(lpN);
+    HIP_TRY(ctx, hipMemcpy(hAsg.data(), dAsg.p, asgN * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(hLp.data(), dLp.p, lpN * 8, hipMemcpyDeviceToHost));
+    for (int b = 0; b < B; b++) {
+        memcpy(assign + asgOff[b], hAsg.data() + asgOff[b], (size_t)nSample * (size_t)nM[b] * 4);
+        memcpy(logProb + lpOff[b], hLp.data() + lpOff[b], (size_t)nSample * 8);
+    }
+    if (logPerm) HIP_TRY(ctx, hipMemcpy(logPerm, o8, (size_t)B * 8, hipMemcpyDeviceToHost));
+    if (info) HIP_TRY(ctx, hipMemcpy(info, o8 + (size_t)B * 8, (size_t)B * 4, hipMemcpyDeviceToHost));
+    if (maxCluster) HIP_TRY(ctx, hipMemcpy(maxCluster, o8 + (size_t)B * 12, (size_t)B * 4, hipMemcpyDeviceToHost));
+    return KBEST_OK;
+}
+
 // tie (optional): [B] KBEST_TIE_* per frame.  tieExtra > 0: the general pipeline enumerates k + tieExtra solutions and weighs the
 // first k of them in the canonical order -- how a frame whose k-th and (k+1)-th gains are equal gets the one answer (kbest_ties.h).
 // tieExtra < 0: the general pipeline with the reference-order kernel as its enumeration, whatever the context says -- how such a frame

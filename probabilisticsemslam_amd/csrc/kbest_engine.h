@@ -634,6 +634,30 @@ hipError_t launch_kbest_cluster(const ClusterParams &p, const ClusterPlan &pl, i
 hipError_t launch_kbest_cluster_partial(const ClusterParams &p, const ClusterOpenParams &q, const ClusterPlan &pl, int grid,
                                         hipStream_t stream);
 
+// kbest_cluster_sample.hip: joint associations drawn from the exact posterior of a gated frame, one walk per cluster (the plan, the
+// work space and the refusals of kbest_cluster.hip, the generator and the walk of kbest_sample.hip)
+struct ClusterSampleParams {
+    const double *cost;        // packed column-major (nL + nM) x nM blocks
+    const long long *costOff;  // [B]
+    const int *nL, *nM;        // [B]
+    const u64 *frameKey;       // [B] or nullptr (frame b: b): words 2 and 3 of the generator's counter
+    int *assign;               // [nSample][nM] per frame at asgOff[b]: the raw row every column takes
+    const long long *asgOff;   // [B]
+    double *logProb;           // [nSample] per frame at lpOff[b]
+    const long long *lpOff;    // [B]
+    double *logPerm;           // [B] or nullptr, info, maxCluster: as ClusterParams
+    int *info;
+    int *maxCluster;
+    double *work;              // work space: slotStride doubles per workgroup of the launch
+    long long slotStride;      // maxRawRow * 16 doubles for a cluster's a, then slotBytes of layers
+    long long slotBytes;       // layers (R_k + 2) 2^m_k 8 bytes beyond it: the frame is refused (-3)
+    u64 seed;                  // the generator's key
+    u32 sampleBase;            // sample s of the launch is draw sampleBase + s of the frame
+    int nSample;
+    int arenaBytes, B, maxRawRow, maxCol, condition;
+};
+hipError_t launch_kbest_cluster_sample(const ClusterSampleParams &p, const ClusterPlan &pl, int grid, hipStream_t stream);
+
 // kbest_bigcluster.hip: one open cluster of up to 20 measurements over the whole chip, its layers in HBM (kbest_c.h, "Exact
 // association probabilities of clusters of 17 .. 20 measurements").  The clusters of a pack share every launch (grid.y).
 constexpr int KB_BIGCLUSTER_PACK = 32;

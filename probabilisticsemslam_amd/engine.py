@@ -57,6 +57,7 @@ C_ABI_SYMBOLS = (
     "kbest_belief_probs_batch_f64", "kbest_belief_probs_batch_f64_dev", "kbest_reserve_belief", "kbest_set_belief_lds_limit",
     "kbest_clustered_probs_batch_f64", "kbest_clustered_probs_batch_f64_dev", "kbest_reserve_clustered",
     "kbest_set_clustered_slot_cap", "kbest_set_clustered_work_cap", "kbest_last_clustered_grid",
+    "kbest_clustered_sample_assoc_batch_f64", "kbest_clustered_sample_assoc_batch_f64_dev", "kbest_reserve_clustered_sample",
     "kbest_clustered_partial_batch_f64_dev", "kbest_hybrid_probs_batch_f64",
     "kbest_reserve_bigcluster", "kbest_set_bigcluster_work_cap", "kbest_bigcluster_probs_f64_dev",
     "kbest_hybrid_exact_probs_batch_f64",
@@ -184,6 +185,12 @@ def load_library():
         lib.kbest_set_clustered_slot_cap.argtypes = [vp, C.c_size_t]
         lib.kbest_set_clustered_work_cap.argtypes = [vp, C.c_size_t]
         lib.kbest_last_clustered_grid.argtypes = [vp]
+    if hasattr(lib, "kbest_clustered_sample_assoc_batch_f64"):
+        lib.kbest_clustered_sample_assoc_batch_f64.argtypes = [vp, C.c_int, i32p, i32p, dp, i64p, C.c_int, C.c_int, C.c_uint64, C.c_uint32,
+                                                               i64p, i32p, i64p, dp, i64p, dp, i32p, i32p]
+        lib.kbest_clustered_sample_assoc_batch_f64_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int, i32p, i32p, dp, i64p, C.c_int, C.c_int,
+                                                                   C.c_uint64, C.c_uint32, i64p, i32p, i64p, dp, i64p, dp, i32p, i32p, vp]
+        lib.kbest_reserve_clustered_sample.argtypes = [vp, C.c_int, C.c_int, C.c_int]
     if hasattr(lib, "kbest_hybrid_probs_batch_f64"):
         lib.kbest_clustered_partial_batch_f64_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int, i32p, i32p, dp, i64p, C.c_int, C.c_int,
                                                               dp, i64p, dp, i32p, i32p, i32p, C.c_int, i32p, i32p, C.c_int, i32p,
@@ -487,6 +494,33 @@ class KBestEngine:
                                                              _ptr(info), _ptr(maxCluster), _ptr(lab), stride))
         out = _split_probs(probs, probOff, psizes, nL, nM)
         return (out, logPerm, info, maxCluster, lab) if labels else (out, logPerm, info, maxCluster)
+
+    def clustered_sample_assoc(self, costs, nL, nM, n_sample, seed=0, condition=False, frame_key=None, sample_base=0):
+        """Joint associations drawn from the exact posterior by gated clusters (kbest_cluster_sample.hip): sample_assoc() for the
+        frames clustered_probs() takes -- nM <= 128, nL + nM <= 1024, clusters of at most 16 measurements; on a frame sample_assoc()
+        takes, the same draws.  Packing, condition, frame_key and sample_base as sample_assoc().  Returns (list of int32
+        [n_sample, nM] arrays: the raw row of the frame's block every measurement takes, a row >= nL is a miss; list of logProb
+        [n_sample] arrays; logPerm[B], info[B], maxCluster[B] as clustered_probs()).  A refused (info -2 / -3) or infeasible
+        (info 0) frame has assign -1 and logProb NaN."""
+        nL, nM, B, flat, costOff, _, _, _ = _pack_frames(costs, nL, nM, "clustered_sample_assoc")
+        n_sample = int(n_sample)
+        asgOff = np.zeros(B, np.int64)
+        asgOff[1:] = np.cumsum(nM.astype(np.int64) * n_sample)[:-1]
+        lpOff = np.arange(B, dtype=np.int64) * n_sample
+        assign = np.zeros(int(nM.astype(np.int64).sum()) * max(n_sample, 0), np.int32)
+        logp = np.zeros(B * max(n_sample, 0), np.float64)
+        logPerm = np.zeros(B, np.float64)
+        info = np.zeros(B, np.int32)
+        maxCluster = np.zeros(B, np.int32)
+        key = None if frame_key is None else np.ascontiguousarray(frame_key, dtype=np.uint64)
+        if key is not None and key.shape != (B,):
+            raise KBestError("clustered_sample_assoc: frame_key must hold one key per frame")
+        self._check(self.lib.kbest_clustered_sample_assoc_batch_f64(self.ctx, B, _ptr(nL), _ptr(nM), _ptr(flat), _ptr(costOff),
+                                                                    int(bool(condition)), n_sample, int(seed), int(sample_base),
+                                                                    _ptr(key), _ptr(assign), _ptr(asgOff), _ptr(logp), _ptr(lpOff),
+                                                                    _ptr(logPerm), _ptr(info), _ptr(maxCluster)))
+        return ([assign[asgOff[b]: asgOff[b] + n_sample * int(nM[b])].reshape(n_sample, int(nM[b])) for b in range(B)],
+                [logp[lpOff[b]: lpOff[b] + n_sample] for b in range(B)], logPerm, info, maxCluster)
 
     def exact_or_belief_probs(self, costs, nL, nM, condition=False, tol=1e-12, max_iter=10000):
         """The exact probabilities wherever the gate leaves clusters of at most 16 measurements, belief propagation elsewhere:
@@ -808,6 +842,24 @@ class KBestEngine:
                                                                  _dptr(d_logPerm), _dptr(d_info), _dptr(d_maxCluster), _dptr(d_label),
                                                                  int(labelStride), _stream(stream)))
 
+    def reserve_clustered_sample(self, B, maxRawRow, maxCol):
+        self._check(self.lib.kbest_reserve_clustered_sample(self.ctx, B, maxRawRow, maxCol))
+
+    def clustered_sample_assoc_dev(self, B, maxRawRow, maxCol, d_nL, d_nM, d_cost, d_costOff, n_sample, d_assign, d_asgOff, d_logProb,
+                                   d_lpOff, d_logPerm=None, d_info=None, d_maxCluster=None, seed=0, sample_base=0, d_frameKey=None,
+                                   condition=False, stream=None, reserve=True):
+        """kbest_clustered_sample_assoc_batch_f64_dev on torch CUDA tensors, asynchronous on `stream` (a raw hipStream_t integer):
+        one launch.  d_frameKey: int64 / uint64 [B] or None.  The work space is sized here (a no-op once it is large enough): the C
+        entry never allocates.  reserve=False: the caller has called reserve_clustered_sample."""
+        if reserve:
+            self.reserve_clustered_sample(B, maxRawRow, maxCol)
+        self._check(self.lib.kbest_clustered_sample_assoc_batch_f64_dev(self.ctx, B, maxRawRow, maxCol, _dptr(d_nL), _dptr(d_nM),
+                                                                        _dptr(d_cost), _dptr(d_costOff), int(bool(condition)),
+                                                                        int(n_sample), int(seed), int(sample_base), _dptr(d_frameKey),
+                                                                        _dptr(d_assign), _dptr(d_asgOff), _dptr(d_logProb),
+                                                                        _dptr(d_lpOff), _dptr(d_logPerm), _dptr(d_info),
+                                                                        _dptr(d_maxCluster), _stream(stream)))
+
     def clustered_partial_dev(self, B, maxRawRow, maxCol, d_nL, d_nM, d_cost, d_costOff, d_probs, d_probOff, d_nOpen, d_openDesc,
                               descStride, d_openRows, rowStride, d_sub, max_exact=16, d_logPerm=None, d_info=None,
                               d_maxCluster=None, d_label=None, labelStride=0, condition=False, stream=None, reserve=True):
@@ -983,6 +1035,18 @@ def clusterProb(costMatrix, nL, nM):
     out, _, info, maxCluster = _engine().clustered_probs([costMatrix], [nL], [nM])
     if info[0] < 0:
         raise RuntimeError(f"clusterProb: frame refused (info {int(info[0])}): its largest cluster has {int(maxCluster[0])} measurements")
+    return out[0]
+
+
+def clusterSampleAssoc(costMatrix, nL, nM, nSample, seed=0):
+    """Not in the reference: sampleAssoc for the frames clusterProb takes (up to 128 measurements, clusters of at most 16; frame key
+    0).  Returns int32 [nSample][nM]: the row every measurement takes (a row >= nL: unassigned); raises RuntimeError naming the
+    largest cluster when the frame is refused, and when the frame has no consistent association."""
+    out, _, _, info, maxCluster = _engine().clustered_sample_assoc([costMatrix], [nL], [nM], nSample, seed=seed, frame_key=[0])
+    if info[0] < 0:
+        raise RuntimeError(f"clusterSampleAssoc: frame refused (info {int(info[0])}): its largest cluster has {int(maxCluster[0])} measurements")
+    if info[0] == 0:
+        raise RuntimeError("clusterSampleAssoc: the frame has no consistent association (some cluster's permanent is 0)")
     return out[0]
 
 
