@@ -20,7 +20,7 @@
  *   kbest_quadric_costs_f64 / kbest_quadric_assoc_probs_batch_f64
  *        batched form of  computeQuadricCostMatrix (assignment.cpp:705-722) and of the whole
  *        getAssignmentProbs chain behind it
- *   kbest_bb_match_batch_f64
+ *   kbest_bb_costs_f64 / kbest_bb_match_batch_f64
  *        batched form of  asgnBB (assignment.cpp:724-797; k = 1, maximize)
  *   kbest_permanent_probs_batch_f64 / kbest_permanent_probs_batch_f64_dev
  *        batched form of  permanentProb (assignment.h:13, assignment.cpp:145-290), exact for every permOpt
@@ -801,9 +801,21 @@ int kbest_quadric_assoc_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL
                                         const int64_t *probOff, int32_t *nf);
 
 /*
+ * Batched computeBBCostMatrix (assignment.cpp:777-797), the cost-only counterpart of kbest_quadric_costs_f64: boxes and
+ * gate as kbest_bb_match_batch_f64 takes them; cost receives the (nR+nL) x nL column-major profit blocks -- min of the two
+ * asymmetric IoUs (boundBox.h:62-75), -inf fill, the gate on each left box's own dummy row -- packed back to back.  Runs no
+ * solver.  Host buffers.
+ */
+int kbest_bb_costs_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nR, const double *boxL, const double *boxR,
+                       double gate, double *cost);
+
+/*
  * Batched asgnBB (assignment.h:21, assignment.cpp:724-797): stereo bounding-box matching.  Boxes are
  * (xmin, ymin, xmax, ymax, xOffset) -- boundBox.h:13-25 -- nL[b] left and nR[b] right boxes per frame, packed;
  * gate is NONASSIGN_BOUNDBOX.  assign[sum nL]: for every left box the index of its right box, or -1.
+ * Synchronous, so on exact ties it answers as the reference does ("Order of exact ties" (1)): a frame whose optimum is
+ * attained by more than one matching (duplicate detections, containment, an IoU equal to the gate) is solved again by the
+ * reference-order kernel; frames without a tie stay on the fast kernels.
  */
 int kbest_bb_match_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nR, const double *boxL,
                              const double *boxR, double gate, int32_t *assign);

@@ -4446,6 +4446,85 @@ int kbest_quadric_assoc_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL
     return weights_entry(ctx, B, nL, nM, nullptr, off.data(), k, probs, probOff, nf, true, &q, false);
 }
 
+}  // extern "C"
+
+// The frames of the two box entries on the device: shapes, offsets, boxes and the packed (nR + nL) x nL cost blocks that
+// bb_cost_kernel fills (computeBBCostMatrix, assignment.cpp:777-797).
+struct BoxBatch {
+    DevBuf dBL, dBR, dOL, dOR, dOC, dNL, dNRt, dNRow, dCost, dAsg;
+    kb::BoxParams bp;
+    long long sl = 0, sr = 0, sc = 0;  // left boxes, right boxes, cost entries of the whole batch
+    int maxRow = 1, maxCol = 1;
+
+    // uploads the frames and launches the cost kernel on the context's stream (B >= 1)
+    int build(kbest_ctx *ctx, const char *who, int B, const int32_t *nL, const int32_t *nR, const double *boxL, const double *boxR,
+              double gate)
+    {
+        std::vector<long long> offL(B), offR(B), costOff(B);
+        std::vector<int32_t> nRow(B);
+        for (int b = 0; b < B; b++) {
+            // (asgnBB returns an empty vector for a frame without left boxes and all -1 for one without right boxes,
+            //  assignment.cpp:730-732: both are legal frames, not errors)
+            if (nL[b] < 0 || nR[b] < 0) return fail(ctx, KBEST_ERR_BAD_ARG, (std::string(who) + ": need nL >= 0, nR >= 0").c_str());
+            offL[b] = sl; offR[b] = sr; costOff[b] = sc;
+            nRow[b] = nR[b] + nL[b];
+            sl += nL[b]; sr += nR[b]; sc += (long long)nRow[b] * nL[b];
+            if (nRow[b] > maxRow) maxRow = nRow[b];
+            if (nL[b] > maxCol) maxCol = nL[b];
+        }
+        if (maxRow > KBEST_MAX_DIM_WIDE) return fail(ctx, KBEST_ERR_UNSUPPORTED, "nL + nR > KBEST_MAX_DIM_WIDE");
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, dBL.alloc(ctx, (size_t)sl * 40));
+        HIP_TRY(ctx, dBR.alloc(ctx, (size_t)sr * 40));
+        HIP_TRY(ctx, dOL.alloc(ctx, (size_t)B * 8));
+        HIP_TRY(ctx, dOR.alloc(ctx, (size_t)B * 8));
+        HIP_TRY(ctx, dOC.alloc(ctx, (size_t)B * 8));
+        HIP_TRY(ctx, dNL.alloc(ctx, (size_t)B * 4));
+        HIP_TRY(ctx, dNRt.alloc(ctx, (size_t)B * 4));
+        HIP_TRY(ctx, dNRow.alloc(ctx, (size_t)B * 4));
+        HIP_TRY(ctx, dCost.alloc(ctx, (size_t)sc * 8));
+        HIP_TRY(ctx, dAsg.alloc(ctx, (size_t)sl * 4));
+        if (sl) HIP_TRY(ctx, hipMemcpy(dBL.p, boxL, (size_t)sl * 40, hipMemcpyHostToDevice));
+        if (sr) HIP_TRY(ctx, hipMemcpy(dBR.p, boxR, (size_t)sr * 40, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(dOL.p, offL.data(), (size_t)B * 8, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(dOR.p, offR.data(), (size_t)B * 8, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(dOC.p, costOff.data(), (size_t)B * 8, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(dNL.p, nL, (size_t)B * 4, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(dNRt.p, nR, (size_t)B * 4, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(dNRow.p, nRow.data(), (size_t)B * 4, hipMemcpyHostToDevice));
+        bp.nL = dNL.as<int>();
+        bp.nR = dNRt.as<int>();
+        bp.offL = dOL.as<long long>();
+        bp.offR = dOR.as<long long>();
+        bp.boxL = dBL.as<double>();
+        bp.boxR = dBR.as<double>();
+        bp.gate = gate;
+        bp.cost = dCost.as<double>();
+        bp.costOff = dOC.as<long long>();
+        bp.assign = dAsg.as<int>();
+        hipError_t e = kb::launch_bb_costs(bp, B, ctx->stream);  // computeBBCostMatrix, assignment.cpp:777-797
+        if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "bounding-box cost kernel launch", e);
+        return KBEST_OK;
+    }
+};
+
+extern "C" {
+
+int kbest_bb_costs_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nR, const double *boxL, const double *boxR,
+                       double gate, double *cost)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    if (B < 0 || !nL || !nR || !boxL || !boxR || !cost)
+        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_bb_costs_f64: bad argument");
+    if (B == 0) return KBEST_OK;
+    BoxBatch bb;
+    const int rc = bb.build(ctx, "kbest_bb_costs_f64", B, nL, nR, boxL, boxR, gate);
+    if (rc != KBEST_OK) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (bb.sc) HIP_TRY(ctx, hipMemcpy(cost, bb.dCost.p, (size_t)bb.sc * 8, hipMemcpyDeviceToHost));
+    return KBEST_OK;
+}
+
 int kbest_bb_match_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nR, const double *boxL,
                              const double *boxR, double gate, int32_t *assign)
 {
@@ -4453,69 +4532,37 @@ int kbest_bb_match_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int
     if (B < 0 || !nL || !nR || !boxL || !boxR || !assign)
         return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_bb_match_batch_f64: bad argument");
     if (B == 0) return KBEST_OK;
-    std::vector<long long> offL(B), offR(B), costOff(B);
-    std::vector<int32_t> nRow(B);
-    long long sl = 0, sr = 0, sc = 0;
-    int maxRow = 1, maxCol = 1;
-    for (int b = 0; b < B; b++) {
-        // (asgnBB returns an empty vector for a frame without left boxes and all -1 for one without right boxes,
-        //  assignment.cpp:730-732: both are legal frames, not errors)
-        if (nL[b] < 0 || nR[b] < 0) return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_bb_match_batch_f64: need nL >= 0, nR >= 0");
-        offL[b] = sl; offR[b] = sr; costOff[b] = sc;
-        nRow[b] = nR[b] + nL[b];
-        sl += nL[b]; sr += nR[b]; sc += (long long)nRow[b] * nL[b];
-        if (nRow[b] > maxRow) maxRow = nRow[b];
-        if (nL[b] > maxCol) maxCol = nL[b];
-    }
-    if (maxRow > KBEST_MAX_DIM_WIDE) return fail(ctx, KBEST_ERR_UNSUPPORTED, "nL + nR > KBEST_MAX_DIM_WIDE");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    DevBuf dBL, dBR, dOL, dOR, dOC, dNL, dNRt, dNRow, dCost, dR4C, dC4R, dGain, dNf, dAsg;
-    HIP_TRY(ctx, dBL.alloc(ctx, (size_t)sl * 40));
-    HIP_TRY(ctx, dBR.alloc(ctx, (size_t)sr * 40));
-    HIP_TRY(ctx, dOL.alloc(ctx, (size_t)B * 8));
-    HIP_TRY(ctx, dOR.alloc(ctx, (size_t)B * 8));
-    HIP_TRY(ctx, dOC.alloc(ctx, (size_t)B * 8));
-    HIP_TRY(ctx, dNL.alloc(ctx, (size_t)B * 4));
-    HIP_TRY(ctx, dNRt.alloc(ctx, (size_t)B * 4));
-    HIP_TRY(ctx, dNRow.alloc(ctx, (size_t)B * 4));
-    HIP_TRY(ctx, dCost.alloc(ctx, (size_t)sc * 8));
+    BoxBatch bb;
+    int rc = bb.build(ctx, "kbest_bb_match_batch_f64", B, nL, nR, boxL, boxR, gate);
+    if (rc != KBEST_OK) return rc;
+    const int maxRow = bb.maxRow, maxCol = bb.maxCol;
+    DevBuf dR4C, dC4R, dGain, dNf, dTie;
     HIP_TRY(ctx, dR4C.alloc(ctx, (size_t)B * maxCol * 4));
     HIP_TRY(ctx, dC4R.alloc(ctx, (size_t)B * maxRow * 4));
     HIP_TRY(ctx, dGain.alloc(ctx, (size_t)B * 8));
     HIP_TRY(ctx, dNf.alloc(ctx, (size_t)B * 4));
-    HIP_TRY(ctx, dAsg.alloc(ctx, (size_t)sl * 4));
-    HIP_TRY(ctx, hipMemcpy(dBL.p, boxL, (size_t)sl * 40, hipMemcpyHostToDevice));
-    if (sr) HIP_TRY(ctx, hipMemcpy(dBR.p, boxR, (size_t)sr * 40, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(dOL.p, offL.data(), (size_t)B * 8, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(dOR.p, offR.data(), (size_t)B * 8, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(dOC.p, costOff.data(), (size_t)B * 8, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(dNL.p, nL, (size_t)B * 4, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(dNRt.p, nR, (size_t)B * 4, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(dNRow.p, nRow.data(), (size_t)B * 4, hipMemcpyHostToDevice));
-    kb::BoxParams bp;
-    bp.nL = dNL.as<int>();
-    bp.nR = dNRt.as<int>();
-    bp.offL = dOL.as<long long>();
-    bp.offR = dOR.as<long long>();
-    bp.boxL = dBL.as<double>();
-    bp.boxR = dBR.as<double>();
-    bp.gate = gate;
-    bp.cost = dCost.as<double>();
-    bp.costOff = dOC.as<long long>();
-    bp.assign = dAsg.as<int>();
-    hipError_t e = kb::launch_bb_costs(bp, B, ctx->stream);  // computeBBCostMatrix, assignment.cpp:777-797
-    if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "bounding-box cost kernel launch", e);
+    HIP_TRY(ctx, dTie.alloc(ctx, (size_t)B * 4));
+    HIP_TRY(ctx, hipMemsetAsync(dTie.p, 0, (size_t)B * 4, ctx->stream));
     kbest_opts o;
     kbest_default_opts(&o);
     o.maximize = 1;  // assignment.cpp:749-750: kBest2D(k = 1, maximize = true)
-    int rc = batch_dev_impl(ctx, &o, B, maxRow, maxCol, dNRow.as<int32_t>(), dNL.as<int32_t>(), dCost.as<double>(),
-                            dOC.as<int64_t>(), 1, dR4C.as<int32_t>(), dC4R.as<int32_t>(), dGain.as<double>(),
-                            dNf.as<int32_t>(), nullptr, ctx->stream, true);
+    o.tie_flags = dTie.as<int32_t>();
+    rc = batch_dev_impl(ctx, &o, B, maxRow, maxCol, bb.dNRow.as<int32_t>(), bb.dNL.as<int32_t>(), bb.dCost.as<double>(),
+                        bb.dOC.as<int64_t>(), 1, dR4C.as<int32_t>(), dC4R.as<int32_t>(), dGain.as<double>(),
+                        dNf.as<int32_t>(), nullptr, ctx->stream, true);
     if (rc != KBEST_OK) return rc;
-    e = kb::launch_bb_assign(bp, dR4C.as<int>(), dNf.as<int>(), 1, maxCol, B, ctx->stream);
+    // A synchronous entry answers as the reference does (kbest_c.h, "Order of exact ties" (1)): duplicate detections and
+    // containment make equal IoU sums, and which optimal matching asgnBB then returns is the reference solver's order of
+    // operations.  The frames whose best two gains are equal (flagged by the launch above) run again on the
+    // reference-order kernel and their tables are replaced; frames without a tie keep the fast kernels' answer.
+    rc = kbest_resolve_ties_dev(ctx, &o, B, maxRow, maxCol, bb.dNRow.as<int32_t>(), bb.dNL.as<int32_t>(), bb.dCost.as<double>(),
+                                bb.dOC.as<int64_t>(), 1, dR4C.as<int32_t>(), dC4R.as<int32_t>(), dGain.as<double>(), dTie.as<int32_t>(),
+                                dNf.as<int32_t>(), ctx->stream);
+    if (rc != KBEST_OK) return rc;
+    hipError_t e = kb::launch_bb_assign(bb.bp, dR4C.as<int>(), dNf.as<int>(), 1, maxCol, B, ctx->stream);
     if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "bounding-box assign kernel launch", e);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipMemcpy(assign, dAsg.p, (size_t)sl * 4, hipMemcpyDeviceToHost));
+    if (bb.sl) HIP_TRY(ctx, hipMemcpy(assign, bb.dAsg.p, (size_t)bb.sl * 4, hipMemcpyDeviceToHost));
     return KBEST_OK;
 }
 

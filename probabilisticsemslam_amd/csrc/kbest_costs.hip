@@ -155,12 +155,13 @@ hipError_t launch_bb_assign(const BoxParams &p, const int *row4col, const int *n
 }
 
 
-// toProbs (assignment.h:19, assignment.cpp:527-542): m = min of the vector; x -> exp(m - x) where m + 42 > x, else 0.
+// toProbs (assignment.h:19, assignment.cpp:527-542): m = std::min_element of the vector; x -> exp(m - x) where m + 42 > x, else 0.
 // One workgroup; in place.  (The reference uses it on the permanent path only; it is elementwise, so this is all of it.)
 __global__ void __launch_bounds__(256) to_probs_kernel(double *x, long long n)
 {
     __shared__ double red[256];
     const int tid = threadIdx.x;
+    const double x0 = n > 0 ? x[0] : 0.0;  // (read before the barriers below: the second loop overwrites it)
     double m = c_inf();
     for (long long i = tid; i < n; i += 256) m = x[i] < m ? x[i] : m;  // std::min_element: first minimum, same value
     red[tid] = m;
@@ -169,7 +170,9 @@ __global__ void __launch_bounds__(256) to_probs_kernel(double *x, long long n)
         if (tid < w) red[tid] = red[tid + w] < red[tid] ? red[tid + w] : red[tid];
         __syncthreads();
     }
-    m = red[0];
+    // std::min_element starts from the FIRST element and moves on only where another compares less: a NaN there stays the
+    // "minimum" (nothing compares less than it), and every output is 0.  A NaN anywhere else never compares less and is skipped.
+    m = x0 != x0 ? x0 : red[0];
     const double GATE = 42.0;  // assignment.cpp:9
     for (long long i = tid; i < n; i += 256) {
         const double c = x[i];

@@ -64,6 +64,7 @@ C_ABI_SYMBOLS = (
     "kbest_reserve_frontier", "kbest_set_frontier_work_cap", "kbest_set_frontier_slot", "kbest_frontier_probs_f64_dev",
     "kbest_hybrid_frontier_probs_batch_f64",
     "kbest_reserve_hybrid_dev", "kbest_hybrid_frontier_probs_batch_f64_dev",
+    "kbest_bb_costs_f64",
 )
 KBEST_MULTI_STAMPS = 6
 KBEST_MULTI_BATCH, KBEST_MULTI_SUBTREE = 0, 1
@@ -122,6 +123,7 @@ def load_library():
     lib.kbest_quadric_assoc_probs_batch_f64.argtypes = [vp, C.c_int, i32p, i32p, dp, dp, dp, dp, C.c_double, C.c_int,
                                                         dp, i64p, i32p]
     lib.kbest_bb_match_batch_f64.argtypes = [vp, C.c_int, i32p, i32p, dp, dp, C.c_double, i32p]
+    lib.kbest_bb_costs_f64.argtypes = [vp, C.c_int, i32p, i32p, dp, dp, C.c_double, dp]
     lib.kbest_assign_batch_f64.argtypes = [vp, C.c_int, C.c_int, C.c_int, i32p, i32p, dp, i64p, C.c_int, C.c_int, C.c_int,
                                            i32p, i32p, dp, dp, dp, i32p]
     lib.kbest_to_probs_f64.argtypes = [vp, dp, C.c_int64]
@@ -694,12 +696,26 @@ class KBestEngine:
                                                                  _ptr(nf)))
         return [probs[poff[b]: poff[b] + psizes[b]].reshape(int(nM[b]), int(nL[b]) + 1) for b in range(len(frames))], nf
 
-    def bb_match(self, boxesL, boxesR, gate):
-        """Batched asgnBB.  boxesL / boxesR: lists of (n, 5) arrays (xmin, ymin, xmax, ymax, xOffset)."""
+    @staticmethod
+    def _pack_boxes(boxesL, boxesR):
+        """boxesL / boxesR: lists of (n, 5) arrays (xmin, ymin, xmax, ymax, xOffset)."""
         nL = np.array([len(b) for b in boxesL], np.int32)
         nR = np.array([len(b) for b in boxesR], np.int32)
-        bl = np.ascontiguousarray(np.concatenate([np.asarray(b, np.float64).reshape(-1, 5) for b in boxesL]))
-        br = np.ascontiguousarray(np.concatenate([np.asarray(b, np.float64).reshape(-1, 5) for b in boxesR] + [np.zeros((0, 5))]))
+        cat = lambda boxes: np.ascontiguousarray(np.concatenate([np.asarray(b, np.float64).reshape(-1, 5) for b in boxes] + [np.zeros((0, 5))]))  # noqa: E731
+        return nL, nR, cat(boxesL), cat(boxesR)
+
+    def bb_costs(self, boxesL, boxesR, gate):
+        """Batched computeBBCostMatrix.  Returns a list of (nR+nL)*nL column-major profit blocks."""
+        nL, nR, bl, br = self._pack_boxes(boxesL, boxesR)
+        sizes = (nR.astype(np.int64) + nL) * nL
+        out = np.zeros(int(sizes.sum()))
+        self._check(self.lib.kbest_bb_costs_f64(self.ctx, len(boxesL), _ptr(nL), _ptr(nR), _ptr(bl), _ptr(br), float(gate), _ptr(out)))
+        off = np.concatenate([[0], np.cumsum(sizes)])
+        return [out[off[b]: off[b + 1]] for b in range(len(boxesL))]
+
+    def bb_match(self, boxesL, boxesR, gate):
+        """Batched asgnBB.  boxesL / boxesR: lists of (n, 5) arrays (xmin, ymin, xmax, ymax, xOffset)."""
+        nL, nR, bl, br = self._pack_boxes(boxesL, boxesR)
         asg = np.full(int(nL.sum()), -9, np.int32)
         self._check(self.lib.kbest_bb_match_batch_f64(self.ctx, len(boxesL), _ptr(nL), _ptr(nR), _ptr(bl), _ptr(br),
                                                       float(gate), _ptr(asg)))

@@ -15,6 +15,7 @@ REF_SO = os.path.join(ORACLE_DIR, "_ref", "libref_kbest.so")
 REF_OFAST_SO = os.path.join(ORACLE_DIR, "_ref", "libref_kbest_ofast.so")
 REF_ASSIGN_SO = os.path.join(ORACLE_DIR, "_ref", "libref_assign.so")
 REF_ASSIGN_OFAST_SO = os.path.join(ORACLE_DIR, "_ref", "libref_assign_ofast.so")
+REF_BOXES_SO = os.path.join(ORACLE_DIR, "_ref", "libref_boxes.so")
 
 _dp = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
 _i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
@@ -121,6 +122,38 @@ def ref_assign(ofast: bool = False):
         lib.ref_minc_constant.argtypes = [C.c_int, C.c_int]
         _ref[path] = lib
     return _ref[path]
+
+
+def have_ref_boxes() -> bool:
+    return os.path.exists(REF_BOXES_SO)
+
+
+def ref_boxes():
+    """The reference's own stereo box matching (verbatim slices of boundBox.h / assignment.cpp, oracle/ref_boxes_shim.cpp)."""
+    if REF_BOXES_SO not in _ref:
+        lib = C.CDLL(REF_BOXES_SO)
+        lib.ref_bb_costs.restype = None
+        lib.ref_bb_costs.argtypes = [_dp, C.c_int, _dp, C.c_int, C.c_double, _dp]
+        lib.ref_asgn_bb.restype = None
+        lib.ref_asgn_bb.argtypes = [_dp, C.c_int, _dp, C.c_int, C.c_double, _i32p]
+        _ref[REF_BOXES_SO] = lib
+    return _ref[REF_BOXES_SO]
+
+
+def ref_bb_costs(bbL, bbR, gate):
+    """Reference computeBBCostMatrix: boxes (n, 5) as (xmin, ymin, xmax, ymax, xOffset) -> (nR + nL) * nL column-major."""
+    bbL = np.ascontiguousarray(bbL, dtype=np.float64).reshape(-1, 5); bbR = np.ascontiguousarray(bbR, dtype=np.float64).reshape(-1, 5)
+    out = np.empty((len(bbR) + len(bbL)) * len(bbL))
+    ref_boxes().ref_bb_costs(bbL.reshape(-1), len(bbL), bbR.reshape(-1), len(bbR), float(gate), out)
+    return out
+
+
+def ref_asgn_bb(bbL, bbR, gate):
+    """Reference asgnBB: for every left box the index of its right box, or -1."""
+    bbL = np.ascontiguousarray(bbL, dtype=np.float64).reshape(-1, 5); bbR = np.ascontiguousarray(bbR, dtype=np.float64).reshape(-1, 5)
+    asg = np.full(len(bbL), -1, np.int32)
+    ref_boxes().ref_asgn_bb(bbL.reshape(-1), len(bbL), bbR.reshape(-1), len(bbR), float(gate), asg)
+    return asg
 
 
 def ref_condition_costs(cost, nRows, nCols):
