@@ -716,6 +716,64 @@ int kbest_hybrid_frontier_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *
                                           double *probs, const int64_t *probOff, double *logPerm, int32_t *method, int32_t *nOpen,
                                           int32_t *nBig, int32_t *maxCluster, int32_t *nFrontier);
 /*
+ * Draws from the exact posterior of sparse clusters (kbest_frontier_sample.hip; not in the reference): whole joint associations of a
+ * cluster the frontier tier answers, drawn by a backward walk over the forward layers that tier keeps.  Nothing new is summed: the
+ * plan, the scaling a'[r][c] = exp(colMin_c - x[r][c]) and the forward sweep are kbest_frontier.hip's, and d_logZ[k], d_info[k]
+ * (1 / 0 / -3 / -4) and d_width[k] carry the bits of kbest_frontier_probs_f64_dev on the same cluster.  No backward sweep.
+ *
+ * The walk of one draw: S = empty after the last row; from the last step of the plan to the first, with row r of step i:
+ * T = S | closing_i, tot = F_{i+1}[S], Tt = u tot; where T holds no new column, acc = F_i[T] and Tt < acc leaves the row
+ * unassigned; else the columns c of T in the row, ascending, whose T \ c holds no new column: acc += a'[r][c] F_i[T \ c], the
+ * first c with Tt < acc is taken (if rounding leaves none: the last c whose term was > 0).  Rows that are all +inf are no steps.
+ * The uniform u is Philox4x32-10 with the key (seed low word, seed high word) and the counter
+ *     (sampleBase + s, 0x80000000 | (q >> 1), frameKey low word, frameKey high word);
+ * output words 0, 1 serve an even q, words 2, 3 an odd q, and u is built from the pair as in kbest_sample_assoc_batch_f64.
+ * q = d_rowKey[rowKeyOff[k] + r] is the caller's integer for row r of the sub-block (0 <= q).  Bit 31 of the second counter word
+ * keeps these uniforms disjoint from those of kbest_clustered_sample_assoc_batch_f64, whose second word is at most 511: no uniform
+ * is ever shared between a small cluster and a frontier cluster of one frame.
+ *
+ * kbest_frontier_sample_f64_dev: n clusters; m, nLk, subOff and d_sub as kbest_frontier_probs_f64_dev; frameKeyOfCluster[k] (host,
+ * may be NULL: 0) the frame key of the cluster's frame.  Out, on the device: d_assignLocal + asgOff[k]: int32 [nSample][m_k], the
+ * row of the sub-block every column takes; d_logTerm + ltOff[k]: double [nSample], sum_c (colMin_c - x[r_c][c]) - log Z'_k over the
+ * cluster's columns in ascending order -- every log from the cost itself, no log of a product.  d_info[k] = 0 (Z_k = 0): -1 and
+ * NaN; a refused cluster (-3, -4): neither is touched.  One workgroup takes a cluster at a time, the grid strides over the
+ * clusters, ONE launch per 64 clusters, no workgroup waits for another, no floating-point atomics: a cluster's outputs are a
+ * function of (cluster, row keys, seed, frame key, draw index) alone -- the same bits alone, anywhere in a batch and under any
+ * work cap.  Asynchronous on `stream` (NULL: the context's), allocates nothing: kbest_reserve_frontier_sample reserves exactly
+ * what kbest_reserve_frontier does, and without it the entry returns KBEST_ERR_NOT_RESERVED; kbest_set_frontier_work_cap and
+ * kbest_set_frontier_slot apply as they do to the marginal tier.  The argument checks of kbest_frontier_probs_f64_dev, plus
+ * 1 <= nSample and sampleBase + nSample <= 2^32: KBEST_ERR_BAD_ARG.
+ *
+ * kbest_hybrid_frontier_sample_assoc_batch_f64 (host buffers, synchronous): nSample whole hypotheses for every frame that
+ * kbest_hybrid_frontier_probs_batch_f64(k = 0, maxBig = 0) answers.  Frames, cost, costOff, condition, maxExact (0: 16) and
+ * maxWidth (0 .. 16) as there; nSample, seed, sampleBase, frameKey, assign, asgOff, logProb and lpOff as
+ * kbest_clustered_sample_assoc_batch_f64.  Every cluster of at most maxExact measurements is drawn by the walk of
+ * kbest_clustered_sample_assoc_batch_f64 with its contract unchanged (a second instantiation of its kernel that leaves the open
+ * clusters alone): the uniforms are indexed by the frame's ACTIVE rows and the rows of a cluster are walked from last to first; on
+ * a frame without an open cluster assign, logProb and logPerm carry the bits of kbest_clustered_sample_assoc_batch_f64.  Every
+ * open cluster goes through kbest_frontier_sample_f64_dev with q = the RAW row of the caller's block: a landmark row's entry in the
+ * partial kernel's row list, nL + c for the miss row of column c (in general: the row's own index in the block); its draws are
+ * mapped back to raw rows.  logProb[s] is built in two passes: the small clusters' terms in label order from 0.0, then the open
+ * clusters' terms in label order.  method[b], nOpen[b], nFrontier[b], maxCluster[b] (the last three may be NULL) and logPerm[b]
+ * (may be NULL): those of kbest_hybrid_frontier_probs_batch_f64(k = 0, maxBig = 0) on the same frames, bit for bit.  A frame with
+ * a cluster nobody takes (more than 64 measurements, -3, -4, or W > maxWidth): method -1, every assign -1, every logProb NaN; an
+ * infeasible frame: method -2, -1s and NaNs; the call itself succeeds in both cases.
+ * NOTE: the draws with condition = 1 on a raw block and with condition = 0 on its conditioned block are NOT equal for the open
+ * clusters, because q is a raw row and conditionCosts renumbers the rows it keeps.  Both are exact draws from the same posterior.
+ * The small clusters keep that equality (their uniforms are indexed by the active rows, which conditioning does not renumber).
+ */
+int kbest_hybrid_frontier_sample_assoc_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,
+                                                 const int64_t *costOff, int condition, int maxExact, int maxWidth, int nSample,
+                                                 uint64_t seed, uint32_t sampleBase, const uint64_t *frameKey, int32_t *assign,
+                                                 const int64_t *asgOff, double *logProb, const int64_t *lpOff, double *logPerm,
+                                                 int32_t *method, int32_t *nOpen, int32_t *nFrontier, int32_t *maxCluster);
+int kbest_reserve_frontier_sample(kbest_ctx *ctx, int n, int maxM, int maxRows);
+int kbest_frontier_sample_f64_dev(kbest_ctx *ctx, int n, const int32_t *m, const int32_t *nLk, const int64_t *subOff,
+                                  const double *d_sub, const int32_t *d_rowKey, const int64_t *rowKeyOff,
+                                  const uint64_t *frameKeyOfCluster, int nSample, uint64_t seed, uint32_t sampleBase,
+                                  int32_t *d_assignLocal, const int64_t *asgOff, double *d_logTerm, const int64_t *ltOff,
+                                  double *d_logZ, int32_t *d_info, int32_t *d_width, void *stream);
+/*
  * Asynchronous exact hybrid probabilities (kbest_hybrid.hip; not in the reference): the whole exact path of
  * kbest_hybrid_frontier_probs_batch_f64(k = 0, maxBig = 0) on buffers that already lie on the device, on ONE stream -- the partial
  * clustered kernel, a gather of the open clusters of all frames into one list (frame order, then label order: a prefix sum, no

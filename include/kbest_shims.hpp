@@ -146,6 +146,14 @@ std::vector<std::vector<double>> clusterProb(const std::vector<double> &costMatr
 std::vector<std::vector<int>> clusterSampleAssoc(const std::vector<double> &costMatrix, size_t nL, size_t nM, size_t nSample,
                                                  uint64_t seed);
 
+// Not in the reference: clusterSampleAssoc for the frames hybridFrontierProb(k = 0) takes
+// (kbest_hybrid_frontier_sample_assoc_batch_f64 with maxExact = 16, maxWidth = 16; frame key 0, draws 0 .. nSample-1 of `seed`):
+// clusters of up to 64 measurements whose rows, in the greedy order, keep at most 16 columns open are drawn too.  [nSample][nM] as
+// clusterSampleAssoc, and on a frame clusterSampleAssoc takes its draws.  Throws std::runtime_error naming the largest cluster when
+// the frame is refused, and when the frame has no consistent association.
+std::vector<std::vector<int>> hybridFrontierSampleAssoc(const std::vector<double> &costMatrix, size_t nL, size_t nM, size_t nSample,
+                                                        uint64_t seed);
+
 // Not in the reference: the hybrid association probabilities (kbest_hybrid_probs_batch_f64), [nM][nL+1] like assignmentProb, for
 // frames of up to 128 measurements and 1 024 rows: exact on every cluster of at most 16 measurements, assignmentProb(k) on the
 // larger ones alone.  Throws std::runtime_error only when the frame is refused (method -1: not the reference's layout of miss

@@ -3271,12 +3271,13 @@ extern "C" int kbest_reserve_clustered_sample(kbest_ctx *ctx, int B, int maxRawR
     return kbest_reserve_clustered(ctx, B, maxRawRow, maxCol);
 }
 
-extern "C" int kbest_clustered_sample_assoc_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, const int32_t *d_nL,
-                                                          const int32_t *d_nM, const double *d_cost, const int64_t *d_costOff,
-                                                          int condition, int nSample, uint64_t seed, uint32_t sampleBase,
-                                                          const uint64_t *d_frameKey, int32_t *d_assign, const int64_t *d_asgOff,
-                                                          double *d_logProb, const int64_t *d_lpOff, double *d_logPerm,
-                                                          int32_t *d_info, int32_t *d_maxCluster, void *stream)
+// partialMaxExact < 0: the plain kernel.  Else its second instantiation (kbest_cluster_sample_partial.hip): the clusters the partial
+// clustered kernel leaves open with maxExact = partialMaxExact are left open here.
+static int cluster_sample_dev(kbest_ctx *ctx, int partialMaxExact, int B, int maxRawRow, int maxCol, const int32_t *d_nL,
+                              const int32_t *d_nM, const double *d_cost, const int64_t *d_costOff, int condition, int nSample,
+                              uint64_t seed, uint32_t sampleBase, const uint64_t *d_frameKey, int32_t *d_assign,
+                              const int64_t *d_asgOff, double *d_logProb, const int64_t *d_lpOff, double *d_logPerm, int32_t *d_info,
+                              int32_t *d_maxCluster, void *stream)
 {
     if (!ctx) return KBEST_ERR_BAD_ARG;
     const char *who = "kbest_clustered_sample_assoc_batch_f64_dev";
@@ -3324,9 +3325,21 @@ extern "C" int kbest_clustered_sample_assoc_batch_f64_dev(kbest_ctx *ctx, int B,
     // (frames in flight as the clustered entry counts them: the same slots of the same work space)
     ctx->clusLastGrid = frames_in_flight(ctx, CLUSTER_WAVES_PER_CU, pl.threads, pl.lds, pl.slotDoubles, B,
                                          ctx->clusBuf.bytes < ctx->clusWorkCap ? ctx->clusBuf.bytes : ctx->clusWorkCap);
-    const hipError_t e = kb::launch_kbest_cluster_sample(sp, pl, ctx->clusLastGrid, s);
+    const hipError_t e = partialMaxExact < 0 ? kb::launch_kbest_cluster_sample(sp, pl, ctx->clusLastGrid, s)
+                                             : kb::launch_kbest_cluster_sample_partial(sp, partialMaxExact, pl, ctx->clusLastGrid, s);
     if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "clustered sampling kernel launch", e);
     return KBEST_OK;
+}
+
+extern "C" int kbest_clustered_sample_assoc_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, const int32_t *d_nL,
+                                                          const int32_t *d_nM, const double *d_cost, const int64_t *d_costOff,
+                                                          int condition, int nSample, uint64_t seed, uint32_t sampleBase,
+                                                          const uint64_t *d_frameKey, int32_t *d_assign, const int64_t *d_asgOff,
+                                                          double *d_logProb, const int64_t *d_lpOff, double *d_logPerm,
+                                                          int32_t *d_info, int32_t *d_maxCluster, void *stream)
+{
+    return cluster_sample_dev(ctx, -1, B, maxRawRow, maxCol, d_nL, d_nM, d_cost, d_costOff, condition, nSample, seed, sampleBase,
+                              d_frameKey, d_assign, d_asgOff, d_logProb, d_lpOff, d_logPerm, d_info, d_maxCluster, stream);
 }
 
 extern "C" int kbest_clustered_sample_assoc_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,
@@ -3931,6 +3944,68 @@ int kbest_frontier_probs_f64_dev(kbest_ctx *ctx, int n, const int32_t *m, const 
     return KBEST_OK;
 }
 
+// ---- draws from the exact posterior of open clusters (kbest_frontier_sample.hip): the frontier tier's slots, plans, caps and
+//      clusters in flight ------------------------------------------------------------------------------------------------------------
+int kbest_reserve_frontier_sample(kbest_ctx *ctx, int n, int maxM, int maxRows)
+{
+    return kbest_reserve_frontier(ctx, n, maxM, maxRows);
+}
+
+int kbest_frontier_sample_f64_dev(kbest_ctx *ctx, int n, const int32_t *m, const int32_t *nLk, const int64_t *subOff,
+                                  const double *d_sub, const int32_t *d_rowKey, const int64_t *rowKeyOff,
+                                  const uint64_t *frameKeyOfCluster, int nSample, uint64_t seed, uint32_t sampleBase,
+                                  int32_t *d_assignLocal, const int64_t *asgOff, double *d_logTerm, const int64_t *ltOff,
+                                  double *d_logZ, int32_t *d_info, int32_t *d_width, void *stream)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    if (n < 0 || nSample < 1 || (uint64_t)sampleBase + (uint64_t)nSample > ((uint64_t)1 << 32) ||
+        (n > 0 && (!m || !nLk || !subOff || !d_sub || !d_rowKey || !rowKeyOff || !d_assignLocal || !asgOff || !d_logTerm || !ltOff)))
+        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_frontier_sample_f64_dev: bad argument");
+    if (n == 0) return KBEST_OK;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    int maxRows = 1;
+    for (int k = 0; k < n; k++) {  // everything is checked before anything is launched
+        if (m[k] < 1 || m[k] > KBEST_FRONTIER_MAX_COLS || nLk[k] < 0 || nLk[k] > KBEST_MAX_DIM_WIDE || subOff[k] < 0 || rowKeyOff[k] < 0 ||
+            asgOff[k] < 0 || ltOff[k] < 0)
+            return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_frontier_sample_f64_dev: a cluster with m outside 1 .. 64, nLk outside 0 .. 1024 or a negative offset");
+        if (nLk[k] + m[k] > maxRows) maxRows = nLk[k] + m[k];
+    }
+    // workgroups: as kbest_frontier_probs_f64_dev counts them -- the same slots and plans of the same work space
+    kb::FrontierWork w;
+    w.slotDoubles = (long long)(ctx->frSlot / 8);
+    w.planDoubles = (long long)maxRows * kb::KB_FRONTIER_STEP_DOUBLES;
+    long long g = frames_in_flight(ctx, FRONTIER_WAVES_PER_CU, kb::KB_FRONTIER_THREADS, FRONTIER_LDS, w.slotDoubles, n, ctx->frWorkCap);
+    const long long slots = (long long)(ctx->frLayers.bytes / ctx->frSlot), plans = (long long)(ctx->frPlan.bytes / ((size_t)w.planDoubles * 8));
+    if (g > slots) g = slots;
+    if (g > plans) g = plans;
+    if (g < 1) return fail(ctx, KBEST_ERR_NOT_RESERVED, "kbest_frontier_sample_f64_dev: call kbest_reserve_frontier_sample first");
+    w.layers = static_cast<double *>(ctx->frLayers.p);
+    w.plan = static_cast<double *>(ctx->frPlan.p);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    int rc = order_behind_last(ctx, s);  // (one work space per context)
+    if (rc != KBEST_OK) return rc;
+    const Launched mark{ctx, s};
+    kb::FrontierSamplePack pk;
+    for (int at = 0; at < n; at += kb::KB_FRONTIER_SAMPLE_PACK) {  // (launches of one stream: the next pack takes the slots over)
+        pk.n = n - at < kb::KB_FRONTIER_SAMPLE_PACK ? n - at : kb::KB_FRONTIER_SAMPLE_PACK;
+        pk.base = at;
+        for (int j = 0; j < pk.n; j++) {
+            pk.c[j].subOff = subOff[at + j];
+            pk.c[j].rowKeyOff = rowKeyOff[at + j];
+            pk.c[j].asgOff = asgOff[at + j];
+            pk.c[j].ltOff = ltOff[at + j];
+            pk.c[j].frameKey = frameKeyOfCluster ? frameKeyOfCluster[at + j] : 0;
+            pk.c[j].m = m[at + j];
+            pk.c[j].nL = nLk[at + j];
+        }
+        const hipError_t e = kb::launch_frontier_sample_pack(pk, d_sub, d_rowKey, nSample, seed, sampleBase, d_assignLocal, d_logTerm,
+                                                             d_logZ, d_info, d_width, w, (int)g, s);
+        if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "frontier sampling kernel launch", e);
+    }
+    return KBEST_OK;
+}
+
 // ---- the exact hybrid path on the device (kbest_hybrid.hip): partial kernel, gather, frontier sweep, scatter, on one stream ------
 // Where everything lies in ctx->hybBuf for a call of (B, maxRawRow, maxCol), in bytes; every part is 16-byte aligned.  Each
 // size grows with each of the three, so a call within what was reserved fits.
@@ -4395,6 +4470,277 @@ int kbest_hybrid_frontier_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *
     if (B == 0) return KBEST_OK;
     return hybrid_impl(ctx, "kbest_hybrid_frontier_probs_batch_f64", B, nL, nM, cost, costOff, condition, k, maxExact, maxBig, maxWidth,
                        probs, probOff, logPerm, method, nOpen, nBig, nFrontier, maxCluster);
+}
+
+// ---- whole hypotheses for the frames of kbest_hybrid_frontier_probs_batch_f64(k = 0, maxBig = 0): the small clusters by the
+//      clustered sampler's second instantiation, the open ones by kbest_frontier_sample.hip, joined on the host ------------------------
+// The rows >= nL of an open cluster, ascending, in the caller's numbering: the partial kernel hands out the landmark rows only.
+// The gate is kbest_cluster.hip's (conditionCosts, the block minimum, 42), with comparisons and differences alone -- no exp.
+struct FrameGate {
+    std::vector<double> colMin;
+    std::vector<char> kept;
+    double mn = 0.0;
+    bool cond = false;
+    const double *x = nullptr;
+    int NR = 0, M = 0;
+    void make(const double *cost, int nL, int nM, bool condition)
+    {
+        const double INF = std::numeric_limits<double>::infinity();
+        x = cost; NR = nL + nM; M = nM; cond = condition;
+        colMin.assign(M, INF);
+        kept.assign(NR, 1);
+        if (cond) {
+            for (int c = 0; c < M; c++)
+                for (int r = 0; r < NR; r++) colMin[c] = x[(size_t)c * NR + r] < colMin[c] ? x[(size_t)c * NR + r] : colMin[c];
+            for (int r = 0; r < NR; r++) {
+                bool good = false;
+                for (int c = 0; c < M; c++) good = good | (x[(size_t)c * NR + r] <= colMin[c] + 42.0);
+                kept[r] = good ? 1 : 0;
+            }
+        }
+        mn = INF;
+        for (int c = 0; c < M; c++)
+            for (int r = 0; r < NR; r++)
+                if (kept[r]) mn = value(c, r) < mn ? value(c, r) : mn;
+    }
+    double value(int c, int r) const
+    {
+        double v = x[(size_t)c * NR + r];
+        if (cond) v = (v <= colMin[c] + 42.0) ? (v - colMin[c]) : std::numeric_limits<double>::infinity();
+        return v;
+    }
+    bool nonzero(int c, int r) const { return kept[r] && mn + 42.0 > value(c, r); }
+};
+
+int kbest_hybrid_frontier_sample_assoc_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,
+                                                 const int64_t *costOff, int condition, int maxExact, int maxWidth, int nSample,
+                                                 uint64_t seed, uint32_t sampleBase, const uint64_t *frameKey, int32_t *assign,
+                                                 const int64_t *asgOff, double *logProb, const int64_t *lpOff, double *logPerm,
+                                                 int32_t *method, int32_t *nOpen, int32_t *nFrontier, int32_t *maxCluster)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    const char *who = "kbest_hybrid_frontier_sample_assoc_batch_f64";
+    if (B < 0 || maxExact < 0 || maxExact > KBEST_CLUSTER_MAX_SIZE || maxWidth < 0 || maxWidth > KBEST_FRONTIER_MAX_WIDTH || nSample < 1 ||
+        (uint64_t)sampleBase + (uint64_t)nSample > ((uint64_t)1 << 32) ||
+        (B > 0 && (!nL || !nM || !cost || !costOff || !assign || !asgOff || !logProb || !lpOff || !method)))
+        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_hybrid_frontier_sample_assoc_batch_f64: bad argument (maxExact 0 .. 16, maxWidth 0 .. 16, "
+                                            "nSample >= 1, sampleBase + nSample <= 2^32)");
+    if (B == 0) return KBEST_OK;
+    std::vector<int64_t> pOff(B);  // the partial kernel's probabilities: packed, and dropped
+    {
+        int64_t at = 0;
+        for (int b = 0; b < B; b++) {
+            pOff[b] = at;
+            if (nL[b] >= 0 && nM[b] >= 1) at += (int64_t)nM[b] * ((int64_t)nL[b] + 1);
+        }
+    }
+    FrameBatch fb;
+    int rc = fb.scan(ctx, who, B, nL, nM, costOff, pOff.data());
+    if (rc != KBEST_OK) return rc;
+    const int maxRawRow = fb.maxRawRow, maxCol = fb.maxCol;
+    rc = check_frame_shape(ctx, who, B, maxRawRow, maxCol, KBEST_CLUSTER_MAX_COLS, CLUSTER_COLS_TEXT);
+    if (rc != KBEST_OK) return rc;
+    size_t asgN = 0, lpN = 0;  // int32s / doubles up to the end of the last frame's draws
+    for (int b = 0; b < B; b++) {
+        if (asgOff[b] < 0 || lpOff[b] < 0) return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_hybrid_frontier_sample_assoc_batch_f64: a negative offset");
+        asgN = std::max(asgN, (size_t)asgOff[b] + (size_t)nSample * (size_t)nM[b]);
+        lpN = std::max(lpN, (size_t)lpOff[b] + (size_t)nSample);
+    }
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = kbest_reserve_clustered(ctx, B, maxRawRow, maxCol);
+    if (rc != KBEST_OK) return rc;
+    const size_t descStride = (size_t)maxCol, rowStride = (size_t)maxRawRow;
+    // out: info[B] | maxCluster[B] | nOpen[B] (int32), the partial kernel's;  sOut: logPerm[B] (double) | info[B] (int32), the
+    // sampler's;  off: asgOff[B] | lpOff[B] | frameKey[B]
+    DevBuf dOut, dLabel, dDesc, dRows, dSub, dLp, dSOut, dAsg, dLpS, dOff;
+    rc = fb.upload(ctx, who, cost, {{&dOut, (size_t)B * 12}, {&dLabel, (size_t)B * maxCol * 4}, {&dDesc, (size_t)B * descStride * 16},
+                                    {&dRows, (size_t)B * rowStride * 4}, {&dSub, fb.costN * 8}, {&dLp, (size_t)B * 8},
+                                    {&dSOut, (size_t)B * 12}, {&dAsg, asgN * 4}, {&dLpS, lpN * 8}, {&dOff, (size_t)B * 24}});
+    if (rc != KBEST_OK) return rc;
+    HIP_TRY(ctx, hipMemcpy(dOff.p, asgOff, (size_t)B * 8, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(dOff.as<int64_t>() + B, lpOff, (size_t)B * 8, hipMemcpyHostToDevice));
+    if (frameKey) HIP_TRY(ctx, hipMemcpy(dOff.as<int64_t>() + 2 * (size_t)B, frameKey, (size_t)B * 8, hipMemcpyHostToDevice));
+    int32_t *o4 = dOut.as<int32_t>();
+    rc = kbest_clustered_partial_batch_f64_dev(ctx, B, maxRawRow, maxCol, fb.d_nL(), fb.d_nM(), fb.d_cost(), fb.d_costOff(), condition,
+                                               maxExact, fb.d_probs(), fb.d_probOff(), dLp.as<double>(), o4, o4 + B, dLabel.as<int32_t>(),
+                                               maxCol, o4 + 2 * (size_t)B, dDesc.as<int32_t>(), (int)descStride, dRows.as<int32_t>(),
+                                               (int)rowStride, dSub.as<double>(), nullptr);
+    if (rc != KBEST_OK) return rc;
+    unsigned char *s8 = dSOut.as<unsigned char>();
+    rc = cluster_sample_dev(ctx, maxExact ? maxExact : KBEST_CLUSTER_MAX_SIZE, B, maxRawRow, maxCol, fb.d_nL(), fb.d_nM(), fb.d_cost(), fb.d_costOff(), condition, nSample, seed,
+                            sampleBase, frameKey ? dOff.as<uint64_t>() + 2 * (size_t)B : nullptr, dAsg.as<int32_t>(), dOff.as<int64_t>(),
+                            dLpS.as<double>(), dOff.as<int64_t>() + B, reinterpret_cast<double *>(s8),
+                            reinterpret_cast<int32_t *>(s8 + (size_t)B * 8), nullptr, nullptr);
+    if (rc != KBEST_OK) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<int32_t> hInt((size_t)B * 3), hDesc, hRows, hLabel;  // info | maxCluster | nOpen
+    std::vector<double> hLp(B), sLp(B);
+    HIP_TRY(ctx, hipMemcpy(hInt.data(), dOut.p, (size_t)B * 12, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(hLp.data(), dLp.p, (size_t)B * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(sLp.data(), s8, (size_t)B * 8, hipMemcpyDeviceToHost));
+    const int32_t *hInfo = hInt.data(), *hOpen = hInt.data() + 2 * (size_t)B;
+    // every open cluster, in frame and label order; sent: through the sampler (at most 64 measurements); at: its place there
+    struct Open { int b, root, m, cL, R; size_t rowAt, from; int at; bool taken; };
+    std::vector<Open> open;
+    bool any = false;
+    for (int b = 0; b < B; b++) any = any || hOpen[b] > 0;
+    std::vector<int32_t> fM, fL, rowKey, fInfo, fWidth, hLocal;
+    std::vector<int64_t> fSo, fKo, fAo, fLo;
+    std::vector<uint64_t> fKey;
+    std::vector<double> fLogZ, hTerm;
+    if (any) {
+        hDesc.resize((size_t)B * descStride * 4);
+        hRows.resize((size_t)B * rowStride);
+        hLabel.resize((size_t)B * maxCol);
+        HIP_TRY(ctx, hipMemcpy(hDesc.data(), dDesc.p, hDesc.size() * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(hRows.data(), dRows.p, hRows.size() * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(hLabel.data(), dLabel.p, hLabel.size() * 4, hipMemcpyDeviceToHost));
+        size_t asgAt = 0;
+        int frM = 1, frRows = 1;
+        FrameGate gate;
+        for (int b = 0; b < B; b++) {
+            size_t n = 0, rowAt = (size_t)b * rowStride;
+            if (hOpen[b] > 0) gate.make(cost + costOff[b], nL[b], nM[b], condition != 0);
+            for (int j = 0; j < hOpen[b]; j++) {
+                const int32_t *d = hDesc.data() + ((size_t)b * descStride + j) * 4;
+                Open o{b, d[0], d[1], d[2], d[3], rowAt, n, -1, false};
+                n += (size_t)(o.cL + o.m) * o.m;
+                rowAt += (size_t)o.cL;
+                if (o.m <= KBEST_FRONTIER_MAX_COLS) {
+                    // q of every row of the sub-block: the RAW row of the caller's block (the all-+inf rows behind them are no steps)
+                    o.at = (int)fM.size();
+                    fM.push_back(o.m);
+                    fL.push_back(o.cL);
+                    fSo.push_back(costOff[b] + (int64_t)o.from);
+                    fKo.push_back((int64_t)rowKey.size());
+                    fAo.push_back((int64_t)asgAt);
+                    fLo.push_back((int64_t)o.at * nSample);
+                    fKey.push_back(frameKey ? frameKey[b] : (uint64_t)b);
+                    asgAt += (size_t)nSample * o.m;
+                    for (int r = 0; r < o.cL; r++) rowKey.push_back(hRows[o.rowAt + r]);
+                    int found = 0;
+                    const int32_t *lab = hLabel.data() + (size_t)b * maxCol;
+                    for (int r = nL[b]; r < nL[b] + nM[b]; r++) {
+                        bool in = false;
+                        for (int c = 0; c < nM[b] && !in; c++) in = lab[c] == o.root && gate.nonzero(c, r);
+                        if (in && found < o.m) rowKey.push_back(r);
+                        found += in ? 1 : 0;
+                    }
+                    if (found != o.R - o.cL) return fail(ctx, KBEST_ERR_INTERNAL, "kbest_hybrid_frontier_sample_assoc_batch_f64: the rows of an open cluster");
+                    for (int r = o.R; r < o.cL + o.m; r++) rowKey.push_back(0);
+                    if (o.m > frM) frM = o.m;
+                    if (o.cL + o.m > frRows) frRows = o.cL + o.m;
+                }
+                open.push_back(o);
+            }
+        }
+        if (!fM.empty() && maxWidth > 0) {
+            const int nf = (int)fM.size();
+            rc = kbest_reserve_frontier_sample(ctx, nf, frM, frRows);
+            if (rc != KBEST_OK) return rc;
+            DevBuf dKey, dLocal, dTerm, dFrOut;  // frOut: logZ[nf] (double) | info[nf] | width[nf] (int32)
+            hipError_t e;
+            if ((e = dKey.alloc(ctx, rowKey.size() * 4)) != hipSuccess || (e = dLocal.alloc(ctx, asgAt * 4)) != hipSuccess ||
+                (e = dTerm.alloc(ctx, (size_t)nf * nSample * 8)) != hipSuccess || (e = dFrOut.alloc(ctx, (size_t)nf * 16)) != hipSuccess)
+                return fail(ctx, KBEST_ERR_NOMEM, (std::string(who) + ": device buffers").c_str(), e);
+            HIP_TRY(ctx, hipMemcpy(dKey.p, rowKey.data(), rowKey.size() * 4, hipMemcpyHostToDevice));
+            unsigned char *f8 = dFrOut.as<unsigned char>();
+            int32_t *f4 = reinterpret_cast<int32_t *>(f8 + (size_t)nf * 8);
+            rc = kbest_frontier_sample_f64_dev(ctx, nf, fM.data(), fL.data(), fSo.data(), dSub.as<double>(), dKey.as<int32_t>(), fKo.data(),
+                                               fKey.data(), nSample, seed, sampleBase, dLocal.as<int32_t>(), fAo.data(), dTerm.as<double>(),
+                                               fLo.data(), reinterpret_cast<double *>(f8), f4, f4 + nf, nullptr);
+            if (rc != KBEST_OK) return rc;
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            fLogZ.resize(nf);
+            fInfo.resize(nf);
+            fWidth.resize(nf);
+            hLocal.resize(asgAt);
+            hTerm.resize((size_t)nf * nSample);
+            HIP_TRY(ctx, hipMemcpy(fLogZ.data(), f8, (size_t)nf * 8, hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(fInfo.data(), f4, (size_t)nf * 4, hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(fWidth.data(), f4 + nf, (size_t)nf * 4, hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(hLocal.data(), dLocal.p, asgAt * 4, hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(hTerm.data(), dTerm.p, hTerm.size() * 8, hipMemcpyDeviceToHost));
+            for (Open &o : open)
+                if (o.at >= 0 && fInfo[o.at] >= 0 && fWidth[o.at] <= maxWidth) o.taken = true;
+        }
+    }
+    std::vector<int32_t> hAsg(asgN);
+    std::vector<double> hLpS(lpN);
+    HIP_TRY(ctx, hipMemcpy(hAsg.data(), dAsg.p, asgN * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(hLpS.data(), dLpS.p, lpN * 8, hipMemcpyDeviceToHost));
+    // method, nFrontier: as kbest_hybrid_frontier_probs_batch_f64(k = 0, maxBig = 0) decides them
+    for (int b = 0; b < B; b++) method[b] = hInfo[b] < 0 ? -1 : hInfo[b] == 0 ? -2 : 0;
+    std::vector<int32_t> nFr(B, 0);
+    std::vector<char> refused(B, 0);
+    for (const Open &o : open) {
+        if (!o.taken) refused[o.b] = 1;
+        else if (fInfo[o.at] <= 0) method[o.b] = -2;
+        else nFr[o.b]++;
+    }
+    for (int b = 0; b < B; b++) {
+        if (refused[b]) method[b] = -1;
+        if (method[b] < 0 && hOpen[b] > 0) nFr[b] = 0;
+    }
+    // the draws: the small clusters' columns and terms are the sampler's; the open clusters' follow, in label order
+    const double QNAN = std::numeric_limits<double>::quiet_NaN();
+    for (const Open &o : open) {
+        if (method[o.b] != 0) continue;
+        const int b = o.b, M = nM[b];
+        const int32_t *lab = hLabel.data() + (size_t)b * maxCol, *keys = rowKey.data() + fKo[o.at];
+        const int32_t *loc = hLocal.data() + fAo[o.at];
+        const double *term = hTerm.data() + fLo[o.at];
+        int32_t *fa = hAsg.data() + asgOff[b];
+        double *fl = hLpS.data() + lpOff[b];
+        std::vector<int> cols;
+        for (int c = 0; c < M && (int)cols.size() < o.m; c++)
+            if (lab[c] == o.root) cols.push_back(c);
+        for (int s = 0; s < nSample; s++) {
+            for (int j = 0; j < o.m; j++) {
+                const int r = loc[(size_t)s * o.m + j];
+                fa[(size_t)s * M + cols[j]] = (r >= 0 && r < o.R) ? keys[r] : -1;
+            }
+            fl[s] = fl[s] + term[s];
+        }
+    }
+    for (int b = 0; b < B; b++) {
+        if (method[b] != 0) {
+            std::fill(hAsg.begin() + asgOff[b], hAsg.begin() + asgOff[b] + (size_t)nSample * (size_t)nM[b], -1);
+            std::fill(hLpS.begin() + lpOff[b], hLpS.begin() + lpOff[b] + (size_t)nSample, QNAN);
+        }
+        memcpy(assign + asgOff[b], hAsg.data() + asgOff[b], (size_t)nSample * (size_t)nM[b] * 4);
+        memcpy(logProb + lpOff[b], hLpS.data() + lpOff[b], (size_t)nSample * 8);
+    }
+    if (logPerm) {
+        // a frame without an open cluster: the sampler's own sum.  Else the partial kernel's sum over the clusters it answered, then
+        // the open clusters in label order, as kbest_hybrid_frontier_probs_batch_f64 adds them
+        for (int b = 0; b < B; b++) logPerm[b] = hOpen[b] > 0 ? hLp[b] : sLp[b];
+        int lastB = -1;
+        double mn = 0.0;
+        for (const Open &o : open) {
+            if (!o.taken || method[o.b] < 0) continue;
+            if (o.b != lastB) {
+                lastB = o.b;
+                mn = 0.0;
+                if (!condition) {
+                    const double *x = cost + costOff[o.b];
+                    const size_t cnt = ((size_t)nL[o.b] + nM[o.b]) * (size_t)nM[o.b];
+                    mn = x[0];
+                    for (size_t i = 1; i < cnt; i++) mn = x[i] < mn ? x[i] : mn;
+                }
+            }
+            logPerm[o.b] = logPerm[o.b] + (fLogZ[o.at] + (double)o.m * mn);
+        }
+        for (int b = 0; b < B; b++) {
+            if (method[b] == -2) logPerm[b] = -std::numeric_limits<double>::infinity();
+            if (method[b] == -1) logPerm[b] = QNAN;
+        }
+    }
+    if (nOpen) memcpy(nOpen, hOpen, (size_t)B * 4);
+    if (nFrontier) memcpy(nFrontier, nFr.data(), (size_t)B * 4);
+    if (maxCluster) memcpy(maxCluster, hInt.data() + B, (size_t)B * 4);
+    return KBEST_OK;
 }
 
 int kbest_bruteforce_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,

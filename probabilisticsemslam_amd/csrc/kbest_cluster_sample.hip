@@ -108,7 +108,21 @@ __device__ __forceinline__ bool cs_nonzero(const double *Cg, int NR, int c, int 
     return mn + CS_GATE > x;
 }
 
-__global__ void __launch_bounds__(512) kbest_cluster_sample_kernel(ClusterSampleParams p)
+// This file is compiled twice.  On its own: kbest_clustered_sample_assoc_batch_f64_dev's kernel.  Through
+// kbest_cluster_sample_partial.hip, which defines KB_CLUSTER_SAMPLE_PARTIAL and includes it
+// (kbest_hybrid_frontier_sample_assoc_batch_f64): a cluster of more than maxExact columns, or whose layers exceed the slot, is OPEN
+// as in kbest_cluster.hip's partial mode -- it does not refuse the frame, its columns stay -1, it adds no term to logProb or
+// logPerm and takes no place among the clusters; every other cluster is drawn by the same sweeps and the same walk with the same
+// uniforms.  A translation unit of its own, so that the plain kernel's code stays what it is, register for register.
+#ifdef KB_CLUSTER_SAMPLE_PARTIAL
+constexpr bool CS_PARTIAL = true;
+#define CS_KERNEL kbest_cluster_sample_partial_kernel(ClusterSampleParams p, int maxExact)
+#else
+constexpr bool CS_PARTIAL = false;
+#define CS_KERNEL kbest_cluster_sample_kernel(ClusterSampleParams p)
+#endif
+
+__global__ void __launch_bounds__(512) CS_KERNEL
 {
     extern __shared__ __align__(16) unsigned char smem[];
     const int tid = threadIdx.x, NT = blockDim.x, lane = tid & 63, wave = tid >> 6, NWV = NT >> 6;
@@ -275,8 +289,12 @@ __global__ void __launch_bounds__(512) kbest_cluster_sample_kernel(ClusterSample
                     cstart[c] = at;
                     at += R;
                     if (m > maxC) maxC = m;
+#ifdef KB_CLUSTER_SAMPLE_PARTIAL
+                    if (m > maxExact || ((long long)(R + 2) << m) * 8 > p.slotBytes) n--;  // open: no place in clist
+#else
                     if (m > CS_MAX_SIZE) refuse = -2;
                     else if (refuse == 0 && ((long long)(R + 2) << m) * 8 > p.slotBytes) refuse = -3;
+#endif
                 }
             ctl[2] = n;
             ctl[3] = maxC;
@@ -305,6 +323,9 @@ __global__ void __launch_bounds__(512) kbest_cluster_sample_kernel(ClusterSample
             rowAct[cstart[root] + rank] = (unsigned short)i;  // the i of u(s, i): the row's index among the frame's active rows
         }
         for (int s = tid; s < p.nSample; s += NT) lp[s] = 0.0;  // (its owner's running sum)
+        if constexpr (CS_PARTIAL)
+            for (int s = tid; s < p.nSample; s += NT)  // (its owner: the columns of the open clusters stay so)
+                for (int c = 0; c < M; c++) asg[(long long)s * M + c] = -1;
         __syncthreads();
 
         const u64 fk = p.frameKey ? p.frameKey[b] : (u64)b;
@@ -454,6 +475,25 @@ __global__ void __launch_bounds__(512) kbest_cluster_sample_kernel(ClusterSample
 
 }  // namespace
 
+#ifdef KB_CLUSTER_SAMPLE_PARTIAL
+hipError_t launch_kbest_cluster_sample_partial(const ClusterSampleParams &p, int maxExact, const ClusterPlan &pl, int grid,
+                                               hipStream_t stream)
+{
+    static std::atomic<int> granted[16];
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const int lds = cs_lds(p.maxRawRow, p.maxCol, pl.arena).total;
+    if (lds != pl.lds || p.arenaBytes != pl.arena) return hipErrorInvalidValue;
+    if (lds > granted[dev & 15].load(std::memory_order_relaxed)) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kbest_cluster_sample_partial_kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (e != hipSuccess) return e;
+        granted[dev & 15].store(lds, std::memory_order_relaxed);
+    }
+    hipLaunchKernelGGL(kbest_cluster_sample_partial_kernel, dim3(grid), dim3(pl.threads), lds, stream, p, maxExact);
+    return hipGetLastError();
+}
+#else
 hipError_t launch_kbest_cluster_sample(const ClusterSampleParams &p, const ClusterPlan &pl, int grid, hipStream_t stream)
 {
     static std::atomic<int> granted[16];
@@ -470,5 +510,6 @@ hipError_t launch_kbest_cluster_sample(const ClusterSampleParams &p, const Clust
     hipLaunchKernelGGL(kbest_cluster_sample_kernel, dim3(grid), dim3(pl.threads), lds, stream, p);
     return hipGetLastError();
 }
+#endif
 
 }  // namespace kb

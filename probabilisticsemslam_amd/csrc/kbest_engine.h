@@ -657,6 +657,10 @@ struct ClusterSampleParams {
     int arenaBytes, B, maxRawRow, maxCol, condition;
 };
 hipError_t launch_kbest_cluster_sample(const ClusterSampleParams &p, const ClusterPlan &pl, int grid, hipStream_t stream);
+// ... its second instantiation (kbest_cluster_sample_partial.hip): clusters of more than maxExact columns, or beyond the slot, are
+// left open -- their columns -1, no term of theirs in logProb or logPerm
+hipError_t launch_kbest_cluster_sample_partial(const ClusterSampleParams &p, int maxExact, const ClusterPlan &pl, int grid,
+                                               hipStream_t stream);
 
 // kbest_bigcluster.hip: one open cluster of up to 20 measurements over the whole chip, its layers in HBM (kbest_c.h, "Exact
 // association probabilities of clusters of 17 .. 20 measurements").  The clusters of a pack share every launch (grid.y).
@@ -713,6 +717,25 @@ struct FrontierWork {
 };
 hipError_t launch_frontier_pack(const FrontierPack &p, const double *sub, double *probs, double *logZ, int *info, int *width,
                                 const FrontierWork &w, int grid, hipStream_t stream);
+
+// kbest_frontier_sample.hip: joint associations drawn from the exact posterior of such a cluster -- the plan and the forward sweep
+// of kbest_frontier.hip, then one backward walk per draw (kbest_c.h, "Draws from the exact posterior of sparse clusters").  The
+// work space is the frontier tier's (FrontierWork); the descriptors travel as a kernel argument.
+constexpr int KB_FRONTIER_SAMPLE_PACK = 64;    // clusters of one launch
+struct FrontierSampleDesc {
+    long long subOff;           // the cluster's sub-block, in doubles from sub
+    long long rowKeyOff;        // the keys q of its nL + m rows, in int32s from rowKeys
+    long long asgOff, ltOff;    // its [nSample][m] rows / its [nSample] terms, from the caller's buffers
+    u64 frameKey;               // words 2 and 3 of the generator's counter
+    int m, nL;                  // columns, landmark rows
+};
+struct FrontierSamplePack {
+    FrontierSampleDesc c[KB_FRONTIER_SAMPLE_PACK];
+    int n, base;                // clusters; the place of the first one in logZ / info / width
+};
+hipError_t launch_frontier_sample_pack(const FrontierSamplePack &p, const double *sub, const int *rowKeys, int nSample, u64 seed,
+                                       u32 sampleBase, int *assignLocal, double *logTerm, double *logZ, int *info, int *width,
+                                       const FrontierWork &w, int grid, hipStream_t stream);
 
 // kbest_hybrid.hip: the exact hybrid path on the device (kbest_c.h, "Asynchronous exact hybrid probabilities").  One open cluster
 // of the flat list hybrid_gather_kernel makes of the partial kernel's descriptors, in frame order, then label order.

@@ -318,6 +318,29 @@ std::vector<std::vector<int>> clusterSampleAssoc(const std::vector<double> &cost
     return out;
 }
 
+std::vector<std::vector<int>> hybridFrontierSampleAssoc(const std::vector<double> &costMatrix, size_t nL, size_t nM, size_t nSample,
+                                                        uint64_t seed)
+{
+    kbest_ctx *ctx = global_ctx();
+    const int32_t l = (int32_t)nL, m = (int32_t)nM;
+    const int64_t zero = 0;
+    const uint64_t key = 0;
+    int32_t method = 0, maxCluster = 0;
+    std::vector<int32_t> flat(nSample * nM);
+    std::vector<double> logProb(nSample);
+    check(ctx, kbest_hybrid_frontier_sample_assoc_batch_f64(ctx, 1, &l, &m, costMatrix.data(), &zero, 0, KBEST_CLUSTER_MAX_SIZE,
+                                                            KBEST_FRONTIER_MAX_WIDTH, (int)nSample, seed, 0, &key, flat.data(), &zero,
+                                                            logProb.data(), &zero, nullptr, &method, nullptr, nullptr, &maxCluster));
+    if (method == -1)
+        throw std::runtime_error("hybridFrontierSampleAssoc: frame refused: its largest cluster has " + std::to_string(maxCluster) +
+                                 " measurements");
+    if (method == -2)
+        throw std::runtime_error("hybridFrontierSampleAssoc: the frame has no consistent association (some cluster's permanent is 0)");
+    std::vector<std::vector<int>> out(nSample);
+    for (size_t s = 0; s < nSample; s++) out[s].assign(flat.begin() + s * nM, flat.begin() + (s + 1) * nM);
+    return out;
+}
+
 std::vector<std::vector<double>> hybridProb(const std::vector<double> &costMatrix, size_t nL, size_t nM, size_t k)
 {
     kbest_ctx *ctx = global_ctx();

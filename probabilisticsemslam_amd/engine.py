@@ -64,6 +64,7 @@ C_ABI_SYMBOLS = (
     "kbest_reserve_frontier", "kbest_set_frontier_work_cap", "kbest_set_frontier_slot", "kbest_frontier_probs_f64_dev",
     "kbest_hybrid_frontier_probs_batch_f64",
     "kbest_reserve_hybrid_dev", "kbest_hybrid_frontier_probs_batch_f64_dev",
+    "kbest_reserve_frontier_sample", "kbest_frontier_sample_f64_dev", "kbest_hybrid_frontier_sample_assoc_batch_f64",
     "kbest_bb_costs_f64",
 )
 KBEST_MULTI_STAMPS = 6
@@ -216,6 +217,13 @@ def load_library():
         lib.kbest_reserve_hybrid_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int]
         lib.kbest_hybrid_frontier_probs_batch_f64_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int, i32p, i32p, dp, i64p, C.c_int, C.c_int,
                                                                   C.c_int, dp, dp, i64p, dp, i32p, i32p, i32p, i32p, vp]
+    if hasattr(lib, "kbest_frontier_sample_f64_dev"):
+        lib.kbest_reserve_frontier_sample.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+        lib.kbest_frontier_sample_f64_dev.argtypes = [vp, C.c_int, i32p, i32p, i64p, dp, i32p, i64p, i64p, C.c_int, C.c_uint64,
+                                                      C.c_uint32, i32p, i64p, dp, i64p, dp, i32p, i32p, vp]
+        lib.kbest_hybrid_frontier_sample_assoc_batch_f64.argtypes = [vp, C.c_int, i32p, i32p, dp, i64p, C.c_int, C.c_int, C.c_int,
+                                                                     C.c_int, C.c_uint64, C.c_uint32, i64p, i32p, i64p, dp, i64p, dp,
+                                                                     i32p, i32p, i32p, i32p]
     lib.kbest_register_host_buffer.argtypes = [vp, vp, C.c_size_t]
     lib.kbest_unregister_host_buffer.argtypes = [vp, vp]
     _lib = lib
@@ -652,6 +660,61 @@ class KBestEngine:
                                                           _dptr(d_sub), _dptr(d_probs), _dptr(d_logZ), _dptr(d_info),
                                                           _dptr(d_width), _stream(stream)))
 
+    def hybrid_frontier_sample_assoc(self, costs, nL, nM, n_sample, seed=0, condition=False, frame_key=None, sample_base=0,
+                                     max_exact=16, max_width=16):
+        """kbest_hybrid_frontier_sample_assoc_batch_f64: clustered_sample_assoc() for the frames hybrid_frontier_probs(k=0, max_big=0)
+        answers -- the clusters of at most max_exact measurements by the clustered sampler's walk (the same draws), every larger one
+        of at most 64 measurements and a frontier width of at most max_width by a backward walk over the frontier tier's layers.
+        Returns (list of int32 [n_sample, nM] arrays: the raw row every measurement takes, list of logProb [n_sample], logPerm[B],
+        method[B]: 0 drawn, -1 refused (assign -1, logProb NaN), -2 infeasible (likewise), nOpen[B], nFrontier[B], maxCluster[B])."""
+        nL, nM, B, flat, costOff, _, _, _ = _pack_frames(costs, nL, nM, "hybrid_frontier_sample_assoc")
+        n_sample = int(n_sample)
+        sizes = n_sample * nM.astype(np.int64)
+        asgOff = np.concatenate(([0], np.cumsum(sizes)[:-1])).astype(np.int64) if B else np.zeros(0, np.int64)
+        lpOff = (np.arange(B, dtype=np.int64) * n_sample)
+        assign = np.zeros(int(sizes.sum()) if B else 0, np.int32)
+        logp = np.zeros(B * n_sample, np.float64)
+        logPerm = np.zeros(B, np.float64)
+        method, nOpen, nFrontier, maxCluster = (np.zeros(B, np.int32) for _ in range(4))
+        key = None if frame_key is None else np.ascontiguousarray(frame_key, dtype=np.uint64)
+        if key is not None and len(key) != B:
+            raise ValueError("hybrid_frontier_sample_assoc: one frame key per frame")
+        self._check(self.lib.kbest_hybrid_frontier_sample_assoc_batch_f64(
+            self.ctx, B, _ptr(nL), _ptr(nM), _ptr(flat), _ptr(costOff), int(bool(condition)), int(max_exact), int(max_width), n_sample,
+            int(seed), int(sample_base), _ptr(key), _ptr(assign), _ptr(asgOff), _ptr(logp), _ptr(lpOff), _ptr(logPerm), _ptr(method),
+            _ptr(nOpen), _ptr(nFrontier), _ptr(maxCluster)))
+        return ([assign[asgOff[b]: asgOff[b] + n_sample * int(nM[b])].reshape(n_sample, int(nM[b])) for b in range(B)],
+                [logp[lpOff[b]: lpOff[b] + n_sample] for b in range(B)], logPerm, method, nOpen, nFrontier, maxCluster)
+
+    def reserve_frontier_sample(self, n, maxM, maxRows):
+        """kbest_reserve_frontier_sample: the work space of frontier_sample_dev -- exactly what reserve_frontier() reserves."""
+        self._check(self.lib.kbest_reserve_frontier_sample(self.ctx, int(n), int(maxM), int(maxRows)))
+
+    def frontier_sample_dev(self, m, nLk, subOff, d_sub, d_rowKey, rowKeyOff, n_sample, d_assignLocal, asgOff, d_logTerm, ltOff,
+                            d_logZ=None, d_info=None, d_width=None, seed=0, sample_base=0, frame_key=None, stream=None, reserve=True):
+        """kbest_frontier_sample_f64_dev, asynchronous on `stream`: n_sample joint associations of every cluster, drawn from its
+        exact posterior by a backward walk over the frontier tier's forward layers.  m, nLk, subOff, d_sub, d_logZ, d_info and
+        d_width as frontier_probs_dev() (and with its bits); d_rowKey (int32, device) at rowKeyOff[k] the key q of every row of
+        the cluster's sub-block, frame_key[k] (host, None: 0) the key of its frame.  Out: d_assignLocal at asgOff[k]
+        [n_sample][m_k] the row of the sub-block every column takes, d_logTerm at ltOff[k] [n_sample] the draw's log-probability
+        inside the cluster.  info 0: -1 and NaN; a refused cluster (-3, -4): untouched."""
+        m = np.ascontiguousarray(m, dtype=np.int32)
+        nLk = np.ascontiguousarray(nLk, dtype=np.int32)
+        subOff = np.ascontiguousarray(subOff, dtype=np.int64)
+        rowKeyOff = np.ascontiguousarray(rowKeyOff, dtype=np.int64)
+        asgOff = np.ascontiguousarray(asgOff, dtype=np.int64)
+        ltOff = np.ascontiguousarray(ltOff, dtype=np.int64)
+        fk = None if frame_key is None else np.ascontiguousarray(frame_key, dtype=np.uint64)
+        if fk is not None and len(fk) != len(m):
+            raise ValueError("frontier_sample_dev: one frame key per cluster")
+        if reserve and len(m):
+            self.reserve_frontier_sample(len(m), int(m.max()), int((m + nLk).max()))
+        self._check(self.lib.kbest_frontier_sample_f64_dev(self.ctx, len(m), _ptr(m), _ptr(nLk), _ptr(subOff), _dptr(d_sub),
+                                                           _dptr(d_rowKey), _ptr(rowKeyOff), None if fk is None else _ptr(fk),
+                                                           int(n_sample), int(seed), int(sample_base), _dptr(d_assignLocal),
+                                                           _ptr(asgOff), _dptr(d_logTerm), _ptr(ltOff), _dptr(d_logZ), _dptr(d_info),
+                                                           _dptr(d_width), _stream(stream)))
+
     def set_clustered_slot_cap(self, nbytes=0):
         """For tests (kbest_set_clustered_slot_cap): the layers of one cluster at the most, 0 = KBEST_CLUSTER_SLOT_CAP again; a frame
         with a cluster that needs more is refused (info = -3)."""
@@ -1075,6 +1138,19 @@ def hybridProb(costMatrix, nL, nM, k):
     if method[0] == -1:
         raise RuntimeError("hybridProb: frame refused: a cluster holds more rows >= nL than measurements")
     return out[0]
+
+
+def hybridFrontierSampleAssoc(costMatrix, nL, nM, nSample, seed=0):
+    """Not in the reference: clusterSampleAssoc for the frames hybridFrontierProb(k = 0) takes: gated clusters of up to 64
+    measurements whose rows, in the greedy order, keep at most 16 columns open are drawn too.  Returns int32 [nSample][nM]; raises
+    RuntimeError when the frame is refused or has no consistent association."""
+    asg, _, _, method, _, _, maxCluster = _engine().hybrid_frontier_sample_assoc([costMatrix], [nL], [nM], nSample, seed=seed,
+                                                                                   frame_key=[0])
+    if method[0] == -1:
+        raise RuntimeError(f"hybridFrontierSampleAssoc: frame refused: its largest cluster has {int(maxCluster[0])} measurements")
+    if method[0] == -2:
+        raise RuntimeError("hybridFrontierSampleAssoc: the frame has no consistent association (some cluster's permanent is 0)")
+    return asg[0]
 
 
 def hybridFrontierProb(costMatrix, nL, nM, k):

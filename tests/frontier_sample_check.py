@@ -1,0 +1,256 @@
+"""numpy restatement of the draws from the exact posterior of sparse clusters (kbest_frontier_sample.hip,
+kbest_hybrid_frontier_sample_assoc_batch_f64) for the tests.
+
+    per cluster: frontier_check.scaled_block and frontier_check.greedy_plan (a', the counting rows, the row order, Phi / new /
+    closing of every step); the forward layers as arrays over the subsets of Phi_i (state bit j = the j-th column of Phi_i in
+    ascending order), with the kernel's order of additions:
+        F_{i+1}[S] = [T & new = 0] F_i[T] + sum_{c in T & N_r, (T \\ c) & new = 0, c ascending} a'[r][c] F_i[T \\ c],  T = S | closing_i
+    Z' = F_R[empty]
+    the walk, vectorised over the draws: S = empty; for i = R-1 .. 0: tot = F_{i+1}[S], Tt = u tot; T & new == 0: acc = F_i[T],
+    Tt < acc: nothing; else for c ascending as above: acc = acc + a'[r][c] F_i[T \\ c], the first c with Tt < acc (else the last
+    with a term > 0)
+    u: Philox4x32-10 of sample_check with the counter (sampleBase + s, 0x80000000 | (q >> 1), frameKey low, frameKey high), words
+    0, 1 for an even q, 2, 3 for an odd one; q = row_key[row of the sub-block]
+    logTerm[s] = sum_c (colMin_c - x[r_c][c]) - log Z', the columns ascending
+    the frame (hybrid_frontier_sample_assoc): the clusters of at most max_exact measurements by cluster_sample_check.walk_cluster
+    (uniforms indexed by the frame's active rows), the open ones by the walk above with q = the RAW row; logProb = the small
+    clusters' terms in label order from 0.0, then the open clusters' terms in label order; method, nOpen, nFrontier, maxCluster,
+    logPerm: frontier_check.hybrid_frontier_probs(k = 0, max_big = 0)
+
+Besides the draws everything returns the smallest RELATIVE MARGIN min |Tt - acc| / tot over every comparison made, as sample_check
+does.  Cost blocks are column-major (nL+nM) x nM, as everywhere in this project."""
+from __future__ import annotations
+
+import collections
+import functools
+
+import numpy as np
+
+import cluster_check as cc
+import cluster_sample_check as csc
+import frontier_check as fc
+import sample_check as sc
+
+M32 = sc.M32
+DOMAIN = 0x80000000  # bit 31 of the counter's second word: the frontier sampler's uniforms
+Layers = collections.namedtuple("Layers", "A rows colmin X masks steps W F Z info")
+FrameDraws = collections.namedtuple("FrameDraws", "assign logp logperm method nopen nfrontier maxc margin opens small_cols")
+
+
+def bits_of(mask):
+    return [c for c in range(mask.bit_length()) if (mask >> c) & 1]
+
+
+def pack(v, cols):
+    """The bits of v (int64 array or int) at the columns `cols`, packed: bit j = column cols[j]."""
+    out = v * 0
+    for j, c in enumerate(cols):
+        out = out | (((v >> c) & 1) << j)
+    return out
+
+
+def spread(idx, cols):
+    out = idx * 0
+    for j, c in enumerate(cols):
+        out = out | (((idx >> j) & 1) << c)
+    return out
+
+
+def counter(q):
+    """(word 1 of the counter, which pair of output words) of row key q."""
+    return DOMAIN | (q >> 1), q & 1
+
+
+def uniforms(seed, draw, q, frame_key):
+    """u of the draws `draw` (uint64 array of sampleBase + s) at the row with key q."""
+    c1, odd = counter(int(q))
+    w = sc.philox4x32_10((draw, np.uint64(c1), frame_key & M32, (frame_key >> 32) & M32), (seed & M32, (seed >> 32) & M32))
+    lo, hi = (w[2], w[3]) if odd else (w[0], w[1])
+    return (((hi << np.uint64(32)) | lo) >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+
+
+def cluster_layers(block, nLk, m, slot_bytes=fc.SLOT, max_width=fc.MAX_WIDTH):
+    """The plan and the forward layers of one sub-block.  info as frontier_check.frontier_cluster (F, Z None when refused)."""
+    assert m <= 62  # (int64 masks)
+    A, rows, colmin = fc.scaled_block(block, nLk, m)
+    X = np.asarray(block, dtype=np.float64).reshape(m, nLk + m).T
+    masks = fc.row_masks(A)
+    steps, W, layers = fc.greedy_plan(masks, m)
+    if W > max_width:
+        return Layers(A, rows, colmin, X, masks, steps, W, None, None, fc.REFUSED_WIDTH)
+    if layers * 8 > slot_bytes:
+        return Layers(A, rows, colmin, X, masks, steps, W, None, None, fc.REFUSED_SLOT)
+    F = [np.array([1.0])]
+    for st in steps:
+        r, phi, new = st["row"], st["phi"], st["new"]
+        phi_cols, nxt_cols = bits_of(phi), bits_of(st["nxt"])
+        T = spread(np.arange(1 << len(nxt_cols), dtype=np.int64), nxt_cols) | st["closing"]
+        Fi = F[-1]
+        val = np.where((T & new) == 0, Fi[pack(T & phi, phi_cols)], 0.0)
+        for c in bits_of(masks[r]):
+            Tc = T & ~(1 << c)
+            on = (((T >> c) & 1) == 1) & ((Tc & new) == 0)
+            val = np.where(on, val + A[r, c] * Fi[pack(Tc & phi, phi_cols)], val)
+        F.append(val)
+    Z = float(F[-1][0])
+    ok = Z > 0.0 and np.isfinite(colmin).all() and all(any((n >> c) & 1 for n in masks) for c in range(m))
+    return Layers(A, rows, colmin, X, masks, steps, W, F, Z, 1 if ok else 0)
+
+
+def walk(L, row_key, n_sample, seed=0, frame_key=0, sample_base=0):
+    """n_sample draws of the cluster of L = cluster_layers(...), info 1.  row_key[r]: q of row r of the sub-block.  Returns
+    (assignLocal int32 [n_sample, m]: the row of the sub-block every column takes, logTerm [n_sample], margin)."""
+    m = L.A.shape[1]
+    draw = np.arange(sample_base, sample_base + n_sample, dtype=np.uint64)
+    S = np.zeros(n_sample, np.int64)
+    assign = np.full((n_sample, m), -1, np.int32)
+    margin = np.inf
+    for i in range(len(L.steps) - 1, -1, -1):
+        st = L.steps[i]
+        r, phi, new = st["row"], st["phi"], st["new"]
+        sub_row = int(L.rows[r])
+        phi_cols, nxt_cols = bits_of(phi), bits_of(st["nxt"])
+        Fi, Fn = L.F[i], L.F[i + 1]
+        T = spread(S, nxt_cols) | st["closing"]
+        tot = Fn[S]
+        Tt = uniforms(seed, draw, int(row_key[sub_row]), frame_key) * tot
+        none = (T & new) == 0
+        acc = np.where(none, Fi[pack(T & phi, phi_cols)], 0.0)
+        if none.any():
+            margin = min(margin, (np.abs(Tt - acc) / tot)[none].min())
+        walking = ~(none & (Tt < acc))
+        take = np.full(n_sample, -1)
+        for c in bits_of(L.masks[r]):
+            Tc = T & ~(1 << c)
+            on = walking & (((T >> c) & 1) == 1) & ((Tc & new) == 0)
+            if not on.any():
+                continue
+            term = L.A[r, c] * Fi[pack(Tc & phi, phi_cols)]
+            acc = np.where(on, acc + term, acc)
+            take = np.where(on & (term > 0.0), c, take)
+            margin = min(margin, (np.abs(Tt - acc) / tot)[on].min())
+            walking = walking & ~(on & (Tt < acc))
+        for c in bits_of(L.masks[r]):
+            got = take == c
+            assign[got, c] = sub_row
+            T = np.where(got, T & ~(1 << c), T)
+        S = pack(T & phi, phi_cols)
+    assert (S == 0).all() and (assign >= 0).all()  # a state is only entered through a term > 0: every column is taken
+    lt = np.zeros(n_sample)
+    for c in range(m):
+        lt = lt + (L.colmin[c] - L.X[assign[:, c], c])
+    return assign, lt - np.log(L.Z), float(margin)
+
+
+def sample_cluster(block, nLk, m, row_key, n_sample, seed=0, frame_key=0, sample_base=0, slot_bytes=fc.SLOT):
+    """kbest_frontier_sample_f64_dev on one sub-block: (assignLocal or None, logTerm or None, logZ, info, W, margin)."""
+    L = cluster_layers(block, nLk, m, slot_bytes)
+    if L.info < 0:
+        return None, None, None, L.info, L.W, np.inf
+    if L.info == 0:
+        return np.full((n_sample, m), -1, np.int32), np.full(n_sample, np.nan), float("-inf"), 0, L.W, np.inf
+    a, lt, mg = walk(L, row_key, n_sample, seed, frame_key, sample_base)
+    return a, lt, float(np.log(L.Z) - L.colmin.sum()), 1, L.W, mg
+
+
+def open_row_keys(o, nL):
+    """q of every row of the sub-block of hybrid_check's open cluster o, and the same as raw rows: the RAW row of the caller's
+    block -- the landmark rows, then the cluster's rows >= nL ascending; the all-+inf rows behind them are no steps (0)."""
+    raw = np.zeros(o["nL"] + o["m"], np.int64)
+    raw[: o["R"]] = o["all_rows"]
+    return raw
+
+
+def hybrid_frontier_sample_assoc(cost, nL, nM, n_sample, seed=0, condition=False, frame_key=0, sample_base=0, max_exact=cc.MAX_SIZE,
+                                 max_width=fc.MAX_WIDTH, frontier_slot=fc.SLOT):
+    """One frame.  Returns FrameDraws; opens: frontier_check.hybrid_frontier_probs' dicts with all_rows (raw), and for a drawn
+    frame assign_local, logterm and margin; small_cols: the columns of the clusters the clustered sampler's walk draws."""
+    import hybrid_check as hc
+    probs, method, opens, nfr, _, maxc, logperm = fc.hybrid_frontier_probs(cost, nL, nM, 0, condition, max_exact, 0, max_width,
+                                                                           frontier_slot=frontier_slot)
+    parts, _ = csc.cluster_parts(cost, nL, nM, condition)
+    _, A = hc.gated_block(cost, nL, nM, condition)
+    clusters, _ = cc.clusters_of(A)
+    open_roots = {}
+    for cols, rows in clusters:
+        if len(cols) > max_exact or ((len(rows) + 2) << len(cols)) * 8 > cc.SLOT_CAP:
+            open_roots[int(cols[0])] = rows
+    for o in opens:
+        o["all_rows"] = open_roots[o["root"]]
+    small = [p for p in parts if int(p.cols[0]) not in open_roots]
+    assign = np.full((n_sample, nM), -1, np.int32)
+    nan = np.full(n_sample, np.nan)
+    small_cols = np.concatenate([p.cols for p in small]) if small else np.zeros(0, np.int64)
+    if method != 0:
+        return FrameDraws(assign, nan, logperm, method, len(opens), 0, maxc, np.inf, opens, small_cols)
+    logp = np.zeros(n_sample)
+    margin = np.inf
+    for p in small:
+        prod, mg = csc.walk_cluster(p, n_sample, seed, frame_key, sample_base, assign)
+        logp = logp + (np.log(prod) - np.log(p.Z))
+        margin = min(margin, mg)
+    for o in opens:
+        L = cluster_layers(o["block"], o["nL"], o["m"], frontier_slot)
+        keys = open_row_keys(o, nL)
+        a, lt, mg = walk(L, keys, n_sample, seed, frame_key, sample_base)
+        o["assign_local"], o["logterm"], o["margin"] = a, lt, mg
+        assign[:, o["cols"]] = keys[a]
+        logp = logp + lt
+        margin = min(margin, mg)
+    if not opens:  # the bits of the clustered sampler's sum
+        logperm = 0.0
+        for p in small:
+            logperm = logperm + float(np.log(p.Z))
+    return FrameDraws(assign, logp, logperm, method, len(opens), nfr, maxc, float(margin), opens, small_cols)
+
+
+# ---- the cases of the tests: computed once, shared, read-only ------------------------------------------------------------------------
+SMALL = (200, 40, 24, 24.0)
+MID = (200, 60, 40, 30.0)
+SEED = sc.SEED
+
+
+@functools.lru_cache(maxsize=None)
+def scene(F, nL, nM, side):
+    from probabilisticsemslam_amd import workloads as wl
+    return wl.scene_frames(F, nL, nM, side)
+
+
+@functools.lru_cache(maxsize=None)
+def frame_draws(shape, index, n_sample, max_exact=4, condition=True, seed=SEED, frame_key=None, sample_base=0, max_width=fc.MAX_WIDTH):
+    _, nL, nM, _ = shape
+    d = hybrid_frontier_sample_assoc(scene(*shape)[index], nL, nM, n_sample, seed, condition, index if frame_key is None else frame_key,
+                                     sample_base, max_exact, max_width)
+    d.assign.setflags(write=False)
+    d.logp.setflags(write=False)
+    return d
+
+
+@functools.lru_cache(maxsize=None)
+def open_clusters(shape, frames, max_exact=4, condition=True):
+    """[(frame, o)] of every open cluster of those frames: o = hybrid_check's dict with all_rows and keys (q of every sub-block row)."""
+    _, nL, nM, _ = shape
+    out = []
+    for b in frames:
+        f = scene(*shape)[b]
+        for o in hc_opens(f, nL, nM, condition, max_exact):
+            o["keys"] = open_row_keys(o, nL).astype(np.int32)
+            out.append((b, o))
+    return tuple(out)
+
+
+def hc_opens(cost, nL, nM, condition, max_exact):
+    """The open clusters of a frame as the partial kernel hands them out (hybrid_check.hybrid_probs' dicts, without its k-best leg)."""
+    import hybrid_check as hc
+    X, A = hc.gated_block(cost, nL, nM, condition)
+    opens = []
+    for cols, rows in cc.clusters_of(A)[0]:
+        m, R = len(cols), len(rows)
+        if m > max_exact or ((R + 2) << m) * 8 > cc.SLOT_CAP:
+            cL = int((rows < nL).sum())
+            assert R - cL <= m
+            blk = np.full((cL + m, m), np.inf)
+            blk[:R] = np.where(A[np.ix_(rows, cols)] > 0.0, X[np.ix_(rows, cols)], np.inf)
+            opens.append(dict(root=int(cols[0]), m=m, nL=cL, R=R, rows=rows[:cL].astype(np.int32), cols=cols, all_rows=rows,
+                              block=np.ascontiguousarray(blk.T).reshape(-1)))
+    return opens
