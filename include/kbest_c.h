@@ -35,6 +35,7 @@
  *   kbest_hybrid_frontier_probs_batch_f64_dev / kbest_reserve_hybrid_dev
  *        the exact association probabilities by gated clusters, for frames of up to 128 measurements (not in the reference)
  *   kbest_clustered_sample_assoc_batch_f64 / kbest_clustered_sample_assoc_batch_f64_dev
+ *   kbest_hybrid_frontier_sample_assoc_batch_f64 / kbest_hybrid_frontier_sample_assoc_batch_f64_dev
  *        joint associations drawn from the exact posterior of such frames, one walk per cluster (not in the reference)
  *
  * Conventions kept from the reference: cost matrices are column-major
@@ -807,6 +808,43 @@ int kbest_hybrid_frontier_probs_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawR
                                               int maxExact, int maxWidth, double *d_sub, double *d_probs, const int64_t *d_probOff,
                                               double *d_logPerm, int32_t *d_method, int32_t *d_nOpen, int32_t *d_nFrontier,
                                               int32_t *d_maxCluster, void *stream);
+/*
+ * Asynchronous exact hybrid draws (kbest_hybrid_sample.hip; not in the reference): kbest_hybrid_frontier_sample_assoc_batch_f64 on
+ * buffers that already lie on the device, on ONE stream -- the partial clustered kernel, the clustered sampler's second
+ * instantiation, the gather of the open clusters of all frames into one list (frame order, then label order: a prefix sum, no
+ * atomics), a kernel that finds every listed cluster's row keys (the RAW rows of the caller's block: the landmark rows of the
+ * partial kernel's row list, then the rows >= nL that have a non-zero entry in a column of the cluster, by the gate of the partial
+ * kernel restated with comparisons and differences), the sampler of kbest_frontier_sample_f64_dev over that list in ONE launch, and
+ * a join that maps the local rows back and adds the terms.  No host read, no synchronise, no allocation, no floating-point atomics,
+ * no workgroup waits for another; stream order between the launches is the only synchronisation.  Every output carries the bits of
+ * the host entry on the same frames, arguments, seed, keys and sampleBase: assign, logProb and logPerm (NaN as NaN, -inf as -inf),
+ * method, nOpen, nFrontier, maxCluster.  A frame's outputs are a function of (frame, seed, frame key, draw index) alone.
+ *
+ * kbest_hybrid_frontier_sample_assoc_batch_f64_dev: frames, d_cost, d_costOff, condition, maxExact (0 .. 16, 0 = 16) and d_sub (the
+ * caller's work buffer, sized and addressed like d_cost) as in kbest_hybrid_frontier_probs_batch_f64_dev; maxWidth 0 .. 16, where 0
+ * refuses every frame with an open cluster, as on the host; nSample >= 1, seed, sampleBase (sampleBase + nSample <= 2^32),
+ * d_frameKey (may be NULL: frame b has key b), d_assign, d_asgOff, d_logProb and d_lpOff as in
+ * kbest_clustered_sample_assoc_batch_f64_dev.  Anything outside those ranges: KBEST_ERR_BAD_ARG.  d_method is required; d_logPerm,
+ * d_nOpen, d_nFrontier and d_maxCluster may be NULL.
+ *   method -1 or -2 on a frame within the launch bounds: every assign -1, every logProb NaN, as on the host.
+ *   A frame beyond the bounds (nM < 1, nM > maxCol, nL < 0 or nL + nM > maxRawRow): method -1, nOpen and nFrontier 0, logPerm NaN;
+ *   its assign, logProb and maxCluster are not touched.
+ *   An open cluster whose rows the key kernel cannot tell (the host entry's KBEST_ERR_INTERNAL) is not sent: method -1.
+ * The context holds everything else: kbest_reserve_hybrid_sample_dev(ctx, B, maxRawRow, maxCol, nSample) sizes, from those four
+ * alone, what kbest_reserve_hybrid_dev and kbest_reserve_clustered_sample size, and per frame its offset into the packed scratch,
+ * two sums and the sampler's info, maxRawRow row keys and nSample * maxCol local rows, and per cluster of the list its key item and
+ * nSample terms.  A reservation never shrinks: it is sized for the largest of each of the four numbers so far.  Without it, or
+ * with a call beyond it in any of the four numbers: KBEST_ERR_NOT_RESERVED.  B = 0: KBEST_OK, nothing
+ * launched.  Asynchronous on `stream` (NULL: the context's); two calls on one stream need no synchronise between them.
+ */
+int kbest_reserve_hybrid_sample_dev(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, int nSample);
+int kbest_hybrid_frontier_sample_assoc_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, const int32_t *d_nL,
+                                                     const int32_t *d_nM, const double *d_cost, const int64_t *d_costOff,
+                                                     int condition, int maxExact, int maxWidth, int nSample, uint64_t seed,
+                                                     uint32_t sampleBase, const uint64_t *d_frameKey, double *d_sub,
+                                                     int32_t *d_assign, const int64_t *d_asgOff, double *d_logProb,
+                                                     const int64_t *d_lpOff, double *d_logPerm, int32_t *d_method, int32_t *d_nOpen,
+                                                     int32_t *d_nFrontier, int32_t *d_maxCluster, void *stream);
 /* on = 1: the HOST-buffer association entries of this context (kbest_weights / assoc_probs / bruteforce / quadric_assoc) enumerate
  * their k best in the REFERENCE's own order of operations (the reference-order kernel, as KBEST_FLAG_REFERENCE_ORDER does for
  * kbest_batch_f64): where exactly equal gains straddle slot k the assignments that are weighed are the ones the reference's

@@ -158,6 +158,9 @@ struct kbest_ctx {
     size_t frWorkCap = KBEST_FRONTIER_WORK_CAP;   // ... the slots in flight at the most (kbest_set_frontier_work_cap)
     DevBufRaw hybBuf;         // kbest_hybrid_frontier_probs_batch_f64_dev: labels, descriptors, row lists, the cluster list, the
                               // per-cluster outputs and the packed probabilities (kbest_reserve_hybrid_dev; HybridLayout)
+    DevBufRaw hybSampBuf;     // kbest_hybrid_frontier_sample_assoc_batch_f64_dev: offsets, sums, the clusters' keys, local draws and
+                              // terms (kbest_reserve_hybrid_sample_dev; HybridSampleLayout)
+    int hybSampB = 0, hybSampRow = 0, hybSampCol = 0, hybSampN = 0;  // ... the largest of each number reserved so far: what it is sized for
     DevBufRaw relayBuf;       // relay launches of the 64-row kernel: [B] LDS images (kbest_engine.hip)
     DevBufRaw relayFlags;     // ... and three words per matrix: claimed / done / gone (zeroed when the buffer is made, put back to zero by every launch)
     long long relayLaunches = 0;  // relay launches made (kbest_relay_launches)
@@ -624,6 +627,7 @@ int kbest_destroy(kbest_ctx *ctx)
     if (ctx->frLayers.p) (void)hipFree(ctx->frLayers.p);
     if (ctx->frPlan.p) (void)hipFree(ctx->frPlan.p);
     if (ctx->hybBuf.p) (void)hipFree(ctx->hybBuf.p);
+    if (ctx->hybSampBuf.p) (void)hipFree(ctx->hybSampBuf.p);
     if (ctx->relayFlags.p) (void)hipFree(ctx->relayFlags.p);
     if (ctx->lastEvent) (void)hipEventDestroy(ctx->lastEvent);
     for (auto &a : ctx->aux)
@@ -4740,6 +4744,174 @@ int kbest_hybrid_frontier_sample_assoc_batch_f64(kbest_ctx *ctx, int B, const in
     if (nOpen) memcpy(nOpen, hOpen, (size_t)B * 4);
     if (nFrontier) memcpy(nFrontier, nFr.data(), (size_t)B * 4);
     if (maxCluster) memcpy(maxCluster, hInt.data() + B, (size_t)B * 4);
+    return KBEST_OK;
+}
+
+// ---- the same draws on the device (kbest_hybrid_sample.hip): everything the entry above does on the host between its kernels,
+//      on one stream ---------------------------------------------------------------------------------------------------------------
+// Where everything lies in ctx->hybSampBuf for a call of (B, maxRawRow, maxCol, nSample), in bytes, beside HybridLayout's part in
+// ctx->hybBuf; every part is 16-byte aligned.  Each size grows with each of the four, so a call within what was reserved fits.
+struct HybridSampleLayout {
+    size_t probOff, partLp, drawLp, drawInfo, keys, rowKey, local, term, total;
+};
+static HybridSampleLayout hybrid_sample_layout(int B, int maxRawRow, int maxCol, int nSample)
+{
+    HybridSampleLayout L;
+    size_t at = 0;
+    auto take = [&at](size_t bytes) { const size_t here = at; at += (bytes + 15) & ~(size_t)15; return here; };
+    const size_t b = (size_t)B, cap = b * (size_t)maxCol;    // a frame has at most nM clusters
+    L.probOff = take(b * 8);
+    L.partLp = take(b * 8);
+    L.drawLp = take(b * 8);
+    L.drawInfo = take(b * 4);
+    L.keys = take(cap * sizeof(kb::HybridKeyItem));
+    L.rowKey = take(b * (size_t)maxRawRow * 4);               // a frame's clusters: sum (nL_k + m_k) <= nL + nM
+    L.local = take(cap * (size_t)nSample * 4);                // ... and sum m_k <= nM
+    L.term = take(cap * (size_t)nSample * 8);
+    L.total = at;
+    return L;
+}
+
+static const char HYBRID_SAMPLE_ARGS_TEXT[] = ": bad argument (maxExact 0 .. 16, maxWidth 0 .. 16, nSample >= 1, sampleBase + nSample <= 2^32)";
+
+int kbest_reserve_hybrid_sample_dev(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, int nSample)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    const char *who = "kbest_reserve_hybrid_sample_dev";
+    int rc = check_frame_shape(ctx, who, B, maxRawRow, maxCol, KBEST_CLUSTER_MAX_COLS, CLUSTER_COLS_TEXT);
+    if (rc != KBEST_OK) return rc;
+    if (nSample < 1) return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_reserve_hybrid_sample_dev: bad argument (nSample >= 1)");
+    if (B == 0) return KBEST_OK;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    // a reservation never shrinks: everything is sized for the largest of each number so far, and a call is held against those
+    B = std::max(ctx->hybSampB, B);
+    maxRawRow = std::max(ctx->hybSampRow, maxRawRow);
+    maxCol = std::max(ctx->hybSampCol, maxCol);
+    nSample = std::max(ctx->hybSampN, nSample);
+    rc = kbest_reserve_hybrid_dev(ctx, B, maxRawRow, maxCol);  // (with it kbest_reserve_clustered: the clustered sampler's too)
+    if (rc != KBEST_OK) return rc;
+    rc = raw_reserve(ctx, ctx->hybSampBuf, hybrid_sample_layout(B, maxRawRow, maxCol, nSample).total);
+    if (rc != KBEST_OK) return rc;
+    ctx->hybSampB = B;
+    ctx->hybSampRow = maxRawRow;
+    ctx->hybSampCol = maxCol;
+    ctx->hybSampN = nSample;
+    return KBEST_OK;
+}
+
+int kbest_hybrid_frontier_sample_assoc_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, const int32_t *d_nL,
+                                                     const int32_t *d_nM, const double *d_cost, const int64_t *d_costOff,
+                                                     int condition, int maxExact, int maxWidth, int nSample, uint64_t seed,
+                                                     uint32_t sampleBase, const uint64_t *d_frameKey, double *d_sub,
+                                                     int32_t *d_assign, const int64_t *d_asgOff, double *d_logProb,
+                                                     const int64_t *d_lpOff, double *d_logPerm, int32_t *d_method, int32_t *d_nOpen,
+                                                     int32_t *d_nFrontier, int32_t *d_maxCluster, void *stream)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    const std::string who = "kbest_hybrid_frontier_sample_assoc_batch_f64_dev";
+    int rc = check_frame_shape(ctx, who.c_str(), B, maxRawRow, maxCol, KBEST_CLUSTER_MAX_COLS, CLUSTER_COLS_TEXT);
+    if (rc != KBEST_OK) return rc;
+    if (maxExact < 0 || maxExact > KBEST_CLUSTER_MAX_SIZE || maxWidth < 0 || maxWidth > KBEST_FRONTIER_MAX_WIDTH || nSample < 1 ||
+        (uint64_t)sampleBase + (uint64_t)nSample > ((uint64_t)1 << 32))
+        return fail(ctx, KBEST_ERR_BAD_ARG, (who + HYBRID_SAMPLE_ARGS_TEXT).c_str());
+    if (B == 0) return KBEST_OK;
+    if (!d_nL || !d_nM || !d_cost || !d_costOff || !d_sub || !d_assign || !d_asgOff || !d_logProb || !d_lpOff || !d_method)
+        return fail(ctx, KBEST_ERR_BAD_ARG, (who + ": bad argument").c_str());
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // everything is checked before anything is launched; an asynchronous entry never allocates
+    const HybridLayout L = hybrid_layout(B, maxRawRow, maxCol);
+    const HybridSampleLayout S = hybrid_sample_layout(B, maxRawRow, maxCol, nSample);
+    kb::FrontierWork w;
+    w.slotDoubles = (long long)(ctx->frSlot / 8);
+    w.planDoubles = (long long)maxRawRow * kb::KB_FRONTIER_STEP_DOUBLES;
+    const long long g = frontier_grid(ctx, L.cap, w.planDoubles);
+    kb::ClusterPlan pl;
+    rc = cluster_plan_of(ctx, maxRawRow, maxCol, pl, who.c_str());
+    if (rc != KBEST_OK) return rc;
+    if (B > ctx->hybSampB || maxRawRow > ctx->hybSampRow || maxCol > ctx->hybSampCol || nSample > ctx->hybSampN ||
+        ctx->hybSampBuf.bytes < S.total || ctx->hybBuf.bytes < L.total || g < 1 || ctx->clusBuf.bytes < (size_t)pl.slotDoubles * 8)
+        return fail(ctx, KBEST_ERR_NOT_RESERVED, (who + ": call kbest_reserve_hybrid_sample_dev first").c_str());
+    w.layers = static_cast<double *>(ctx->frLayers.p);
+    w.plan = static_cast<double *>(ctx->frPlan.p);
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    unsigned char *h8 = static_cast<unsigned char *>(ctx->hybBuf.p), *s8 = static_cast<unsigned char *>(ctx->hybSampBuf.p);
+    auto i32 = [h8](size_t off) { return reinterpret_cast<int32_t *>(h8 + off); };
+    auto f64 = [](unsigned char *base, size_t off) { return reinterpret_cast<double *>(base + off); };
+    rc = order_behind_last(ctx, s);  // (one work space per context)
+    if (rc != KBEST_OK) return rc;
+    const Launched mark{ctx, s};
+    kb::HybridSampleParams sp;
+    sp.nL = d_nL;
+    sp.nM = d_nM;
+    sp.costOff = reinterpret_cast<const long long *>(d_costOff);
+    sp.asgOff = reinterpret_cast<const long long *>(d_asgOff);
+    sp.lpOff = reinterpret_cast<const long long *>(d_lpOff);
+    sp.cost = d_cost;
+    sp.frameKey = reinterpret_cast<const kb::u64 *>(d_frameKey);
+    sp.assign = d_assign;
+    sp.logProb = d_logProb;
+    sp.logPerm = d_logPerm;
+    sp.method = d_method;
+    sp.nOpenOut = d_nOpen;
+    sp.nFrontier = d_nFrontier;
+    sp.info = i32(L.info);
+    sp.nOpen = i32(L.nOpen);
+    sp.label = i32(L.label);
+    sp.openDesc = i32(L.desc);
+    sp.openRows = i32(L.rows);
+    sp.partLogPerm = f64(s8, S.partLp);
+    sp.drawLogPerm = f64(s8, S.drawLp);
+    sp.probOff = reinterpret_cast<long long *>(s8 + S.probOff);
+    sp.list = reinterpret_cast<kb::HybridItem *>(h8 + L.list);
+    sp.count = i32(L.count);
+    sp.first = i32(L.first);
+    sp.keys = reinterpret_cast<kb::HybridKeyItem *>(s8 + S.keys);
+    sp.rowKey = reinterpret_cast<int32_t *>(s8 + S.rowKey);
+    sp.local = reinterpret_cast<int32_t *>(s8 + S.local);
+    sp.term = f64(s8, S.term);
+    sp.logZ = f64(h8, L.logZ);
+    sp.finfo = i32(L.finfo);
+    sp.width = i32(L.width);
+    sp.packStride = L.packStride;
+    sp.B = B;
+    sp.maxRawRow = maxRawRow;
+    sp.maxCol = maxCol;
+    sp.condition = condition ? 1 : 0;
+    sp.maxWidth = maxWidth;
+    sp.nSample = nSample;
+    hipError_t e = kb::launch_hybrid_sample_prepare(sp, s);
+    if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "hybrid sampling kernel launch", e);
+    // the partial kernel (its probabilities: packed, and dropped), then the clustered sampler's second instantiation
+    rc = kbest_clustered_partial_batch_f64_dev(ctx, B, maxRawRow, maxCol, d_nL, d_nM, d_cost, d_costOff, condition, maxExact,
+                                               f64(h8, L.packed), reinterpret_cast<const int64_t *>(s8 + S.probOff), f64(s8, S.partLp),
+                                               i32(L.info), d_maxCluster, i32(L.label), maxCol, i32(L.nOpen), i32(L.desc), maxCol,
+                                               i32(L.rows), maxRawRow, d_sub, stream);
+    if (rc != KBEST_OK) return rc;
+    rc = cluster_sample_dev(ctx, maxExact ? maxExact : KBEST_CLUSTER_MAX_SIZE, B, maxRawRow, maxCol, d_nL, d_nM, d_cost, d_costOff,
+                            condition, nSample, seed, sampleBase, d_frameKey, d_assign, d_asgOff, d_logProb, d_lpOff, f64(s8, S.drawLp),
+                            reinterpret_cast<int32_t *>(s8 + S.drawInfo), nullptr, stream);
+    if (rc != KBEST_OK) return rc;
+    kb::HybridParams hp{};  // the gather of kbest_hybrid.hip reads the partial kernel's outputs and writes list, first and count
+    hp.nL = d_nL;
+    hp.nM = d_nM;
+    hp.costOff = sp.costOff;
+    hp.nOpen = sp.nOpen;
+    hp.openDesc = sp.openDesc;
+    hp.list = reinterpret_cast<kb::HybridItem *>(h8 + L.list);
+    hp.count = i32(L.count);
+    hp.first = i32(L.first);
+    hp.packStride = L.packStride;
+    hp.B = B;
+    hp.maxRawRow = maxRawRow;
+    hp.maxCol = maxCol;
+    e = kb::launch_hybrid_gather(hp, s);
+    if (e == hipSuccess) e = kb::launch_hybrid_sample_keys(sp, s);
+    if (e == hipSuccess && maxWidth > 0)  // (maxWidth = 0: nothing goes through the sampler, as on the host)
+        e = kb::launch_frontier_sample_list(sp.list, sp.keys, sp.count, d_sub, sp.rowKey, nSample, seed, sampleBase, sp.local, sp.term,
+                                            f64(h8, L.logZ), i32(L.finfo), i32(L.width), w, (int)g, s);
+    if (e == hipSuccess) e = kb::launch_hybrid_sample_join(sp, s);
+    if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "hybrid sampling kernel launch", e);
     return KBEST_OK;
 }
 

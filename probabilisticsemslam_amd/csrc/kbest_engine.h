@@ -765,6 +765,44 @@ hipError_t launch_frontier_list(const HybridItem *list, const int *count, const 
 hipError_t launch_hybrid_gather(const HybridParams &p, hipStream_t stream);
 hipError_t launch_hybrid_scatter(const HybridParams &p, hipStream_t stream);
 
+// kbest_hybrid_sample.hip: the exact hybrid DRAWS on the device (kbest_c.h, "Asynchronous exact hybrid draws").  What the sampler of
+// kbest_frontier_sample.hip needs of a cluster of that list besides its HybridItem, at the same place k.
+struct HybridKeyItem {
+    long long rowKeyOff;        // the keys q of its nL + m rows, in int32s from rowKey
+    long long asgOff, ltOff;    // its [nSample][m] local rows in local / its [nSample] terms in term
+    u64 frameKey;               // words 2 and 3 of the generator's counter
+    int R, sent;                // rows that count; 0: not sent (HybridItem::sent == 0, or its rows could not be told)
+};
+struct HybridSampleParams {
+    const int *nL, *nM;                        // [B]
+    const long long *costOff, *asgOff, *lpOff; // [B]: the caller's
+    const double *cost;
+    const u64 *frameKey;                       // [B] or nullptr (frame b: b)
+    int *assign;                               // the clustered sampler's draws in, the frames' out
+    double *logProb, *logPerm;                 // logPerm: out, or nullptr
+    int *method, *nOpenOut, *nFrontier;        // [B]; nOpenOut, nFrontier may be nullptr
+    const int *info, *nOpen, *label, *openDesc, *openRows;  // the partial kernel's outputs, as HybridParams
+    const double *partLogPerm, *drawLogPerm;   // [B]: the partial kernel's sums / the clustered sampler's
+    long long *probOff;                        // [B]: where the partial kernel's (dropped) probabilities go in the packed scratch
+    const HybridItem *list;                    // hybrid_gather_kernel's
+    const int *count, *first;
+    HybridKeyItem *keys;                       // [B * maxCol], beside list
+    int *rowKey;                               // [B][maxRawRow]
+    int *local;                                // [B][nSample * maxCol]
+    double *term;                              // [B * maxCol][nSample]
+    const double *logZ;                        // the list sampler's outputs per cluster of the list
+    const int *finfo, *width;
+    long long packStride;
+    int B, maxRawRow, maxCol, condition, maxWidth, nSample;
+};
+hipError_t launch_hybrid_sample_prepare(const HybridSampleParams &p, hipStream_t stream);
+hipError_t launch_hybrid_sample_keys(const HybridSampleParams &p, hipStream_t stream);
+hipError_t launch_hybrid_sample_join(const HybridSampleParams &p, hipStream_t stream);
+// the sampler of kbest_frontier_sample.hip on that list: `grid` workgroups, each with a slot and a plan of w
+hipError_t launch_frontier_sample_list(const HybridItem *list, const HybridKeyItem *keys, const int *count, const double *sub,
+                                       const int *rowKeys, int nSample, u64 seed, u32 sampleBase, int *assignLocal, double *logTerm,
+                                       double *logZ, int *info, int *width, const FrontierWork &w, int grid, hipStream_t stream);
+
 }  // namespace kb
 
 // kbest_capi.cpp: completes the gain levels that straddle slot k in the caller's HOST tables (see there)

@@ -2,6 +2,9 @@
 // KBEST_FRONTIER_MAX_COLS = 64 measurements whose frontier width is at most KBEST_FRONTIER_MAX_WIDTH = 16: the plan and the forward
 // sweep of kbest_frontier.hip, then one backward walk per draw over the layers that sweep keeps.  One workgroup per cluster, one
 // launch per pack of clusters.  gfx950, fp64, plain HIP C++.  DESIGN.md section 18.
+// Two entry points, one walk (frontier_sample_walk<Source>): frontier_sample_kernel takes its clusters from a kernel-argument pack,
+// frontier_sample_list_kernel from the list kbest_hybrid.hip gathers and kbest_hybrid_sample.hip completes on the device, ONE launch
+// for all of them.
 //
 // Input, scaling, plan and forward layers are kbest_frontier.hip's, restated expression for expression (that file keeps its own
 // lines and with them its code objects): the (nL_k + m_k) x m_k column-major sub-block, a'[r][c] = exp(colMin_c - x[r][c]), the
@@ -125,24 +128,56 @@ __device__ __forceinline__ void fs_load_step(FsShared &sh, const FsStep *plan, i
     }
 }
 
-__global__ void __launch_bounds__(FS_THREADS)
-frontier_sample_kernel(FrontierSamplePack p, const double *sub, const int *rowKeys, int nSample, u64 seed, u32 sampleBase,
-                       int *assignLocal, double *logTerm, double *logZ, int *info, int *width, FrontierWork wk)
+// Where the clusters of a launch come from: the kernel-argument pack of kbest_frontier_sample_f64_dev, or the list that
+// kbest_hybrid.hip gathers and kbest_hybrid_sample.hip completes in HBM, with its count word.  The walk below is the same code for both.
+struct FsPackSource {
+    const FrontierSamplePack &p;
+    __device__ __forceinline__ int n() const { return p.n; }
+    __device__ __forceinline__ bool sent(int) const { return true; }
+    __device__ __forceinline__ int m(int k) const { return p.c[k].m; }
+    __device__ __forceinline__ int nL(int k) const { return p.c[k].nL; }
+    __device__ __forceinline__ long long subOff(int k) const { return p.c[k].subOff; }
+    __device__ __forceinline__ long long rowKeyOff(int k) const { return p.c[k].rowKeyOff; }
+    __device__ __forceinline__ long long asgOff(int k) const { return p.c[k].asgOff; }
+    __device__ __forceinline__ long long ltOff(int k) const { return p.c[k].ltOff; }
+    __device__ __forceinline__ u64 frameKey(int k) const { return p.c[k].frameKey; }
+    __device__ __forceinline__ int idx(int k) const { return p.base + k; }
+};
+struct FsListSource {
+    const HybridItem *list;
+    const HybridKeyItem *keys;
+    const int *count;
+    __device__ __forceinline__ int n() const { return *count; }
+    __device__ __forceinline__ bool sent(int k) const { return keys[k].sent != 0; }
+    __device__ __forceinline__ int m(int k) const { return list[k].m; }
+    __device__ __forceinline__ int nL(int k) const { return list[k].nL; }
+    __device__ __forceinline__ long long subOff(int k) const { return list[k].subOff; }
+    __device__ __forceinline__ long long rowKeyOff(int k) const { return keys[k].rowKeyOff; }
+    __device__ __forceinline__ long long asgOff(int k) const { return keys[k].asgOff; }
+    __device__ __forceinline__ long long ltOff(int k) const { return keys[k].ltOff; }
+    __device__ __forceinline__ u64 frameKey(int k) const { return keys[k].frameKey; }
+    __device__ __forceinline__ int idx(int k) const { return k; }
+};
+
+template <class Source>
+__device__ __forceinline__ void frontier_sample_walk(FsShared &sh, const Source &src, const double *sub, const int *rowKeys, int nSample,
+                                                     u64 seed, u32 sampleBase, int *assignLocal, double *logTerm, double *logZ,
+                                                     int *info, int *width, const FrontierWork &wk)
 {
-    __shared__ FsShared sh;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     double *slot = wk.layers + (long long)blockIdx.x * wk.slotDoubles;
     FsStep *plan = reinterpret_cast<FsStep *>(wk.plan + (long long)blockIdx.x * wk.planDoubles);
     const double INF = d_inf();
     const double QNAN = __builtin_nan("");
     const u32 k0 = (u32)seed, k1 = (u32)(seed >> 32);
-    const int n = p.n;
+    const int n = src.n();
     for (int k = blockIdx.x; k < n; k += gridDim.x) {
-        const int m = p.c[k].m, nL = p.c[k].nL, nr = nL + m, idx = p.base + k;
-        const double *x = sub + p.c[k].subOff;
-        const int *rowKey = rowKeys + p.c[k].rowKeyOff;
-        int *asg = assignLocal + p.c[k].asgOff;
-        double *lt = logTerm + p.c[k].ltOff;
+        if (!src.sent(k)) continue;  // (uniform)
+        const int m = src.m(k), nL = src.nL(k), nr = nL + m, idx = src.idx(k);
+        const double *x = sub + src.subOff(k);
+        const int *rowKey = rowKeys + src.rowKeyOff(k);
+        int *asg = assignLocal + src.asgOff(k);
+        double *lt = logTerm + src.ltOff(k);
         __syncthreads();  // (the previous cluster is done with the shared arrays)
         if ((long long)nr * KB_FRONTIER_STEP_DOUBLES > wk.planDoubles || nr > FS_ROWS || m > KB_FRONTIER_MAX_COLS) {
             if (tid == 0 && info) info[idx] = -3;  // (the host entry never lets this happen)
@@ -304,7 +339,8 @@ frontier_sample_kernel(FrontierSamplePack p, const double *sub, const int *rowKe
             continue;
         }
         // ---- the walk: rounds of FS_THREADS * FS_DPT draws, every round through the steps from the last to the first ---------------
-        const u32 f0 = (u32)p.c[k].frameKey, f1 = (u32)(p.c[k].frameKey >> 32);
+        const u64 fk = src.frameKey(k);
+        const u32 f0 = (u32)fk, f1 = (u32)(fk >> 32);
         const double lz = log(Z);
         for (int s0 = 0; s0 < nSample; s0 += FS_THREADS * FS_DPT) {  // (uniform)
             unsigned S[FS_DPT];  // the draw's state in Phi_{i+1}; F_R has the one state `empty`
@@ -379,6 +415,25 @@ frontier_sample_kernel(FrontierSamplePack p, const double *sub, const int *rowKe
     }
 }
 
+__global__ void __launch_bounds__(FS_THREADS)
+frontier_sample_kernel(FrontierSamplePack p, const double *sub, const int *rowKeys, int nSample, u64 seed, u32 sampleBase,
+                       int *assignLocal, double *logTerm, double *logZ, int *info, int *width, FrontierWork wk)
+{
+    __shared__ FsShared sh;
+    frontier_sample_walk(sh, FsPackSource{p}, sub, rowKeys, nSample, seed, sampleBase, assignLocal, logTerm, logZ, info, width, wk);
+}
+
+// a workgroup without a cluster (blockIdx.x >= *count) returns at once
+__global__ void __launch_bounds__(FS_THREADS)
+frontier_sample_list_kernel(const HybridItem *list, const HybridKeyItem *keys, const int *count, const double *sub, const int *rowKeys,
+                            int nSample, u64 seed, u32 sampleBase, int *assignLocal, double *logTerm, double *logZ, int *info,
+                            int *width, FrontierWork wk)
+{
+    __shared__ FsShared sh;
+    frontier_sample_walk(sh, FsListSource{list, keys, count}, sub, rowKeys, nSample, seed, sampleBase, assignLocal, logTerm, logZ, info,
+                         width, wk);
+}
+
 }  // namespace
 
 hipError_t launch_frontier_sample_pack(const FrontierSamplePack &p, const double *sub, const int *rowKeys, int nSample, u64 seed,
@@ -390,6 +445,16 @@ hipError_t launch_frontier_sample_pack(const FrontierSamplePack &p, const double
     if (grid < 1) grid = 1;
     hipLaunchKernelGGL(frontier_sample_kernel, dim3(grid), dim3(FS_THREADS), 0, stream, p, sub, rowKeys, nSample, seed, sampleBase,
                        assignLocal, logTerm, logZ, info, width, w);
+    return hipGetLastError();
+}
+
+hipError_t launch_frontier_sample_list(const HybridItem *list, const HybridKeyItem *keys, const int *count, const double *sub,
+                                       const int *rowKeys, int nSample, u64 seed, u32 sampleBase, int *assignLocal, double *logTerm,
+                                       double *logZ, int *info, int *width, const FrontierWork &w, int grid, hipStream_t stream)
+{
+    if (grid < 1) return hipSuccess;
+    hipLaunchKernelGGL(frontier_sample_list_kernel, dim3(grid), dim3(FS_THREADS), 0, stream, list, keys, count, sub, rowKeys, nSample,
+                       seed, sampleBase, assignLocal, logTerm, logZ, info, width, w);
     return hipGetLastError();
 }
 

@@ -65,6 +65,7 @@ C_ABI_SYMBOLS = (
     "kbest_hybrid_frontier_probs_batch_f64",
     "kbest_reserve_hybrid_dev", "kbest_hybrid_frontier_probs_batch_f64_dev",
     "kbest_reserve_frontier_sample", "kbest_frontier_sample_f64_dev", "kbest_hybrid_frontier_sample_assoc_batch_f64",
+    "kbest_reserve_hybrid_sample_dev", "kbest_hybrid_frontier_sample_assoc_batch_f64_dev",
     "kbest_bb_costs_f64",
 )
 KBEST_MULTI_STAMPS = 6
@@ -224,6 +225,11 @@ def load_library():
         lib.kbest_hybrid_frontier_sample_assoc_batch_f64.argtypes = [vp, C.c_int, i32p, i32p, dp, i64p, C.c_int, C.c_int, C.c_int,
                                                                      C.c_int, C.c_uint64, C.c_uint32, i64p, i32p, i64p, dp, i64p, dp,
                                                                      i32p, i32p, i32p, i32p]
+    if hasattr(lib, "kbest_hybrid_frontier_sample_assoc_batch_f64_dev"):
+        lib.kbest_reserve_hybrid_sample_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
+        lib.kbest_hybrid_frontier_sample_assoc_batch_f64_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int, i32p, i32p, dp, i64p, C.c_int,
+                                                                         C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint32, i64p, dp,
+                                                                         i32p, i64p, dp, i64p, dp, i32p, i32p, i32p, i32p, vp]
     lib.kbest_register_host_buffer.argtypes = [vp, vp, C.c_size_t]
     lib.kbest_unregister_host_buffer.argtypes = [vp, vp]
     _lib = lib
@@ -975,6 +981,31 @@ class KBestEngine:
             self.ctx, int(B), int(maxRawRow), int(maxCol), _dptr(d_nL), _dptr(d_nM), _dptr(d_cost), _dptr(d_costOff),
             int(bool(condition)), int(max_exact), int(max_width), _dptr(d_sub), _dptr(d_probs), _dptr(d_probOff), _dptr(d_logPerm),
             _dptr(d_method), _dptr(d_nOpen), _dptr(d_nFrontier), _dptr(d_maxCluster), _stream(stream)))
+
+    def reserve_hybrid_sample_dev(self, B, maxRawRow, maxCol, n_sample):
+        """kbest_reserve_hybrid_sample_dev: everything hybrid_frontier_sample_assoc_dev needs besides the caller's buffers, sized
+        from the four numbers alone."""
+        self._check(self.lib.kbest_reserve_hybrid_sample_dev(self.ctx, int(B), int(maxRawRow), int(maxCol), int(n_sample)))
+
+    def hybrid_frontier_sample_assoc_dev(self, B, maxRawRow, maxCol, d_nL, d_nM, d_cost, d_costOff, d_sub, n_sample, d_assign, d_asgOff,
+                                         d_logProb, d_lpOff, d_method, d_logPerm=None, d_nOpen=None, d_nFrontier=None,
+                                         d_maxCluster=None, seed=0, sample_base=0, d_frameKey=None, condition=False, max_exact=16,
+                                         max_width=16, stream=None, reserve=True):
+        """kbest_hybrid_frontier_sample_assoc_batch_f64_dev on torch CUDA tensors (or raw addresses), asynchronous on `stream` (a
+        raw hipStream_t integer): hybrid_frontier_sample_assoc() -- n_sample whole hypotheses a frame, the clusters of at most
+        max_exact measurements by the clustered sampler's walk, every larger one by the walk over the frontier tier's layers --
+        without a host read, a synchronise or an allocation, and with that entry's bits.  d_sub: a work buffer shaped like d_cost.
+        d_assign (int32) at d_asgOff[b] [n_sample][nM], d_logProb (float64) at d_lpOff[b] [n_sample]; d_frameKey int64 / uint64
+        [B] or None (frame b: b).  d_method int32 [B] is required; d_logPerm (float64), d_nOpen, d_nFrontier, d_maxCluster (int32)
+        may be None.  A frame beyond (maxRawRow, maxCol): method -1, its draws not touched.  reserve=False: the caller has called
+        reserve_hybrid_sample_dev (timed loops; the C entry never allocates)."""
+        if reserve:
+            self.reserve_hybrid_sample_dev(B, maxRawRow, maxCol, n_sample)
+        self._check(self.lib.kbest_hybrid_frontier_sample_assoc_batch_f64_dev(
+            self.ctx, int(B), int(maxRawRow), int(maxCol), _dptr(d_nL), _dptr(d_nM), _dptr(d_cost), _dptr(d_costOff),
+            int(bool(condition)), int(max_exact), int(max_width), int(n_sample), int(seed), int(sample_base), _dptr(d_frameKey),
+            _dptr(d_sub), _dptr(d_assign), _dptr(d_asgOff), _dptr(d_logProb), _dptr(d_lpOff), _dptr(d_logPerm), _dptr(d_method),
+            _dptr(d_nOpen), _dptr(d_nFrontier), _dptr(d_maxCluster), _stream(stream)))
 
 
 class KBestMulti:
