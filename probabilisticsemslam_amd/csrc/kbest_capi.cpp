@@ -1360,6 +1360,7 @@ static int batch_dev_impl(kbest_ctx *ctx, const kbest_opts *opts, int B, int max
         p.split = S;
         p.splitB = B;
         p.sharedT = S > 1 ? reinterpret_cast<unsigned long long *>(sb + sl.offT) : nullptr;
+        p.tablesHost = hostTables ? 1 : 0;
         // optimistic bounds: the quantile of the pool a node is split against (host model: tests/dev/proto_tickets.cpp; kernel:
         // struct Opt).  Measured (kernel ms, off -> on, one box, interleaved): 4 096 x 32x32, k = 200 (4 waves, 4 hypotheses per
         // round, no a-priori thresholds there) 3.87 -> 3.67 at 0.85 (0.8: 3.81, 0.9: 3.76, 0.75: 4.12); 1 024 x 64x64 (12 x 12, where

@@ -66,6 +66,10 @@ struct Params {
     long long relayStride;
     unsigned *relayFlag;
     unsigned *relayClaim, *relayGone;
+    // 64-row kernel: the result tables are in HOST memory (registered or pinned staging, written over the link): the slots that
+    // have become final are then written at the start of a round's children phase, so that the stores drain under the children;
+    // tables in device memory (0) are written behind a wave's children, in the slack in front of the barrier after them
+    int tablesHost;
 };
 
 struct CondParams {

@@ -1054,6 +1054,8 @@ __global__ void __launch_bounds__(NW * 64, min_waves_per_simd(NW)) kbest_kernel(
         KB_T(tF0);
 #ifdef KB_PROFILE_T0
         KB_ACC(14, tThr - tRound);  // (make PROFILE=1 VARIANT=.. EXTRA=-DKB_PROFILE_T0: [14] is the a-priori threshold block alone)
+#elif defined(KB_PROFILE_OUT)
+        // (make PROFILE=1 VARIANT=.. EXTRA=-DKB_PROFILE_OUT: [14] is the result-table block alone, stamped where it stands)
 #else
         KB_ACC(14, tF0 - tRound);  // [14] round prologue: the a-priori threshold (rounds 1 and 2) + the control reads
 #endif
@@ -1230,28 +1232,54 @@ __global__ void __launch_bounds__(NW * 64, min_waves_per_simd(NW)) kbest_kernel(
         }
         __syncthreads();
         // -- outputs, as they become final: the slots emitted up to the last round (their states are saved, their slot ->
-        //    state entries written behind a barrier) are widened into row4col / col4row NOW, one slot per wave.  The result tables then leave the kernel spread over its
+        //    state entries written behind a barrier) are widened into row4col / col4row in THIS round, one slot per wave.  The result tables then leave the kernel spread over its
         //    whole run instead of in one burst at the end of every matrix -- which is what a host that takes them over PCIe
-        //    (result tables in pinned host memory, kbest_batch_f64) would otherwise wait for after the last matrix.  At the
-        //    START of the children phase: the stores (microseconds each when they cross PCIe) drain while the children are
-        //    solved, not in front of a barrier.
-        {
+        //    (result tables in pinned host memory, kbest_batch_f64) would otherwise wait for after the last matrix.
+        //    Tables in HOST memory (p.tablesHost): at the START of the children phase: the stores (microseconds each when
+        //    they cross PCIe) drain while the children are solved, not in front of a barrier.
+        //    Tables in DEVICE memory: BEHIND a wave's children, in front of the barrier after B.  The stores are cheap there, the
+        //    loads in front of them are not (the slot's state entry, then two bytes per lane of a state saved many rounds ago: HBM
+        //    round trips, one after the other) -- at the head of B2 every wave paid them before its first child; behind the children
+        //    the waves that run out of children first take the slots while they would wait for the round's last child anyway, and
+        //    the wave with that child finds the queue empty.  Nothing reads the tables or `outDone` before phase D.
+        //    A slot's two state bytes are both in registers before either table store, and the NEXT slot's ticket and state entry
+        //    are fetched before the stores of this one (the child queue's pattern): no load waits for a store's acknowledgement.
+        auto write_tables = [&]() {
+#ifdef KB_PROFILE_OUT
+            KB_T(tOut0);
+#endif
             const int outDone = uni32(ctrl->outDone);
-            for (;;) {
-                int t = 0;
-                if (lane == 0) t = atomicAdd(&ctrl->outTicket, 1);
-                const int sOut = outDone + uni32(t);
-                if (sOut >= emitted) break;
-                if (sOut >= kTab) continue;  // (the solution behind the tables: its gain is all that is kept)
-                const unsigned char *st = stBase + (long long)slotSid[sOut] * p.stateStride;
+            const int outEnd = emitted < kTab ? emitted : kTab;  // (a solution behind the tables: its gain is all that is kept)
+            const bool c4rOn = p.col4row != nullptr;
+            int t = 0;
+            if (lane == 0) t = atomicAdd(&ctrl->outTicket, 1);
+            int sOut = outDone + uni32(t);
+            int sidOut = uni32(sOut < outEnd ? (int)slotSid[sOut] : 0);
+            while (sOut < outEnd) {
+                const unsigned char *st = stBase + (long long)sidOut * p.stateStride;
                 // (the states are in the enumeration's column order: the tables in the reference's)
-                if (lane < M) put_index(p.row4col, (outBase + sOut) * p.ldCol + colOf[lane], st[offR4C + lane], tabI8);
-                if (p.col4row && lane < N) {
-                    const int cv = st[offC4R + lane];
+                int rv = (lane < M) ? (int)st[offR4C + lane] : 0;
+                int cv = (c4rOn && lane < N) ? (int)st[offC4R + lane] : 0;
+                int tn = 0;
+                if (lane == 0) tn = atomicAdd(&ctrl->outTicket, 1);
+                const int sNext = outDone + uni32(tn);
+                const int sidNext = uni32(sNext < outEnd ? (int)slotSid[sNext] : 0);
+                // ONE wait for the three loads, here: the stores below are predicated, and behind a store that may or may not have
+                // been issued the compiler can only wait for a loaded register by waiting for everything, the store's
+                // acknowledgement included
+                asm volatile("" : "+v"(rv), "+v"(cv));
+                if (lane < M) put_index(p.row4col, (outBase + sOut) * p.ldCol + colOf[lane], rv, tabI8);
+                if (c4rOn && lane < N)
                     put_index(p.col4row, (outBase + sOut) * p.ldRow + lane, (rect && cv == 255) ? -1 : (cv < M ? (int)colOf[cv] : cv), tabI8);  // unassigned row (cpp:134)
-                }
+                sOut = sNext;
+                sidOut = sidNext;
             }
-        }
+#ifdef KB_PROFILE_OUT
+            KB_ACC(14, __builtin_readcyclecounter() - tOut0);
+#endif
+        };
+        const bool tablesEarly = p.tablesHost != 0;
+        if (tablesEarly) write_tables();
         // -- B2: surviving children (shortestPathUpdateCPP, gain only), dynamic queue over the survivor list.  The
         //    per-node data a wave needs is cached in registers across consecutive items of the same node, and the
         //    next queue ticket is drawn before the current child is solved so that its LDS round trip is hidden.
@@ -1408,6 +1436,7 @@ __global__ void __launch_bounds__(NW * 64, min_waves_per_simd(NW)) kbest_kernel(
             }
             if ((p.flags & KBEST_FLAG_COUNT_PUSHED) && lane == 0 && npush) atomicAdd(&ctrl->pushed, npush);
         }
+        if (!tablesEarly) write_tables();  // (tables in device memory: in the slack in front of the barrier, see above)
         KB_T(tB1);
         KB_ACC(1, tB1 - tRound);  // [1] phase B busy (this wave)
         __syncthreads();
