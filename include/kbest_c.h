@@ -775,6 +775,64 @@ int kbest_frontier_sample_f64_dev(kbest_ctx *ctx, int n, const int32_t *m, const
                                   int32_t *d_assignLocal, const int64_t *asgOff, double *d_logTerm, const int64_t *ltOff,
                                   double *d_logZ, int32_t *d_info, int32_t *d_width, void *stream);
 /*
+ * Draws for every gated frame (kbest_table_sample.hip; not in the reference): whole joint associations of a cluster no exact tier
+ * takes, drawn from a table of its k best assignments under the weights assignmentProb gives them (assignment.cpp:616-648).
+ *
+ * The distribution.  For one problem: gain[0 .. nf-1] in ascending table order and row4col[j][0 .. m-1], in the layout
+ * kbest_batch_f64_dev writes: [n][k][maxCol] int32, [n][k] double, [n] int32 (an nf beyond k counts as k).
+ *   w_j = exp(gain_0 - gain_j) where gain_0 + cutoff > gain_j, strictly; otherwise slot j is skipped and has weight 0.
+ *   P_j = P_{j-1} + w_j, added left to right from 0.0 in table order; total = P_{nf-1}.
+ *   Draw s takes the FIRST j with T < P_j, where T = u total.  If rounding leaves none, it takes the last j whose weight was > 0.
+ *   logTerm[s] = (gain_0 - gain_j) - log(total): no log of a product.  assignLocal[s][c] = row4col[j][c].  pick[s] = j.
+ * The uniform.  Philox4x32-10.  The key is the seed's two words.  The counter is
+ *     (sampleBase + s, 0x40000000 | clusterKey, frameKey low word, frameKey high word).
+ * u = (((word1 << 32) | word0) >> 11) * 2^-53, from words 0 and 1.  clusterKey < 2^30, else KBEST_ERR_BAD_ARG.
+ * Bit 30 set and bit 31 clear keeps these uniforms disjoint from those of kbest_clustered_sample_assoc_batch_f64, whose second
+ * word is at most 511, and from those of kbest_frontier_sample_f64_dev, whose second word has bit 31 set: no uniform is ever
+ * shared between a small cluster, a frontier cluster and an enumerated cluster of one frame.
+ *
+ * kbest_table_sample_f64_dev: n problems; k (1 .. KBEST_TABLE_SAMPLE_MAX_K: the running sums of a problem lie in LDS) and maxCol
+ * the strides of the tables; m[i] (host) the columns of problem i; d_row4col, d_gain, d_nf on the device; cutoff the reference's
+ * (42 in assignmentProb); clusterKey[i] and frameKeyOfCluster[i] (host, each may be NULL: 0).  Out, on the device:
+ * d_assignLocal + asgOff[i]: int32 [nSample][m_i]; d_logTerm + ltOff[i]: double [nSample]; d_pick (may be NULL): int32 [n][nSample];
+ * d_info[i] (may be NULL): 1 drawn; 0: nf <= 0 (or no slot has a weight > 0) -- assignLocal -1, logTerm NaN, pick -1; -1: m_i
+ * outside 1 .. maxCol -- nothing is touched.  One workgroup of 256 per problem, the grid strides over the problems of a launch,
+ * ONE launch per 64 problems; shapes, offsets and keys travel as kernel arguments: the entry copies nothing, allocates nothing and
+ * needs no reservation.  No workgroup waits for another, no floating-point atomics, no sum over threads: a problem's outputs are a
+ * function of (table, cutoff, seed, keys, draw index) alone.  Asynchronous on `stream` (NULL: the context's).  k outside
+ * 1 .. 4096, maxCol < 1, nSample < 1, sampleBase + nSample > 2^32, a negative offset: KBEST_ERR_BAD_ARG.
+ *
+ * kbest_hybrid_sample_assoc_batch_f64 (host buffers, synchronous): the drawing twin of
+ * kbest_hybrid_frontier_probs_batch_f64(k, maxBig = 0) -- kbest_hybrid_frontier_sample_assoc_batch_f64 with int k after condition
+ * and nEnum after nFrontier, and one body with it.  k = 0: that entry, step for step and bit for bit.  k >= 1 (up to
+ * KBEST_TABLE_SAMPLE_MAX_K): every open cluster the frontier sampler does not take (more than 64 measurements, info < 0,
+ * W > maxWidth, or maxWidth = 0) is enumerated instead of refusing its frame: kBest2DCutoff(k, 42) on the (nL_k + m_k) x m_k
+ * sub-block the partial kernel handed out (use_cutoff = 1, cutoff = 42, KBEST_FLAG_CANONICAL_TIES), all such clusters of a call
+ * as ONE batch, then ONE call of kbest_table_sample_f64_dev with clusterKey = the cluster's label (its first column) and the
+ * frame's key.  So the distribution drawn from is the one whose marginals kbest_hybrid_frontier_probs_batch_f64(k, maxBig = 0)
+ * returns for that cluster.  Local rows map to raw rows through the list the frontier clusters use (the partial kernel's row
+ * list, then the rows >= nL the gate finds, ascending), and ONE loop over the frame's open clusters in label order joins the
+ * draws, whichever tier answered: assign[s][col_j] = the key of the local row (-1 beyond the rows that count),
+ * logProb[s] = logProb[s] + term[s], after the small clusters' sum.
+ *   method[b]: 0 everything exact; 1 every enumeration complete within the cutoff (nf < k); 2 some enumeration cut at k; -2 some
+ *       cluster without a feasible assignment (nf <= 0 included): -1s, NaNs, logPerm -inf; -1 refused by the partial kernel: NaN.
+ *   nEnum[b] (may be NULL): the enumerated clusters of the frame; 0 where method < 0.
+ *   logPerm[b]: the sum over the exactly answered clusters only; the enumerated ones add nothing.
+ *   logProb of a frame with method 1 or 2 is the log-probability under the product of the exact posteriors of its exactly
+ *   answered clusters and the TRUNCATED posteriors (the k best within the cutoff, renormalised) of its enumerated ones.
+ */
+#define KBEST_TABLE_SAMPLE_MAX_K 4096
+int kbest_table_sample_f64_dev(kbest_ctx *ctx, int n, int k, int maxCol, const int32_t *m, const int32_t *d_row4col,
+                               const double *d_gain, const int32_t *d_nf, double cutoff, const uint32_t *clusterKey,
+                               const uint64_t *frameKeyOfCluster, int nSample, uint64_t seed, uint32_t sampleBase,
+                               int32_t *d_assignLocal, const int64_t *asgOff, double *d_logTerm, const int64_t *ltOff,
+                               int32_t *d_pick /* or NULL */, int32_t *d_info, void *stream);
+int kbest_hybrid_sample_assoc_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,
+                                        const int64_t *costOff, int condition, int k, int maxExact, int maxWidth, int nSample,
+                                        uint64_t seed, uint32_t sampleBase, const uint64_t *frameKey, int32_t *assign,
+                                        const int64_t *asgOff, double *logProb, const int64_t *lpOff, double *logPerm, int32_t *method,
+                                        int32_t *nOpen, int32_t *nFrontier, int32_t *nEnum, int32_t *maxCluster);
+/*
  * Asynchronous exact hybrid probabilities (kbest_hybrid.hip; not in the reference): the whole exact path of
  * kbest_hybrid_frontier_probs_batch_f64(k = 0, maxBig = 0) on buffers that already lie on the device, on ONE stream -- the partial
  * clustered kernel, a gather of the open clusters of all frames into one list (frame order, then label order: a prefix sum, no

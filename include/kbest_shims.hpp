@@ -154,6 +154,13 @@ std::vector<std::vector<int>> clusterSampleAssoc(const std::vector<double> &cost
 std::vector<std::vector<int>> hybridFrontierSampleAssoc(const std::vector<double> &costMatrix, size_t nL, size_t nM, size_t nSample,
                                                         uint64_t seed);
 
+// Not in the reference: hybridFrontierSampleAssoc for EVERY gated frame (kbest_hybrid_sample_assoc_batch_f64, frame key 0): a cluster
+// no exact tier takes is drawn from its k best assignments within the cutoff 42 under assignmentProb's weights (k >= 1; k = 0 refuses
+// such a frame, as hybridFrontierSampleAssoc does).  [nSample][nM] as clusterSampleAssoc.  Throws std::runtime_error when the frame is
+// refused, and when the frame has no consistent association.
+std::vector<std::vector<int>> hybridSampleAssoc(const std::vector<double> &costMatrix, size_t nL, size_t nM, size_t nSample, size_t k,
+                                                uint64_t seed = 0);
+
 // Not in the reference: the hybrid association probabilities (kbest_hybrid_probs_batch_f64), [nM][nL+1] like assignmentProb, for
 // frames of up to 128 measurements and 1 024 rows: exact on every cluster of at most 16 measurements, assignmentProb(k) on the
 // larger ones alone.  Throws std::runtime_error only when the frame is refused (method -1: not the reference's layout of miss

@@ -20,6 +20,7 @@
 
 #include "kbest_c.h"
 #include "kbest_engine.h"
+#include "kbest_table_sample.h"
 
 namespace kb {
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -4011,6 +4012,45 @@ int kbest_frontier_sample_f64_dev(kbest_ctx *ctx, int n, const int32_t *m, const
     return KBEST_OK;
 }
 
+// ---- draws from tables of k best assignments (kbest_table_sample.hip): no work space, the problems travel in packs --------------
+int kbest_table_sample_f64_dev(kbest_ctx *ctx, int n, int k, int maxCol, const int32_t *m, const int32_t *d_row4col,
+                               const double *d_gain, const int32_t *d_nf, double cutoff, const uint32_t *clusterKey,
+                               const uint64_t *frameKeyOfCluster, int nSample, uint64_t seed, uint32_t sampleBase,
+                               int32_t *d_assignLocal, const int64_t *asgOff, double *d_logTerm, const int64_t *ltOff,
+                               int32_t *d_pick, int32_t *d_info, void *stream)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    if (n < 0 || k < 1 || k > KBEST_TABLE_SAMPLE_MAX_K || maxCol < 1 || maxCol > KBEST_MAX_DIM_EXACT || nSample < 1 ||
+        (uint64_t)sampleBase + (uint64_t)nSample > ((uint64_t)1 << 32) ||
+        (n > 0 && (!m || !d_row4col || !d_gain || !d_nf || !d_assignLocal || !asgOff || !d_logTerm || !ltOff)))
+        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_table_sample_f64_dev: bad argument (k 1 .. 4096, maxCol 1 .. 16384, nSample >= 1, "
+                                            "sampleBase + nSample <= 2^32)");
+    if (n == 0) return KBEST_OK;
+    for (int i = 0; i < n; i++)  // everything is checked before anything is launched
+        if (asgOff[i] < 0 || ltOff[i] < 0 || (clusterKey && clusterKey[i] >= kb::TS_MAX_KEY))
+            return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_table_sample_f64_dev: a problem with a negative offset or a clusterKey >= 2^30");
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    kb::TableSamplePack pk;
+    for (int at = 0; at < n; at += kb::KB_TABLE_SAMPLE_PACK) {
+        pk.n = n - at < kb::KB_TABLE_SAMPLE_PACK ? n - at : kb::KB_TABLE_SAMPLE_PACK;
+        pk.base = at;
+        for (int j = 0; j < pk.n; j++) {
+            pk.c[j].asgOff = asgOff[at + j];
+            pk.c[j].ltOff = ltOff[at + j];
+            pk.c[j].frameKey = frameKeyOfCluster ? frameKeyOfCluster[at + j] : 0;
+            pk.c[j].clusterKey = clusterKey ? clusterKey[at + j] : 0;
+            pk.c[j].m = m[at + j];
+        }
+        const hipError_t e = static_cast<hipError_t>(kb::launch_table_sample_pack(pk, k, maxCol, d_row4col, d_gain, d_nf, cutoff, nSample,
+                                                                                  seed, sampleBase, d_assignLocal, d_logTerm, d_pick,
+                                                                                  d_info, s));
+        if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "table sampling kernel launch", e);
+    }
+    return KBEST_OK;
+}
+
 // ---- the exact hybrid path on the device (kbest_hybrid.hip): partial kernel, gather, frontier sweep, scatter, on one stream ------
 // Where everything lies in ctx->hybBuf for a call of (B, maxRawRow, maxCol), in bytes; every part is 16-byte aligned.  Each
 // size grows with each of the three, so a call within what was reserved fits.
@@ -4517,20 +4557,15 @@ struct FrameGate {
     bool nonzero(int c, int r) const { return kept[r] && mn + 42.0 > value(c, r); }
 };
 
-int kbest_hybrid_frontier_sample_assoc_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,
-                                                 const int64_t *costOff, int condition, int maxExact, int maxWidth, int nSample,
-                                                 uint64_t seed, uint32_t sampleBase, const uint64_t *frameKey, int32_t *assign,
-                                                 const int64_t *asgOff, double *logProb, const int64_t *lpOff, double *logPerm,
-                                                 int32_t *method, int32_t *nOpen, int32_t *nFrontier, int32_t *maxCluster)
+// One body for kbest_hybrid_frontier_sample_assoc_batch_f64 (k = 0: an open cluster the frontier sampler does not take refuses its
+// frame) and kbest_hybrid_sample_assoc_batch_f64 (k >= 1: such a cluster is enumerated -- kBest2DCutoff(k, 42) on its sub-block,
+// all of a call in one batch -- and drawn from its table by kbest_table_sample.hip).  The callers have checked the arguments.
+static int hybrid_sample_impl(kbest_ctx *ctx, const char *who, int B, const int32_t *nL, const int32_t *nM, const double *cost,
+                              const int64_t *costOff, int condition, int k, int maxExact, int maxWidth, int nSample, uint64_t seed,
+                              uint32_t sampleBase, const uint64_t *frameKey, int32_t *assign, const int64_t *asgOff, double *logProb,
+                              const int64_t *lpOff, double *logPerm, int32_t *method, int32_t *nOpen, int32_t *nFrontier,
+                              int32_t *nEnum, int32_t *maxCluster)
 {
-    if (!ctx) return KBEST_ERR_BAD_ARG;
-    const char *who = "kbest_hybrid_frontier_sample_assoc_batch_f64";
-    if (B < 0 || maxExact < 0 || maxExact > KBEST_CLUSTER_MAX_SIZE || maxWidth < 0 || maxWidth > KBEST_FRONTIER_MAX_WIDTH || nSample < 1 ||
-        (uint64_t)sampleBase + (uint64_t)nSample > ((uint64_t)1 << 32) ||
-        (B > 0 && (!nL || !nM || !cost || !costOff || !assign || !asgOff || !logProb || !lpOff || !method)))
-        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_hybrid_frontier_sample_assoc_batch_f64: bad argument (maxExact 0 .. 16, maxWidth 0 .. 16, "
-                                            "nSample >= 1, sampleBase + nSample <= 2^32)");
-    if (B == 0) return KBEST_OK;
     std::vector<int64_t> pOff(B);  // the partial kernel's probabilities: packed, and dropped
     {
         int64_t at = 0;
@@ -4547,7 +4582,7 @@ int kbest_hybrid_frontier_sample_assoc_batch_f64(kbest_ctx *ctx, int B, const in
     if (rc != KBEST_OK) return rc;
     size_t asgN = 0, lpN = 0;  // int32s / doubles up to the end of the last frame's draws
     for (int b = 0; b < B; b++) {
-        if (asgOff[b] < 0 || lpOff[b] < 0) return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_hybrid_frontier_sample_assoc_batch_f64: a negative offset");
+        if (asgOff[b] < 0 || lpOff[b] < 0) return fail(ctx, KBEST_ERR_BAD_ARG, (std::string(who) + ": a negative offset").c_str());
         asgN = std::max(asgN, (size_t)asgOff[b] + (size_t)nSample * (size_t)nM[b]);
         lpN = std::max(lpN, (size_t)lpOff[b] + (size_t)nSample);
     }
@@ -4585,8 +4620,9 @@ int kbest_hybrid_frontier_sample_assoc_batch_f64(kbest_ctx *ctx, int B, const in
     HIP_TRY(ctx, hipMemcpy(hLp.data(), dLp.p, (size_t)B * 8, hipMemcpyDeviceToHost));
     HIP_TRY(ctx, hipMemcpy(sLp.data(), s8, (size_t)B * 8, hipMemcpyDeviceToHost));
     const int32_t *hInfo = hInt.data(), *hOpen = hInt.data() + 2 * (size_t)B;
-    // every open cluster, in frame and label order; sent: through the sampler (at most 64 measurements); at: its place there
-    struct Open { int b, root, m, cL, R; size_t rowAt, from; int at; bool taken; };
+    // every open cluster, in frame and label order; at: its place in the frontier sampler's call (at most 64 measurements), taken:
+    // answered there; en: its place in the enumeration (k >= 1: whatever that sampler leaves); keyAt: its row keys in rowKey
+    struct Open { int b, root, m, cL, R; size_t rowAt, from; int at; bool taken; int en; int64_t keyAt; };
     std::vector<Open> open;
     bool any = false;
     for (int b = 0; b < B; b++) any = any || hOpen[b] > 0;
@@ -4594,6 +4630,9 @@ int kbest_hybrid_frontier_sample_assoc_batch_f64(kbest_ctx *ctx, int B, const in
     std::vector<int64_t> fSo, fKo, fAo, fLo;
     std::vector<uint64_t> fKey;
     std::vector<double> fLogZ, hTerm;
+    std::vector<int32_t> eNf, eInfo, eLocal;  // the enumerated clusters: the counts of their tables, the table sampler's info and rows
+    std::vector<int64_t> eAo;                 // ... and where the rows of each lie
+    std::vector<double> eTerm;
     if (any) {
         hDesc.resize((size_t)B * descStride * 4);
         hRows.resize((size_t)B * rowStride);
@@ -4609,20 +4648,24 @@ int kbest_hybrid_frontier_sample_assoc_batch_f64(kbest_ctx *ctx, int B, const in
             if (hOpen[b] > 0) gate.make(cost + costOff[b], nL[b], nM[b], condition != 0);
             for (int j = 0; j < hOpen[b]; j++) {
                 const int32_t *d = hDesc.data() + ((size_t)b * descStride + j) * 4;
-                Open o{b, d[0], d[1], d[2], d[3], rowAt, n, -1, false};
+                Open o{b, d[0], d[1], d[2], d[3], rowAt, n, -1, false, -1, -1};
                 n += (size_t)(o.cL + o.m) * o.m;
                 rowAt += (size_t)o.cL;
-                if (o.m <= KBEST_FRONTIER_MAX_COLS) {
+                const bool toFrontier = o.m <= KBEST_FRONTIER_MAX_COLS;
+                if (toFrontier || k >= 1) {
                     // q of every row of the sub-block: the RAW row of the caller's block (the all-+inf rows behind them are no steps)
-                    o.at = (int)fM.size();
-                    fM.push_back(o.m);
-                    fL.push_back(o.cL);
-                    fSo.push_back(costOff[b] + (int64_t)o.from);
-                    fKo.push_back((int64_t)rowKey.size());
-                    fAo.push_back((int64_t)asgAt);
-                    fLo.push_back((int64_t)o.at * nSample);
-                    fKey.push_back(frameKey ? frameKey[b] : (uint64_t)b);
-                    asgAt += (size_t)nSample * o.m;
+                    o.keyAt = (int64_t)rowKey.size();
+                    if (toFrontier) {
+                        o.at = (int)fM.size();
+                        fM.push_back(o.m);
+                        fL.push_back(o.cL);
+                        fSo.push_back(costOff[b] + (int64_t)o.from);
+                        fKo.push_back(o.keyAt);
+                        fAo.push_back((int64_t)asgAt);
+                        fLo.push_back((int64_t)o.at * nSample);
+                        fKey.push_back(frameKey ? frameKey[b] : (uint64_t)b);
+                        asgAt += (size_t)nSample * o.m;
+                    }
                     for (int r = 0; r < o.cL; r++) rowKey.push_back(hRows[o.rowAt + r]);
                     int found = 0;
                     const int32_t *lab = hLabel.data() + (size_t)b * maxCol;
@@ -4632,10 +4675,10 @@ int kbest_hybrid_frontier_sample_assoc_batch_f64(kbest_ctx *ctx, int B, const in
                         if (in && found < o.m) rowKey.push_back(r);
                         found += in ? 1 : 0;
                     }
-                    if (found != o.R - o.cL) return fail(ctx, KBEST_ERR_INTERNAL, "kbest_hybrid_frontier_sample_assoc_batch_f64: the rows of an open cluster");
+                    if (found != o.R - o.cL) return fail(ctx, KBEST_ERR_INTERNAL, (std::string(who) + ": the rows of an open cluster").c_str());
                     for (int r = o.R; r < o.cL + o.m; r++) rowKey.push_back(0);
-                    if (o.m > frM) frM = o.m;
-                    if (o.cL + o.m > frRows) frRows = o.cL + o.m;
+                    if (toFrontier && o.m > frM) frM = o.m;
+                    if (toFrontier && o.cL + o.m > frRows) frRows = o.cL + o.m;
                 }
                 open.push_back(o);
             }
@@ -4670,6 +4713,84 @@ int kbest_hybrid_frontier_sample_assoc_batch_f64(kbest_ctx *ctx, int B, const in
             for (Open &o : open)
                 if (o.at >= 0 && fInfo[o.at] >= 0 && fWidth[o.at] <= maxWidth) o.taken = true;
         }
+        if (k >= 1) {
+            // the k-best leg: every open cluster nobody took, of the frames the partial kernel answered -- the sub-blocks come to the
+            // host (a frame's in one copy), go through the engine as ONE batch (kBest2DCutoff(k, 42), the engine's rule on ties), and
+            // the tables go back for ONE call of the table sampler
+            std::vector<int32_t> eRow, eCol;
+            std::vector<int64_t> eCo, eLo;
+            std::vector<uint32_t> eKeyC;
+            std::vector<uint64_t> eKeyF;
+            std::vector<double> sub;
+            int eMaxRow = 1, eMaxCol = 1;
+            size_t eAsg = 0;
+            for (size_t i = 0; i < open.size();) {  // frame by frame
+                size_t e = i;
+                while (e < open.size() && open[e].b == open[i].b) e++;
+                const int b = open[i].b;
+                size_t n = 0;
+                bool need = false;
+                for (size_t t = i; t < e; t++) {
+                    n += (size_t)(open[t].cL + open[t].m) * open[t].m;
+                    need = need || !open[t].taken;
+                }
+                if (need && hInfo[b] > 0) {
+                    const size_t base = sub.size();
+                    sub.resize(base + n);
+                    HIP_TRY(ctx, hipMemcpy(sub.data() + base, dSub.as<double>() + costOff[b], n * 8, hipMemcpyDeviceToHost));
+                    for (size_t t = i; t < e; t++) {
+                        Open &o = open[t];
+                        if (o.taken) continue;
+                        o.en = (int)eRow.size();
+                        eRow.push_back(o.cL + o.m);
+                        eCol.push_back(o.m);
+                        eCo.push_back((int64_t)(base + o.from));
+                        eLo.push_back((int64_t)o.en * nSample);
+                        eKeyC.push_back((uint32_t)o.root);
+                        eKeyF.push_back(frameKey ? frameKey[b] : (uint64_t)b);
+                        eAo.push_back((int64_t)eAsg);
+                        eAsg += (size_t)nSample * o.m;
+                        if (o.cL + o.m > eMaxRow) eMaxRow = o.cL + o.m;
+                        if (o.m > eMaxCol) eMaxCol = o.m;
+                    }
+                }
+                i = e;
+            }
+            const int E = (int)eRow.size();
+            if (E > 0) {
+                std::vector<int32_t> r4c((size_t)E * k * eMaxCol);
+                std::vector<double> gain((size_t)E * k);
+                eNf.assign(E, 0);
+                kbest_opts op;
+                kbest_default_opts(&op);
+                op.use_cutoff = 1;  // assignment.cpp:594: kBest2DCutoff(..., cutoff = 42)
+                op.cutoff = 42.0;
+                op.flags |= KBEST_FLAG_CANONICAL_TIES;
+                rc = kbest_batch_f64(ctx, &op, E, eMaxRow, eMaxCol, eRow.data(), eCol.data(), sub.data(), eCo.data(), k, r4c.data(), nullptr,
+                                     gain.data(), eNf.data(), nullptr);
+                if (rc != KBEST_OK) return rc;
+                DevBuf dTab, dGain, dNf, dELocal, dETerm, dEInfo;
+                hipError_t e;
+                if ((e = dTab.alloc(ctx, r4c.size() * 4)) != hipSuccess || (e = dGain.alloc(ctx, gain.size() * 8)) != hipSuccess ||
+                    (e = dNf.alloc(ctx, (size_t)E * 4)) != hipSuccess || (e = dELocal.alloc(ctx, eAsg * 4)) != hipSuccess ||
+                    (e = dETerm.alloc(ctx, (size_t)E * nSample * 8)) != hipSuccess || (e = dEInfo.alloc(ctx, (size_t)E * 4)) != hipSuccess)
+                    return fail(ctx, KBEST_ERR_NOMEM, (std::string(who) + ": device buffers").c_str(), e);
+                HIP_TRY(ctx, hipMemcpy(dTab.p, r4c.data(), r4c.size() * 4, hipMemcpyHostToDevice));
+                HIP_TRY(ctx, hipMemcpy(dGain.p, gain.data(), gain.size() * 8, hipMemcpyHostToDevice));
+                HIP_TRY(ctx, hipMemcpy(dNf.p, eNf.data(), (size_t)E * 4, hipMemcpyHostToDevice));
+                rc = kbest_table_sample_f64_dev(ctx, E, k, eMaxCol, eCol.data(), dTab.as<int32_t>(), dGain.as<double>(), dNf.as<int32_t>(), 42.0,
+                                                eKeyC.data(), eKeyF.data(), nSample, seed, sampleBase, dELocal.as<int32_t>(), eAo.data(),
+                                                dETerm.as<double>(), eLo.data(), nullptr, dEInfo.as<int32_t>(), nullptr);
+                if (rc != KBEST_OK) return rc;
+                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+                eLocal.resize(eAsg);
+                eTerm.resize((size_t)E * nSample);
+                eInfo.resize(E);
+                HIP_TRY(ctx, hipMemcpy(eLocal.data(), dELocal.p, eAsg * 4, hipMemcpyDeviceToHost));
+                HIP_TRY(ctx, hipMemcpy(eTerm.data(), dETerm.p, eTerm.size() * 8, hipMemcpyDeviceToHost));
+                HIP_TRY(ctx, hipMemcpy(eInfo.data(), dEInfo.p, (size_t)E * 4, hipMemcpyDeviceToHost));
+            }
+        }
     }
     std::vector<int32_t> hAsg(asgN);
     std::vector<double> hLpS(lpN);
@@ -4677,25 +4798,36 @@ int kbest_hybrid_frontier_sample_assoc_batch_f64(kbest_ctx *ctx, int B, const in
     HIP_TRY(ctx, hipMemcpy(hLpS.data(), dLpS.p, lpN * 8, hipMemcpyDeviceToHost));
     // method, nFrontier: as kbest_hybrid_frontier_probs_batch_f64(k = 0, maxBig = 0) decides them
     for (int b = 0; b < B; b++) method[b] = hInfo[b] < 0 ? -1 : hInfo[b] == 0 ? -2 : 0;
-    std::vector<int32_t> nFr(B, 0);
+    // (k >= 1: an enumerated cluster decides as in kbest_hybrid_frontier_probs_batch_f64(k, maxBig = 0) -- 1: complete within the
+    //  cutoff, 2: cut at k, -2: no feasible assignment; a cluster left alone belongs to a frame that is -1 or -2 already)
+    std::vector<int32_t> nFr(B, 0), nEn(B, 0);
     std::vector<char> refused(B, 0);
     for (const Open &o : open) {
-        if (!o.taken) refused[o.b] = 1;
-        else if (fInfo[o.at] <= 0) method[o.b] = -2;
-        else nFr[o.b]++;
+        if (o.taken) {
+            if (fInfo[o.at] <= 0) method[o.b] = -2;
+            else nFr[o.b]++;
+        } else if (k < 1) {
+            refused[o.b] = 1;
+        } else if (o.en >= 0) {
+            if (eNf[o.en] <= 0 || eInfo[o.en] <= 0) method[o.b] = -2;
+            else if (method[o.b] >= 0) method[o.b] = (eNf[o.en] >= k || method[o.b] == 2) ? 2 : 1;
+            nEn[o.b]++;
+        }
     }
     for (int b = 0; b < B; b++) {
         if (refused[b]) method[b] = -1;
         if (method[b] < 0 && hOpen[b] > 0) nFr[b] = 0;
+        if (method[b] < 0) nEn[b] = 0;
     }
-    // the draws: the small clusters' columns and terms are the sampler's; the open clusters' follow, in label order
+    // the draws: the small clusters' columns and terms are the sampler's; the open clusters' follow, in label order, whichever
+    // tier answered
     const double QNAN = std::numeric_limits<double>::quiet_NaN();
     for (const Open &o : open) {
-        if (method[o.b] != 0) continue;
+        if (method[o.b] < 0) continue;
         const int b = o.b, M = nM[b];
-        const int32_t *lab = hLabel.data() + (size_t)b * maxCol, *keys = rowKey.data() + fKo[o.at];
-        const int32_t *loc = hLocal.data() + fAo[o.at];
-        const double *term = hTerm.data() + fLo[o.at];
+        const int32_t *lab = hLabel.data() + (size_t)b * maxCol, *keys = rowKey.data() + o.keyAt;
+        const int32_t *loc = o.taken ? hLocal.data() + fAo[o.at] : eLocal.data() + eAo[o.en];
+        const double *term = o.taken ? hTerm.data() + fLo[o.at] : eTerm.data() + (size_t)o.en * nSample;
         int32_t *fa = hAsg.data() + asgOff[b];
         double *fl = hLpS.data() + lpOff[b];
         std::vector<int> cols;
@@ -4710,7 +4842,7 @@ int kbest_hybrid_frontier_sample_assoc_batch_f64(kbest_ctx *ctx, int B, const in
         }
     }
     for (int b = 0; b < B; b++) {
-        if (method[b] != 0) {
+        if (method[b] < 0) {
             std::fill(hAsg.begin() + asgOff[b], hAsg.begin() + asgOff[b] + (size_t)nSample * (size_t)nM[b], -1);
             std::fill(hLpS.begin() + lpOff[b], hLpS.begin() + lpOff[b] + (size_t)nSample, QNAN);
         }
@@ -4744,8 +4876,45 @@ int kbest_hybrid_frontier_sample_assoc_batch_f64(kbest_ctx *ctx, int B, const in
     }
     if (nOpen) memcpy(nOpen, hOpen, (size_t)B * 4);
     if (nFrontier) memcpy(nFrontier, nFr.data(), (size_t)B * 4);
+    if (nEnum) memcpy(nEnum, nEn.data(), (size_t)B * 4);
     if (maxCluster) memcpy(maxCluster, hInt.data() + B, (size_t)B * 4);
     return KBEST_OK;
+}
+
+int kbest_hybrid_frontier_sample_assoc_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,
+                                                 const int64_t *costOff, int condition, int maxExact, int maxWidth, int nSample,
+                                                 uint64_t seed, uint32_t sampleBase, const uint64_t *frameKey, int32_t *assign,
+                                                 const int64_t *asgOff, double *logProb, const int64_t *lpOff, double *logPerm,
+                                                 int32_t *method, int32_t *nOpen, int32_t *nFrontier, int32_t *maxCluster)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    if (B < 0 || maxExact < 0 || maxExact > KBEST_CLUSTER_MAX_SIZE || maxWidth < 0 || maxWidth > KBEST_FRONTIER_MAX_WIDTH || nSample < 1 ||
+        (uint64_t)sampleBase + (uint64_t)nSample > ((uint64_t)1 << 32) ||
+        (B > 0 && (!nL || !nM || !cost || !costOff || !assign || !asgOff || !logProb || !lpOff || !method)))
+        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_hybrid_frontier_sample_assoc_batch_f64: bad argument (maxExact 0 .. 16, maxWidth 0 .. 16, "
+                                            "nSample >= 1, sampleBase + nSample <= 2^32)");
+    if (B == 0) return KBEST_OK;
+    return hybrid_sample_impl(ctx, "kbest_hybrid_frontier_sample_assoc_batch_f64", B, nL, nM, cost, costOff, condition, 0, maxExact, maxWidth,
+                              nSample, seed, sampleBase, frameKey, assign, asgOff, logProb, lpOff, logPerm, method, nOpen, nFrontier, nullptr,
+                              maxCluster);
+}
+
+int kbest_hybrid_sample_assoc_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,
+                                        const int64_t *costOff, int condition, int k, int maxExact, int maxWidth, int nSample,
+                                        uint64_t seed, uint32_t sampleBase, const uint64_t *frameKey, int32_t *assign,
+                                        const int64_t *asgOff, double *logProb, const int64_t *lpOff, double *logPerm, int32_t *method,
+                                        int32_t *nOpen, int32_t *nFrontier, int32_t *nEnum, int32_t *maxCluster)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    if (B < 0 || k < 0 || k > KBEST_TABLE_SAMPLE_MAX_K || maxExact < 0 || maxExact > KBEST_CLUSTER_MAX_SIZE || maxWidth < 0 ||
+        maxWidth > KBEST_FRONTIER_MAX_WIDTH || nSample < 1 || (uint64_t)sampleBase + (uint64_t)nSample > ((uint64_t)1 << 32) ||
+        (B > 0 && (!nL || !nM || !cost || !costOff || !assign || !asgOff || !logProb || !lpOff || !method)))
+        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_hybrid_sample_assoc_batch_f64: bad argument (k 0 .. 4096, maxExact 0 .. 16, maxWidth 0 .. 16, "
+                                            "nSample >= 1, sampleBase + nSample <= 2^32)");
+    if (B == 0) return KBEST_OK;
+    return hybrid_sample_impl(ctx, "kbest_hybrid_sample_assoc_batch_f64", B, nL, nM, cost, costOff, condition, k, maxExact, maxWidth, nSample,
+                              seed, sampleBase, frameKey, assign, asgOff, logProb, lpOff, logPerm, method, nOpen, nFrontier, nEnum,
+                              maxCluster);
 }
 
 // ---- the same draws on the device (kbest_hybrid_sample.hip): everything the entry above does on the host between its kernels,

@@ -341,6 +341,28 @@ std::vector<std::vector<int>> hybridFrontierSampleAssoc(const std::vector<double
     return out;
 }
 
+std::vector<std::vector<int>> hybridSampleAssoc(const std::vector<double> &costMatrix, size_t nL, size_t nM, size_t nSample, size_t k,
+                                                uint64_t seed)
+{
+    kbest_ctx *ctx = global_ctx();
+    const int32_t l = (int32_t)nL, m = (int32_t)nM;
+    const int64_t zero = 0;
+    const uint64_t key = 0;
+    int32_t method = 0, maxCluster = 0;
+    std::vector<int32_t> flat(nSample * nM);
+    std::vector<double> logProb(nSample);
+    check(ctx, kbest_hybrid_sample_assoc_batch_f64(ctx, 1, &l, &m, costMatrix.data(), &zero, 0, (int)k, KBEST_CLUSTER_MAX_SIZE,
+                                                   KBEST_FRONTIER_MAX_WIDTH, (int)nSample, seed, 0, &key, flat.data(), &zero, logProb.data(),
+                                                   &zero, nullptr, &method, nullptr, nullptr, nullptr, &maxCluster));
+    if (method == -1)
+        throw std::runtime_error("hybridSampleAssoc: frame refused: its largest cluster has " + std::to_string(maxCluster) + " measurements");
+    if (method == -2)
+        throw std::runtime_error("hybridSampleAssoc: the frame has no consistent association (some cluster has no feasible assignment)");
+    std::vector<std::vector<int>> out(nSample);
+    for (size_t s = 0; s < nSample; s++) out[s].assign(flat.begin() + s * nM, flat.begin() + (s + 1) * nM);
+    return out;
+}
+
 std::vector<std::vector<double>> hybridProb(const std::vector<double> &costMatrix, size_t nL, size_t nM, size_t k)
 {
     kbest_ctx *ctx = global_ctx();

@@ -66,6 +66,7 @@ C_ABI_SYMBOLS = (
     "kbest_reserve_hybrid_dev", "kbest_hybrid_frontier_probs_batch_f64_dev",
     "kbest_reserve_frontier_sample", "kbest_frontier_sample_f64_dev", "kbest_hybrid_frontier_sample_assoc_batch_f64",
     "kbest_reserve_hybrid_sample_dev", "kbest_hybrid_frontier_sample_assoc_batch_f64_dev",
+    "kbest_table_sample_f64_dev", "kbest_hybrid_sample_assoc_batch_f64",
     "kbest_bb_costs_f64",
 )
 KBEST_MULTI_STAMPS = 6
@@ -230,6 +231,12 @@ def load_library():
         lib.kbest_hybrid_frontier_sample_assoc_batch_f64_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int, i32p, i32p, dp, i64p, C.c_int,
                                                                          C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint32, i64p, dp,
                                                                          i32p, i64p, dp, i64p, dp, i32p, i32p, i32p, i32p, vp]
+    if hasattr(lib, "kbest_table_sample_f64_dev"):
+        lib.kbest_table_sample_f64_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int, i32p, i32p, dp, i32p, C.c_double, i32p, i64p, C.c_int,
+                                                   C.c_uint64, C.c_uint32, i32p, i64p, dp, i64p, i32p, i32p, vp]
+        lib.kbest_hybrid_sample_assoc_batch_f64.argtypes = [vp, C.c_int, i32p, i32p, dp, i64p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                            C.c_int, C.c_uint64, C.c_uint32, i64p, i32p, i64p, dp, i64p, dp, i32p,
+                                                            i32p, i32p, i32p, i32p]
     lib.kbest_register_host_buffer.argtypes = [vp, vp, C.c_size_t]
     lib.kbest_unregister_host_buffer.argtypes = [vp, vp]
     _lib = lib
@@ -691,6 +698,53 @@ class KBestEngine:
             _ptr(nOpen), _ptr(nFrontier), _ptr(maxCluster)))
         return ([assign[asgOff[b]: asgOff[b] + n_sample * int(nM[b])].reshape(n_sample, int(nM[b])) for b in range(B)],
                 [logp[lpOff[b]: lpOff[b] + n_sample] for b in range(B)], logPerm, method, nOpen, nFrontier, maxCluster)
+
+    def hybrid_sample_assoc(self, costs, nL, nM, n_sample, k, seed=0, condition=False, frame_key=None, sample_base=0, max_exact=16,
+                            max_width=16):
+        """kbest_hybrid_sample_assoc_batch_f64: hybrid_frontier_sample_assoc() for EVERY gated frame -- with k >= 1 an open cluster
+        the frontier sampler does not take is enumerated (kBest2DCutoff(k, 42) on its sub-block) and drawn from its table under
+        assignmentProb's weights, instead of refusing the frame; k = 0 is hybrid_frontier_sample_assoc() bit for bit.  Returns
+        (list of int32 [n_sample, nM] arrays: the raw row every measurement takes, list of logProb [n_sample], logPerm[B] (the exactly
+        answered clusters only), method[B]: 0 all exact, 1 every enumeration complete, 2 some cut at k, -1 refused, -2 infeasible
+        (assign -1, logProb NaN), nOpen[B], nFrontier[B], nEnum[B], maxCluster[B])."""
+        nL, nM, B, flat, costOff, _, _, _ = _pack_frames(costs, nL, nM, "hybrid_sample_assoc")
+        n_sample = int(n_sample)
+        sizes = n_sample * nM.astype(np.int64)
+        asgOff = np.concatenate(([0], np.cumsum(sizes)[:-1])).astype(np.int64) if B else np.zeros(0, np.int64)
+        lpOff = (np.arange(B, dtype=np.int64) * n_sample)
+        assign = np.zeros(int(sizes.sum()) if B else 0, np.int32)
+        logp = np.zeros(B * n_sample, np.float64)
+        logPerm = np.zeros(B, np.float64)
+        method, nOpen, nFrontier, nEnum, maxCluster = (np.zeros(B, np.int32) for _ in range(5))
+        key = None if frame_key is None else np.ascontiguousarray(frame_key, dtype=np.uint64)
+        if key is not None and len(key) != B:
+            raise ValueError("hybrid_sample_assoc: one frame key per frame")
+        self._check(self.lib.kbest_hybrid_sample_assoc_batch_f64(
+            self.ctx, B, _ptr(nL), _ptr(nM), _ptr(flat), _ptr(costOff), int(bool(condition)), int(k), int(max_exact), int(max_width),
+            n_sample, int(seed), int(sample_base), _ptr(key), _ptr(assign), _ptr(asgOff), _ptr(logp), _ptr(lpOff), _ptr(logPerm),
+            _ptr(method), _ptr(nOpen), _ptr(nFrontier), _ptr(nEnum), _ptr(maxCluster)))
+        return ([assign[asgOff[b]: asgOff[b] + n_sample * int(nM[b])].reshape(n_sample, int(nM[b])) for b in range(B)],
+                [logp[lpOff[b]: lpOff[b] + n_sample] for b in range(B)], logPerm, method, nOpen, nFrontier, nEnum, maxCluster)
+
+    def table_sample_dev(self, k, maxCol, m, d_row4col, d_gain, d_nf, n_sample, d_assignLocal, asgOff, d_logTerm, ltOff, d_pick=None,
+                         d_info=None, cutoff=42.0, cluster_key=None, frame_key=None, seed=0, sample_base=0, stream=None):
+        """kbest_table_sample_f64_dev, asynchronous on `stream`: n_sample joint associations of every problem, drawn from its table
+        of k best assignments (d_row4col [n][k][maxCol] int32, d_gain [n][k], d_nf [n]: what kbest_batch_f64_dev writes) under
+        the weights w_j = exp(gain_0 - gain_j) within the cutoff.  m[i] (host) the columns of problem i; cluster_key[i] < 2^30 and
+        frame_key[i] (host, None: 0) the generator's keys.  Out: d_assignLocal at asgOff[i] [n_sample][m_i] = the picked slot's
+        rows, d_logTerm at ltOff[i] [n_sample], d_pick (optional) [n][n_sample] the slot.  info 1 drawn, 0 nothing to draw from
+        (-1, NaN, -1), -1 m outside 1 .. maxCol (untouched)."""
+        m = np.ascontiguousarray(m, dtype=np.int32)
+        asgOff = np.ascontiguousarray(asgOff, dtype=np.int64)
+        ltOff = np.ascontiguousarray(ltOff, dtype=np.int64)
+        ck = None if cluster_key is None else np.ascontiguousarray(cluster_key, dtype=np.uint32)
+        fk = None if frame_key is None else np.ascontiguousarray(frame_key, dtype=np.uint64)
+        if (ck is not None and len(ck) != len(m)) or (fk is not None and len(fk) != len(m)) or len(asgOff) != len(m) or len(ltOff) != len(m):
+            raise ValueError("table_sample_dev: one key and one offset per problem")
+        self._check(self.lib.kbest_table_sample_f64_dev(self.ctx, len(m), int(k), int(maxCol), _ptr(m), _dptr(d_row4col), _dptr(d_gain),
+                                                        _dptr(d_nf), float(cutoff), _ptr(ck), _ptr(fk), int(n_sample), int(seed),
+                                                        int(sample_base), _dptr(d_assignLocal), _ptr(asgOff), _dptr(d_logTerm),
+                                                        _ptr(ltOff), _dptr(d_pick), _dptr(d_info), _stream(stream)))
 
     def reserve_frontier_sample(self, n, maxM, maxRows):
         """kbest_reserve_frontier_sample: the work space of frontier_sample_dev -- exactly what reserve_frontier() reserves."""
@@ -1181,6 +1235,18 @@ def hybridFrontierSampleAssoc(costMatrix, nL, nM, nSample, seed=0):
         raise RuntimeError(f"hybridFrontierSampleAssoc: frame refused: its largest cluster has {int(maxCluster[0])} measurements")
     if method[0] == -2:
         raise RuntimeError("hybridFrontierSampleAssoc: the frame has no consistent association (some cluster's permanent is 0)")
+    return asg[0]
+
+
+def hybridSampleAssoc(costMatrix, nL, nM, nSample, k, seed=0):
+    """Not in the reference: hybridFrontierSampleAssoc for EVERY gated frame of up to 128 measurements: a cluster no exact tier
+    takes is drawn from its k best assignments within the cutoff 42 under assignmentProb's weights (k >= 1; k = 0 refuses such a
+    frame).  Returns int32 [nSample][nM]; raises RuntimeError when the frame is refused or has no consistent association."""
+    asg, _, _, method, _, _, _, maxCluster = _engine().hybrid_sample_assoc([costMatrix], [nL], [nM], nSample, k, seed=seed, frame_key=[0])
+    if method[0] == -1:
+        raise RuntimeError(f"hybridSampleAssoc: frame refused: its largest cluster has {int(maxCluster[0])} measurements")
+    if method[0] == -2:
+        raise RuntimeError("hybridSampleAssoc: the frame has no consistent association (some cluster has no feasible assignment)")
     return asg[0]
 
 
