@@ -275,7 +275,14 @@ int kbest_to_probs_f64(kbest_ctx *ctx, double *x, int64_t n);
  * at most ~400 MB: larger batches are not relayed).  A kbest_batch_f64_dev call whose batch was not reserved for fails with
  * KBEST_ERR_NOT_RESERVED; one whose relay images alone are missing (reserved with a smaller B) runs as a plain launch.
  * A graph that captured a relay launch holds the addresses of the relay work space: reserve for the largest batch BEFORE
- * capturing -- a later kbest_reserve that would have to grow that work space returns KBEST_ERR_BAD_ARG.  A piece of a relay
+ * capturing -- a later kbest_reserve that would have to grow that work space returns KBEST_ERR_BAD_ARG.
+ * WORK SPACES UNDER A CAPTURED LAUNCH -- the same rule for every work space of the context and every asynchronous (_dev) entry:
+ * a launch recorded by a stream capture bakes the addresses of the context's work spaces it uses into the graph, so the context
+ * marks each of them as held, until kbest_destroy.  Reserve (kbest_reserve*, with the bounds of the LARGEST call) before capturing.
+ * Afterwards any reservation, and any host-buffer entry (which stages, reserves and runs the _dev entry), of that context that
+ * would have to grow -- that is, free and reallocate -- a held work space returns KBEST_ERR_BAD_ARG and kbest_last_error says
+ * which work space a captured launch holds; nothing is freed, the graph stays valid.  Calls that fit what is reserved, and work
+ * spaces no captured launch has used, are not affected.  Use another context for larger calls.  A piece of a relay
  * waits for its predecessor at most a few seconds (a healthy launch never gets there); a matrix whose hand-over did not come is
  * reported with nf = -3 (KBEST_ERR_INTERNAL from the host entries), and the context re-zeroes its progress words before the
  * next relay launch after any failed entry. */
@@ -283,6 +290,7 @@ int kbest_reserve(kbest_ctx *ctx, int B, int maxRow, int k);
 /* The same for launches that run on the reference-order kernel (KBEST_FLAG_REFERENCE_ORDER, or maxRow > KBEST_MAX_DIM_WIDE): its work
  * space -- per resident problem a padded cost copy (8 maxRow^2 bytes) and a pool of 2 + (k - 1) maxCol hypotheses of 25 maxRow bytes.
  * kbest_batch_f64_dev needs it up front for such launches; the host entries grow it on demand. */
+/* (a work space a captured launch holds does not grow: "WORK SPACES UNDER A CAPTURED LAUNCH" at kbest_reserve) */
 int kbest_reserve_exact(kbest_ctx *ctx, int B, int maxRow, int maxCol, int k);
 
 /* Diagnostic builds only (make -C probabilisticsemslam_amd/csrc PROFILE=1): device buffer of B*16 uint64
@@ -361,6 +369,7 @@ int kbest_assoc_probs_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawRow, int ma
                                     const int32_t *d_nM, const int32_t *d_nRow, const double *d_cost,
                                     const int64_t *d_costOff, int k, int condition, double *d_probs,
                                     const int64_t *d_probOff, int32_t *d_nf, void *stream);
+/* (a work space a captured launch holds does not grow: "WORK SPACES UNDER A CAPTURED LAUNCH" at kbest_reserve) */
 int kbest_reserve_assoc(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, int k);
 
 /*
@@ -391,6 +400,7 @@ int kbest_permanent_probs_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawRow, in
                                         const int32_t *d_nM, const double *d_cost, const int64_t *d_costOff,
                                         int condition, double *d_probs, const int64_t *d_probOff, double *d_perm,
                                         void *stream);
+/* (a work space a captured launch holds does not grow: "WORK SPACES UNDER A CAPTURED LAUNCH" at kbest_reserve) */
 int kbest_reserve_permanent(kbest_ctx *ctx, int B, int maxRawRow, int maxCol);
 /* Diagnostic, for tests: another cap of the permanent work space (bytes; 0: KBEST_PERM_WORK_CAP again).  A lower cap means
  * fewer frames in flight -- smaller chunks -- and the same results bit for bit. */
@@ -437,6 +447,7 @@ int kbest_sample_assoc_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawRow, int m
                                      int nSample, uint64_t seed, uint32_t sampleBase, const uint64_t *d_frameKey,
                                      int32_t *d_assign, const int64_t *d_asgOff, double *d_logProb, const int64_t *d_lpOff,
                                      double *d_perm, void *stream);
+/* (a work space a captured launch holds does not grow: "WORK SPACES UNDER A CAPTURED LAUNCH" at kbest_reserve) */
 int kbest_reserve_sample(kbest_ctx *ctx, int B, int maxRawRow, int maxCol);
 
 /*
@@ -472,6 +483,7 @@ int kbest_belief_probs_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawRow, int m
                                      const int32_t *d_nM, const double *d_cost, const int64_t *d_costOff, int condition,
                                      double tol, int maxIter, double *d_probs, const int64_t *d_probOff, int32_t *d_iters,
                                      double *d_resid, void *stream);
+/* (a work space a captured launch holds does not grow: "WORK SPACES UNDER A CAPTURED LAUNCH" at kbest_reserve) */
 int kbest_reserve_belief(kbest_ctx *ctx, int B, int maxRawRow, int maxCol);
 /* Diagnostic, for tests: the LDS bytes the belief-propagation launches of this context may plan with (0: the device's limit
  * again).  A low value sends small frames through the work space in HBM -- the same results bit for bit. */
@@ -513,6 +525,7 @@ int kbest_clustered_probs_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawRow, in
                                         const int32_t *d_nM, const double *d_cost, const int64_t *d_costOff, int condition,
                                         double *d_probs, const int64_t *d_probOff, double *d_logPerm, int32_t *d_info,
                                         int32_t *d_maxCluster, int32_t *d_label, int labelStride, void *stream);
+/* (a work space a captured launch holds does not grow: "WORK SPACES UNDER A CAPTURED LAUNCH" at kbest_reserve) */
 int kbest_reserve_clustered(kbest_ctx *ctx, int B, int maxRawRow, int maxCol);
 /* For tests: the layers of one cluster / the whole work space at the most (0: the default again).  The results do not depend on
  * either, bit for bit -- except that a lower slot cap refuses (-3) the frames whose clusters need more. */
@@ -572,6 +585,7 @@ int kbest_clustered_sample_assoc_batch_f64_dev(kbest_ctx *ctx, int B, int maxRaw
                                                int nSample, uint64_t seed, uint32_t sampleBase, const uint64_t *d_frameKey,
                                                int32_t *d_assign, const int64_t *d_asgOff, double *d_logProb, const int64_t *d_lpOff,
                                                double *d_logPerm, int32_t *d_info, int32_t *d_maxCluster, void *stream);
+/* (a work space a captured launch holds does not grow: "WORK SPACES UNDER A CAPTURED LAUNCH" at kbest_reserve) */
 int kbest_reserve_clustered_sample(kbest_ctx *ctx, int B, int maxRawRow, int maxCol);
 
 /*
@@ -657,6 +671,7 @@ int kbest_hybrid_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const
  */
 #define KBEST_BIGCLUSTER_MAX_SIZE 20
 #define KBEST_BIGCLUSTER_WORK_CAP ((size_t)1 << 30)  /* the layers of the clusters in flight */
+/* (a work space a captured launch holds does not grow: "WORK SPACES UNDER A CAPTURED LAUNCH" at kbest_reserve) */
 int kbest_reserve_bigcluster(kbest_ctx *ctx, int maxM, int maxRows);
 /* For tests: the layers in flight at the most (0: the default again).  The results do not depend on it, bit for bit -- except that
  * a cluster whose own layers exceed it is not answered (-3). */
@@ -704,6 +719,7 @@ int kbest_hybrid_exact_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL,
 #define KBEST_FRONTIER_MAX_WIDTH 16
 #define KBEST_FRONTIER_SLOT ((size_t)4 << 20)       /* the layers of one cluster */
 #define KBEST_FRONTIER_WORK_CAP ((size_t)1 << 30)   /* the slots of the clusters in flight */
+/* (a work space a captured launch holds does not grow: "WORK SPACES UNDER A CAPTURED LAUNCH" at kbest_reserve) */
 int kbest_reserve_frontier(kbest_ctx *ctx, int n, int maxM, int maxRows);
 /* For tests: the slots in flight at the most / the layers of one cluster at the most (0: the default again).  The results do not
  * depend on the first, bit for bit; a cluster whose layers exceed the second is not answered (-3). */
@@ -768,6 +784,7 @@ int kbest_hybrid_frontier_sample_assoc_batch_f64(kbest_ctx *ctx, int B, const in
                                                  uint64_t seed, uint32_t sampleBase, const uint64_t *frameKey, int32_t *assign,
                                                  const int64_t *asgOff, double *logProb, const int64_t *lpOff, double *logPerm,
                                                  int32_t *method, int32_t *nOpen, int32_t *nFrontier, int32_t *maxCluster);
+/* (a work space a captured launch holds does not grow: "WORK SPACES UNDER A CAPTURED LAUNCH" at kbest_reserve) */
 int kbest_reserve_frontier_sample(kbest_ctx *ctx, int n, int maxM, int maxRows);
 int kbest_frontier_sample_f64_dev(kbest_ctx *ctx, int n, const int32_t *m, const int32_t *nLk, const int64_t *subOff,
                                   const double *d_sub, const int32_t *d_rowKey, const int64_t *rowKeyOff,
@@ -860,6 +877,7 @@ int kbest_hybrid_sample_assoc_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL
  * with a call beyond what was reserved: KBEST_ERR_NOT_RESERVED.  B = 0: KBEST_OK, nothing launched.  Asynchronous on `stream` (NULL:
  * the context's); takes the context's lock like the other _dev entries; two calls on one stream need no synchronise between them.
  */
+/* (a work space a captured launch holds does not grow: "WORK SPACES UNDER A CAPTURED LAUNCH" at kbest_reserve) */
 int kbest_reserve_hybrid_dev(kbest_ctx *ctx, int B, int maxRawRow, int maxCol);
 int kbest_hybrid_frontier_probs_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, const int32_t *d_nL,
                                               const int32_t *d_nM, const double *d_cost, const int64_t *d_costOff, int condition,
@@ -895,6 +913,7 @@ int kbest_hybrid_frontier_probs_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawR
  * with a call beyond it in any of the four numbers: KBEST_ERR_NOT_RESERVED.  B = 0: KBEST_OK, nothing
  * launched.  Asynchronous on `stream` (NULL: the context's); two calls on one stream need no synchronise between them.
  */
+/* (a work space a captured launch holds does not grow: "WORK SPACES UNDER A CAPTURED LAUNCH" at kbest_reserve) */
 int kbest_reserve_hybrid_sample_dev(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, int nSample);
 int kbest_hybrid_frontier_sample_assoc_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawRow, int maxCol, const int32_t *d_nL,
                                                      const int32_t *d_nM, const double *d_cost, const int64_t *d_costOff,

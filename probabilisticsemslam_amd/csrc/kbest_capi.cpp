@@ -26,7 +26,16 @@ namespace kb {
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 }
 
-struct DevBufRaw { void *p = nullptr; size_t bytes = 0; };
+// A work space of the context.  held: a launch that a stream capture recorded was handed this address, so a graph may replay into
+// it for as long as the context lives -- no reservation frees (= grows) it from then on (kbest_c.h, at kbest_reserve).
+struct DevBufRaw {
+    void *p = nullptr;
+    size_t bytes = 0;
+    bool held = false;
+    const char *what = "staging";
+    DevBufRaw() = default;
+    explicit DevBufRaw(const char *w) : what(w) {}
+};
 
 // A few host threads for the host-side half of the host-buffer entry (widening byte tables into the caller's int32 tables while
 // the GPU works on the next piece): ONE pool per process, shared by every context (a pool per context ran a test session with
@@ -112,8 +121,10 @@ struct kbest_ctx {
     int prioMain = 0, prioAux[3] = {0, 0, 0};          // their stream priorities (kbest_create)
     unsigned char *states = nullptr;  // hypothesis-state workspace (+ the slot -> state table behind it)
     size_t statesBytes = 0;
+    bool statesHeld = false;  // a captured launch holds it (DevBufRaw::held)
         unsigned char *wide = nullptr;    // work space of the general-size kernel (kbest_wide.hip)
     size_t wideBytes = 0;
+    bool wideHeld = false;    // a captured launch holds it (DevBufRaw::held)
     unsigned *wideQueue = nullptr;  // the general-size kernel's problem queue (two words, zero between launches)
     bool noWideQueue = false;       // KBEST_NO_WIDE_QUEUE: fixed stride over the batch (A/B)
     int ldsLimit = 65536;
@@ -138,35 +149,34 @@ struct kbest_ctx {
     bool noSplit = false;     // KBEST_NO_SPLIT: never split one matrix over several workgroups (A/B tests)
     bool noTie = false;       // KBEST_NO_TIE: no extra solution / canonical order of exact ties (A/B tests; kbest_ties.h)
     int splitForce = 0;       // KBEST_SPLIT: workgroups per matrix (2 / 4) whenever the split is possible (A/B tests)
-    DevBufRaw splitBuf;       // per-share result tables + shared thresholds of the split
-    DevBufRaw tieBuf;         // [B] fp64: gain of the solution behind the tables (exact ties, kbest_ties.h)
-    DevBufRaw exactBuf;       // work space of the reference-order kernel (kbest_exact.hip)
-    DevBufRaw permBuf;        // work space of the permanent kernel (kbest_perm.hip): the subset layers that do not fit LDS
+    DevBufRaw splitBuf{"split"};  // per-share result tables + shared thresholds of the split
+    DevBufRaw tieBuf{"tie"};  // [B] fp64: gain of the solution behind the tables (exact ties, kbest_ties.h)
+    DevBufRaw exactBuf{"reference-order"};  // work space of the reference-order kernel (kbest_exact.hip)
+    DevBufRaw permBuf{"permanent"};  // work space of the permanent kernel (kbest_perm.hip): the subset layers that do not fit LDS
     size_t permCap = KBEST_PERM_WORK_CAP;  // ... and its cap (kbest_set_permanent_work_cap)
     int permLastGrid = 0;     // workgroups (frames in flight) of the last permanent launch (kbest_last_permanent_grid)
-    DevBufRaw lbpBuf;         // work space of the belief-propagation kernel (kbest_lbp.hip): frames whose a and nu do not fit LDS
+    DevBufRaw lbpBuf{"belief-propagation"};  // work space of the belief-propagation kernel (kbest_lbp.hip): frames whose a and nu do not fit LDS
     int lbpLdsLimit = 0;      // kbest_set_belief_lds_limit: LDS bytes that kernel may plan with (0: ldsLimit)
-    DevBufRaw clusBuf;        // work space of the clustered exact kernel (kbest_cluster.hip): a cluster's layers that do not fit LDS
+    DevBufRaw clusBuf{"clustered"};  // work space of the clustered exact kernel (kbest_cluster.hip): a cluster's layers that do not fit LDS
     size_t clusSlotCap = KBEST_CLUSTER_SLOT_CAP;  // ... the layers of one cluster at the most (kbest_set_clustered_slot_cap)
     size_t clusWorkCap = KBEST_CLUSTER_WORK_CAP;  // ... the whole work space at the most (kbest_set_clustered_work_cap)
     int clusLastGrid = 0;     // workgroups (frames in flight) of the last clustered launch (kbest_last_clustered_grid)
-    DevBufRaw bigLayers;      // the big-cluster tier (kbest_bigcluster.hip): the layers of the clusters in flight
-    DevBufRaw bigSmall;       // ... and their small arrays: a', row lists, per-workgroup partial sums
+    DevBufRaw bigLayers{"big-cluster layer"};  // the big-cluster tier (kbest_bigcluster.hip): the layers of the clusters in flight
+    DevBufRaw bigSmall{"big-cluster"};  // ... and their small arrays: a', row lists, per-workgroup partial sums
     size_t bigWorkCap = KBEST_BIGCLUSTER_WORK_CAP;  // ... the layers in flight at the most (kbest_set_bigcluster_work_cap)
-    DevBufRaw frLayers;       // the frontier tier (kbest_frontier.hip): one slot of layers per workgroup of a launch
-    DevBufRaw frPlan;         // ... and one plan (KB_FRONTIER_STEP_DOUBLES per row) per workgroup
+    DevBufRaw frLayers{"frontier layer"};  // the frontier tier (kbest_frontier.hip): one slot of layers per workgroup of a launch
+    DevBufRaw frPlan{"frontier plan"};  // ... and one plan (KB_FRONTIER_STEP_DOUBLES per row) per workgroup
     size_t frSlot = KBEST_FRONTIER_SLOT;          // ... the layers of one cluster at the most (kbest_set_frontier_slot)
     size_t frWorkCap = KBEST_FRONTIER_WORK_CAP;   // ... the slots in flight at the most (kbest_set_frontier_work_cap)
-    DevBufRaw hybBuf;         // kbest_hybrid_frontier_probs_batch_f64_dev: labels, descriptors, row lists, the cluster list, the
+    DevBufRaw hybBuf{"hybrid"};  // kbest_hybrid_frontier_probs_batch_f64_dev: labels, descriptors, row lists, the cluster list, the
                               // per-cluster outputs and the packed probabilities (kbest_reserve_hybrid_dev; HybridLayout)
-    DevBufRaw hybSampBuf;     // kbest_hybrid_frontier_sample_assoc_batch_f64_dev: offsets, sums, the clusters' keys, local draws and
+    DevBufRaw hybSampBuf{"hybrid sampling"};  // kbest_hybrid_frontier_sample_assoc_batch_f64_dev: offsets, sums, the clusters' keys, local draws and
                               // terms (kbest_reserve_hybrid_sample_dev; HybridSampleLayout)
     int hybSampB = 0, hybSampRow = 0, hybSampCol = 0, hybSampN = 0;  // ... the largest of each number reserved so far: what it is sized for
-    DevBufRaw relayBuf;       // relay launches of the 64-row kernel: [B] LDS images (kbest_engine.hip)
-    DevBufRaw relayFlags;     // ... and three words per matrix: claimed / done / gone (zeroed when the buffer is made, put back to zero by every launch)
+    DevBufRaw relayBuf{"relay"};  // relay launches of the 64-row kernel: [B] LDS images (kbest_engine.hip)
+    DevBufRaw relayFlags{"relay"};  // ... and three words per matrix: claimed / done / gone (zeroed when the buffer is made, put back to zero by every launch)
     long long relayLaunches = 0;  // relay launches made (kbest_relay_launches)
     std::atomic<bool> relayDirty{false};  // an entry of this context failed (HIP error, nf < 0): the relay's words are zeroed before the next relay launch
-    bool relayCaptured = false;   // a relay launch was captured into a graph: the graph holds the relay work space's addresses
     int lastRoute = 0;            // which kernel(s) the last k-best launch went to (kbest_last_route)
     int refOrder = 0;             // kbest_set_reference_order: 1 = the association entries enumerate in the reference's own order (kbest_exact.hip);
                                   // 2 = only the frames whose k-th and (k+1)-th gains are equal do (their weights are then the reference's)
@@ -235,6 +245,17 @@ int fail(kbest_ctx *ctx, int code, const char *what, hipError_t e = hipSuccess)
         if (e != hipSuccess) { ctx->err += ": "; ctx->err += hipGetErrorString(e); }
     }
     return code;
+}
+
+// A growth path met a work space that a captured launch holds (DevBufRaw::held): growing would free what a graph still writes to.
+int refuse_held(kbest_ctx *ctx, const char *what, const char *largest = "call")
+{
+    std::string msg = "the ";
+    msg += what;
+    msg += " work space cannot grow while a captured launch of this context holds it: reserve for the largest ";
+    msg += largest;
+    msg += " before capturing";
+    return fail(ctx, KBEST_ERR_BAD_ARG, msg.c_str());
 }
 
 #define HIP_TRY(ctx, call)                                                   \
@@ -684,6 +705,7 @@ static int reserve_wide(kbest_ctx *ctx, const WidePlan &w, bool grow)
     const size_t need = w.perSlot * (size_t)w.grid + 256;
     if (need <= ctx->wideBytes) return KBEST_OK;
     if (!grow) return fail(ctx, KBEST_ERR_NOT_RESERVED, "general-size work space too small: call kbest_reserve first");
+    if (ctx->wideHeld && ctx->wide) return refuse_held(ctx, "general-size");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (ctx->wide) { HIP_TRY(ctx, hipDeviceSynchronize()); (void)hipFree(ctx->wide); ctx->wide = nullptr; ctx->wideBytes = 0; }
     hipError_t e = hipMalloc(reinterpret_cast<void **>(&ctx->wide), need);
@@ -829,6 +851,7 @@ static int ensure_states(kbest_ctx *ctx, size_t need, bool grow)
 {
     if (need <= ctx->statesBytes) return KBEST_OK;
     if (!grow) return fail(ctx, KBEST_ERR_NOT_RESERVED, "hypothesis workspace too small: call kbest_reserve first");
+    if (ctx->statesHeld && ctx->states) return refuse_held(ctx, "hypothesis");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (ctx->states) { HIP_TRY(ctx, hipDeviceSynchronize()); (void)hipFree(ctx->states); ctx->states = nullptr; ctx->statesBytes = 0; }
     hipError_t e = hipMalloc(reinterpret_cast<void **>(&ctx->states), need);
@@ -852,6 +875,7 @@ static int exact_reserve(kbest_ctx *ctx, size_t need)
     DevBufRaw &d = ctx->exactBuf;
     if (need <= d.bytes) return KBEST_OK;
     const size_t cap = (need + ((size_t)2 << 20) - 1) & ~(((size_t)2 << 20) - 1);
+    if (d.held && d.p) return refuse_held(ctx, d.what);
     if (d.p) { HIP_TRY(ctx, hipDeviceSynchronize()); (void)hipFree(d.p); d.p = nullptr; d.bytes = 0; }
     hipError_t e = hipMalloc(&d.p, cap);
     if (e != hipSuccess) { d.p = nullptr; return fail(ctx, KBEST_ERR_NOMEM, "hipMalloc(reference-order work space)", e); }
@@ -975,6 +999,15 @@ static bool capturing(hipStream_t s)
     return s && hipStreamIsCapturing(s, &st) == hipSuccess && st != hipStreamCaptureStatusNone;
 }
 
+// Called by every asynchronous entry with the context-owned work spaces whose addresses it hands to a launch on stream s (and the
+// mark of the hypothesis or general-size work space where it hands that one on): a graph that captured the launch keeps them.
+static void hold_if_capturing(hipStream_t s, std::initializer_list<DevBufRaw *> bufs, bool *flag = nullptr)
+{
+    if (!capturing(s)) return;
+    for (DevBufRaw *d : bufs) d->held = true;
+    if (flag) *flag = true;
+}
+
 static int order_behind_last(kbest_ctx *ctx, hipStream_t s)
 {
     // Under stream capture (kbest_c.h allows the asynchronous entries inside a graph capture) nothing of the cross-stream
@@ -1059,8 +1092,8 @@ static int relay_reserve(kbest_ctx *ctx, int B, size_t img, bool grow)
     if (need <= ctx->relayBuf.bytes && needF <= ctx->relayFlags.bytes) return KBEST_OK;
     if (!grow) return KBEST_ERR_NOT_RESERVED;
     // a captured relay launch holds the addresses of these buffers: growing (= freeing) them under it is refused
-    if (ctx->relayCaptured && ctx->relayBuf.p)
-        return fail(ctx, KBEST_ERR_BAD_ARG, "the relay work space cannot grow while a captured launch of this context holds it: reserve for the largest batch before capturing");
+    // (both or neither: the launch is handed the two together)
+    if (ctx->relayBuf.held && ctx->relayBuf.p) return refuse_held(ctx, ctx->relayBuf.what, "batch");
     int rc = raw_reserve(ctx, ctx->relayBuf, need);
     if (rc != KBEST_OK) return rc;
     if (needF > ctx->relayFlags.bytes) {
@@ -1136,6 +1169,7 @@ static int batch_dev_impl(kbest_ctx *ctx, const kbest_opts *opts, int B, int max
         ep.nf = d_nf;
         ep.pushed = (opts->flags & KBEST_FLAG_COUNT_PUSHED) ? reinterpret_cast<long long *>(d_pushed) : nullptr;
         ep.work = static_cast<unsigned char *>(ctx->exactBuf.p);
+        hold_if_capturing(s, {&ctx->exactBuf});
         ep.hypPerSlot = pl.hypPerSlot;
         const hipError_t e = kb::launch_kbest_exact(ep, pl.grid, s);
         if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "reference-order kbest kernel launch", e);
@@ -1192,6 +1226,7 @@ static int batch_dev_impl(kbest_ctx *ctx, const kbest_opts *opts, int B, int max
             if (rc != KBEST_OK) return rc;
         }
         d_tieGain = static_cast<double *>(ctx->tieBuf.p) + base;
+        hold_if_capturing(s, {&ctx->tieBuf});
     }
     // the launch behind the enumeration: runs of equal gains into the canonical order, the tie flags (kbest_ties.h)
     auto finish = [&]() -> int {
@@ -1259,6 +1294,7 @@ static int batch_dev_impl(kbest_ctx *ctx, const kbest_opts *opts, int B, int max
         p.slotSid = reinterpret_cast<unsigned short *>(ctx->states + slotOff) + base * (size_t)kb::slot_table_stride(k);
         p.kTab = kT;
         p.tieGain = d_tieGain;
+        hold_if_capturing(s, {}, &ctx->statesHeld);
         hipError_t e = kb::launch_kbest_lane(p, B, lsh.nWaves, lsh.lanes, s);
         if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "lane-per-child kbest kernel launch", e);
         ctx->lastRoute = KBEST_ROUTE_LANE | (extraSol ? KBEST_ROUTE_EXTRA : 0);
@@ -1295,6 +1331,7 @@ static int batch_dev_impl(kbest_ctx *ctx, const kbest_opts *opts, int B, int max
         sp.prof = ctx->prof;
         sp.kTab = kT;
         sp.tieGain = d_tieGain;
+        hold_if_capturing(s, {}, &ctx->statesHeld);
         hipError_t e = kb::launch_kbest_small(sp, B, snw, s);
         if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "small-problem kbest kernel launch", e);
         ctx->lastRoute = KBEST_ROUTE_SMALL | (extraSol ? KBEST_ROUTE_EXTRA : 0);
@@ -1410,7 +1447,7 @@ static int batch_dev_impl(kbest_ctx *ctx, const kbest_opts *opts, int B, int max
                     const hipError_t ez = kb::launch_zero_words(static_cast<unsigned *>(ctx->relayFlags.p), (long long)(ctx->relayFlags.bytes / 4), s);
                     if (ez != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "relay words: zeroing kernel launch", ez);
                 }
-                if (capturing(s)) ctx->relayCaptured = true;
+                hold_if_capturing(s, {&ctx->relayBuf, &ctx->relayFlags});
                 ctx->relayLaunches++;
                 ctx->lastRoute |= KBEST_ROUTE_RELAY;
                 p.relayBuf = static_cast<unsigned char *>(ctx->relayBuf.p);
@@ -1422,6 +1459,8 @@ static int batch_dev_impl(kbest_ctx *ctx, const kbest_opts *opts, int B, int max
                 return rc;
             }  // (not reserved: an asynchronous entry never allocates -- the launch runs without the relay)
         }
+        if (S > 1) hold_if_capturing(s, {&ctx->splitBuf}, &ctx->statesHeld);
+        else hold_if_capturing(s, {}, &ctx->statesHeld);
         hipError_t e = kb::launch_kbest(p, B * S, shp.nWaves, s);
         if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "kbest kernel launch", e);
         if (S > 1) {  // the global k best of every matrix from its shares' lists
@@ -1513,7 +1552,9 @@ static int batch_dev_impl(kbest_ctx *ctx, const kbest_opts *opts, int B, int max
         p.prof = ctx->prof;
         p.kTab = kT;
         p.tieGain = d_tieGain;
-        p.queue = (ctx->noWideQueue || capturing(s)) ? nullptr : ctx->wideQueue;  // (a captured launch: fixed stride -- nothing to go wrong on a replay)
+        const bool cap = capturing(s);
+        if (cap) ctx->wideHeld = true;
+        p.queue = (ctx->noWideQueue || cap) ? nullptr : ctx->wideQueue;  // (a captured launch: fixed stride -- nothing to go wrong on a replay)
         hipError_t e = kb::launch_kbest_wide(p, w.grid, s);
         if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "general-size kbest kernel launch", e);
     }
@@ -2421,6 +2462,7 @@ static int raw_reserve(kbest_ctx *ctx, DevBufRaw &d, size_t need)
     if (need <= d.bytes) return KBEST_OK;
     size_t cap = 1 << 16;
     while (cap < need) cap <<= 1;
+    if (d.held && d.p) return refuse_held(ctx, d.what);
     if (d.p) { HIP_TRY(ctx, hipDeviceSynchronize()); (void)hipFree(d.p); d.p = nullptr; d.bytes = 0; }  // (rare: only when it grows)
     hipError_t e = hipMalloc(&d.p, cap);
     if (e != hipSuccess) return fail(ctx, KBEST_ERR_NOMEM, "hipMalloc(staging)", e);
@@ -2722,6 +2764,7 @@ extern "C" int kbest_assoc_probs_batch_f64_dev(kbest_ctx *ctx, int B, int maxRaw
     sp.prof = ctx->prof;
     // frame-sized blocks of up to 16 measurements and 64 rows: the bounded walk (kbest_bnb.hip; a frame it hands back has
     // d_nf = -2 like one beyond the fused enumeration kernel: the host-pointer entry re-runs such frames by itself)
+    hold_if_capturing(s, {}, &ctx->statesHeld);
     const int bnbThreads = bnb_many(ctx, B) ? 256 : 1024;
     const bool useBnb = !ctx->noBnb && maxRawRow <= kb::BNB_MAX_ROW && maxCol <= kb::BNB_MAX_COL && kT <= kb::bnb_max_k(bnbThreads) &&
                         kb::bnb_lds_bytes(kT, bnbThreads) <= ctx->ldsLimit;
@@ -2815,6 +2858,7 @@ extern "C" int kbest_permanent_probs_batch_f64_dev(kbest_ctx *ctx, int B, int ma
     pp.probs = d_probs;
     pp.perm = d_perm;
     pp.work = static_cast<double *>(ctx->permBuf.p);
+    hold_if_capturing(s, {&ctx->permBuf});
     pp.slotStride = pl.slotDoubles;
     pp.B = B;
     pp.maxRawRow = maxRawRow;
@@ -2908,6 +2952,7 @@ extern "C" int kbest_sample_assoc_batch_f64_dev(kbest_ctx *ctx, int B, int maxRa
     sp.lpOff = reinterpret_cast<const long long *>(d_lpOff);
     sp.perm = d_perm;
     sp.work = static_cast<double *>(ctx->permBuf.p);
+    hold_if_capturing(s, {&ctx->permBuf});
     sp.slotStride = pl.slotDoubles;
     sp.seed = seed;
     sp.sampleBase = sampleBase;
@@ -3036,6 +3081,7 @@ extern "C" int kbest_belief_probs_batch_f64_dev(kbest_ctx *ctx, int B, int maxRa
     lp.iters = d_iters;
     lp.resid = d_resid;
     lp.work = static_cast<double *>(ctx->lbpBuf.p);
+    hold_if_capturing(s, {&ctx->lbpBuf});
     lp.slotStride = pl.slotDoubles;
     lp.tol = tol;
     lp.maxIter = maxIter;
@@ -3180,6 +3226,7 @@ static int cluster_launch_dev(kbest_ctx *ctx, const char *who, const ClusterPart
     cp.maxCluster = d_maxCluster;
     cp.label = d_label;
     cp.work = static_cast<double *>(ctx->clusBuf.p);
+    hold_if_capturing(s, {&ctx->clusBuf});
     cp.slotStride = pl.slotDoubles;
     cp.slotBytes = pl.slotBytes;
     cp.labelStride = d_label ? labelStride : 0;
@@ -3318,6 +3365,7 @@ static int cluster_sample_dev(kbest_ctx *ctx, int partialMaxExact, int B, int ma
     sp.info = d_info;
     sp.maxCluster = d_maxCluster;
     sp.work = static_cast<double *>(ctx->clusBuf.p);
+    hold_if_capturing(s, {&ctx->clusBuf});
     sp.slotStride = pl.slotDoubles;
     sp.slotBytes = pl.slotBytes;
     sp.seed = seed;
@@ -3824,6 +3872,7 @@ int kbest_bigcluster_probs_f64_dev(kbest_ctx *ctx, int n, const int32_t *m, cons
     int rc = order_behind_last(ctx, s);  // (one work space per context)
     if (rc != KBEST_OK) return rc;
     const Launched mark{ctx, s};
+    hold_if_capturing(s, {&ctx->bigLayers, &ctx->bigSmall});
     kb::BigClusterPack pk;
     pk.n = 0;
     size_t layAt = 0, smAt = 0;  // doubles
@@ -3934,6 +3983,7 @@ int kbest_frontier_probs_f64_dev(kbest_ctx *ctx, int n, const int32_t *m, const 
     int rc = order_behind_last(ctx, s);  // (one work space per context)
     if (rc != KBEST_OK) return rc;
     const Launched mark{ctx, s};
+    hold_if_capturing(s, {&ctx->frLayers, &ctx->frPlan});
     kb::FrontierPack pk;
     for (int at = 0; at < n; at += kb::KB_FRONTIER_PACK) {  // (launches of one stream: the next pack takes the slots over)
         pk.n = n - at < kb::KB_FRONTIER_PACK ? n - at : kb::KB_FRONTIER_PACK;
@@ -3992,6 +4042,7 @@ int kbest_frontier_sample_f64_dev(kbest_ctx *ctx, int n, const int32_t *m, const
     int rc = order_behind_last(ctx, s);  // (one work space per context)
     if (rc != KBEST_OK) return rc;
     const Launched mark{ctx, s};
+    hold_if_capturing(s, {&ctx->frLayers, &ctx->frPlan});
     kb::FrontierSamplePack pk;
     for (int at = 0; at < n; at += kb::KB_FRONTIER_SAMPLE_PACK) {  // (launches of one stream: the next pack takes the slots over)
         pk.n = n - at < kb::KB_FRONTIER_SAMPLE_PACK ? n - at : kb::KB_FRONTIER_SAMPLE_PACK;
@@ -4150,6 +4201,7 @@ int kbest_hybrid_frontier_probs_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawR
                                                i32(L.desc), maxCol, i32(L.rows), maxRawRow, d_sub, stream);
     if (rc != KBEST_OK) return rc;
     const Launched mark{ctx, s};
+    hold_if_capturing(s, {&ctx->hybBuf, &ctx->frLayers, &ctx->frPlan});  // (the clustered work space: by the partial kernel's entry)
     kb::HybridParams hp;
     hp.nL = d_nL;
     hp.nM = d_nM;
@@ -5011,6 +5063,8 @@ int kbest_hybrid_frontier_sample_assoc_batch_f64_dev(kbest_ctx *ctx, int B, int 
     rc = order_behind_last(ctx, s);  // (one work space per context)
     if (rc != KBEST_OK) return rc;
     const Launched mark{ctx, s};
+    // (the clustered work space: by the partial kernel's and the clustered sampler's entries)
+    hold_if_capturing(s, {&ctx->hybBuf, &ctx->hybSampBuf, &ctx->frLayers, &ctx->frPlan});
     kb::HybridSampleParams sp;
     sp.nL = d_nL;
     sp.nM = d_nM;
