@@ -437,6 +437,11 @@ __global__ void __launch_bounds__(NW * 64, min_waves_per_simd(NW)) kbest_kernel(
     int tid = threadIdx.x;   // (not const: see the top of the round loop)
     int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+#ifdef KB_PREFIX_NOPS
+    // (A/B builds only, make VARIANT=.. EXTRA=-DKB_PREFIX_NOPS=n: n s_nop in the prefix move everything behind them by 4 n bytes --
+    //  to compare two builds with the hand-written step loop at the same offset inside its 64-byte fetch window, NOTES section 8)
+    asm volatile(".rept %0\n\ts_nop 0\n\t.endr" ::"n"(KB_PREFIX_NOPS));
+#endif
     // split > 1: ONE matrix is enumerated by `split` workgroups, each taking the root's children on columns c % split == share
     // (Murty's partition of the root is disjoint, cpp:455-532) into its own tables [share][matrix]; a k-way merge follows
     // (kbest_merge.hip).  They share an upper bound of the k-th best gain through sharedT (see the top of the round loop).
@@ -583,20 +588,65 @@ __global__ void __launch_bounds__(NW * 64, min_waves_per_simd(NW)) kbest_kernel(
         const uint4 *src = reinterpret_cast<const uint4 *>(p.relayBuf + (long long)blk * p.relayStride);
         uint4 *dst = reinterpret_cast<uint4 *>(smem);
         __syncthreads();
-        for (int i = tid; i < L.total / 16; i += NT) dst[i] = src[i];
+        // (the loads of a chunk -- at most 8 x 16 bytes per thread -- are all issued before the first LDS write: one memory round
+        //  trip per chunk instead of one per 16 bytes.  Past the end of a short chunk a thread copies the FIRST 16 bytes of its
+        //  chunk again -- its own, the same value to the same place -- so that loads and writes stand in straight-line code:
+        //  behind a condition the compiler moves each load down to its write, and they wait for each other again.)
+        constexpr int IMG_CHUNK = 8;
+        const int n16 = L.total / 16;
+        for (int i0 = tid; i0 < n16; i0 += IMG_CHUNK * NT) {
+            uint4 im[IMG_CHUNK];
+#pragma unroll
+            for (int j = 0; j < IMG_CHUNK; j++) {
+                const int i = i0 + j * NT;
+                im[j] = src[i < n16 ? i : i0];
+            }
+#pragma unroll
+            for (int j = 0; j < IMG_CHUNK; j++) {
+                const int i = i0 + j * NT;
+                dst[i < n16 ? i : i0] = im[j];
+            }
+        }
 #ifdef KB_PROFILE
         if (p.prof && threadIdx.x == 0) p.prof[(long long)gridDim.x * gridDim.y * 16 + ((long long)piece * gridDim.x + blockIdx.x) * 5 + 3] = wall_clock64();  // the image is in
 #endif
     }
     if (fresh) {
         if (tid < 64) { colOf[tid] = (unsigned char)tid; posOf[tid] = (unsigned char)tid; }
+        // Phase 0 reads the cost block ONCE where a wave has at most SETUP_CHUNK columns (8, 12, 16 waves; 4 waves up to 32 columns): a
+        // wave issues the loads of all its columns before it waits for the first (one memory round trip instead of one per
+        // column), takes the minimum from the registers in the order of the columns, and behind the barrier writes the tile
+        // from the same registers.  Columns beyond the first chunk are read once for the minimum and once for the tile, a
+        // chunk in flight each time.  A column beyond M, and a lane beyond N, load an entry that exists (the clamped index)
+        // and do not use it: the loads stand in straight-line code.
+        constexpr int SETUP_CHUNK = 8;
+        const int rN = lane < N ? lane : N - 1;
+        const bool rowOn = lane < N;
+        double x0[SETUP_CHUNK];
+#pragma unroll
+        for (int j = 0; j < SETUP_CHUNK; j++) {
+            const int c = wave + j * NW;
+            x0[j] = Cg[rN + (long long)(c < M ? c : M - 1) * N];
+        }
         double mn = INF;  // min of C, or min of -C when maximising (max C = -min(-C), exact)
-        for (int c = wave; c < M; c += NW)
-            for (int r = lane; r < N; r += 64) {
-                double x = Cg[r + (long long)c * N];
-                x = maximize ? -x : x;
-                mn = min_keep(mn, x);
+#pragma unroll
+        for (int j = 0; j < SETUP_CHUNK; j++) {
+            const double x = maximize ? -x0[j] : x0[j];
+            if (rowOn && wave + j * NW < M) mn = min_keep(mn, x);
+        }
+        for (int c0 = wave + SETUP_CHUNK * NW; c0 < M; c0 += SETUP_CHUNK * NW) {
+            double x1[SETUP_CHUNK];
+#pragma unroll
+            for (int j = 0; j < SETUP_CHUNK; j++) {
+                const int c = c0 + j * NW;
+                x1[j] = Cg[rN + (long long)(c < M ? c : M - 1) * N];
             }
+#pragma unroll
+            for (int j = 0; j < SETUP_CHUNK; j++) {
+                const double x = maximize ? -x1[j] : x1[j];
+                if (rowOn && c0 + j * NW < M) mn = min_keep(mn, x);
+            }
+        }
         mn = wave_min_f64(mn);
         if (lane == 0) red[wave] = mn;
         __syncthreads();
@@ -606,20 +656,37 @@ __global__ void __launch_bounds__(NW * 64, min_waves_per_simd(NW)) kbest_kernel(
         cdelTile = cdel;
         __syncthreads();
         double cm = 0.0;
-        for (int c = wave; c < D; c += NW)
-            for (int r = lane; r < N; r += 64) {
-                double val = 0.0;
-                if (c < M) {
-                    const double x = Cg[r + (long long)c * N];
-                    val = noShift ? x : (maximize ? (-x + cdel) : (x - cdel));  // cpp:558 / cpp:564
-                    // inf - inf (e.g. an all-inf matrix) gives NaN; every comparison the reference makes with
-                    // a NaN reduced cost is false (cpp:185, 314), i.e. the arc behaves exactly like +inf.  The
-                    // integer-key compare of the Dijkstra step needs that made explicit.
-                    if (val != val) val = INF;
-                    if (val < INF && val > cm) cm = val;
-                }
-                Cs[r + c * LDC] = val;
+        // one column of the tile from the entry x of the cost block (zero for a padded column)
+        auto tile_put = [&](int c, double x) {
+            double val = 0.0;
+            if (c < M) {
+                val = noShift ? x : (maximize ? (-x + cdel) : (x - cdel));  // cpp:558 / cpp:564
+                // inf - inf (e.g. an all-inf matrix) gives NaN; every comparison the reference makes with
+                // a NaN reduced cost is false (cpp:185, 314), i.e. the arc behaves exactly like +inf.  The
+                // integer-key compare of the Dijkstra step needs that made explicit.
+                if (val != val) val = INF;
+                if (val < INF && val > cm) cm = val;
             }
+            Cs[lane + c * LDC] = val;
+        };
+#pragma unroll
+        for (int j = 0; j < SETUP_CHUNK; j++) {
+            const int c = wave + j * NW;
+            if (rowOn && c < D) tile_put(c, x0[j]);
+        }
+        for (int c0 = wave + SETUP_CHUNK * NW; c0 < D; c0 += SETUP_CHUNK * NW) {
+            double x1[SETUP_CHUNK];
+#pragma unroll
+            for (int j = 0; j < SETUP_CHUNK; j++) {
+                const int c = c0 + j * NW;
+                x1[j] = Cg[rN + (long long)(c < M ? c : M - 1) * N];
+            }
+#pragma unroll
+            for (int j = 0; j < SETUP_CHUNK; j++) {
+                const int c = c0 + j * NW;
+                if (rowOn && c < D) tile_put(c, x1[j]);
+            }
+        }
         cm = -wave_min_f64(-cm);
         if (lane == 0) red[wave] = cm;
         __syncthreads();

@@ -330,17 +330,26 @@ __device__ __forceinline__ void column_keys_closure(float *dm, double *key, cons
             fw_block(rowBlk ? o : c * 16, rowBlk ? c * 16 : o, o);
         }
         __syncthreads();
-        const int cnt = (nbk - 1) * (nbk - 1) * 256;
+        // (four entries (i, j .. j + 3) per thread, as fw_block holds them: one read of A and one 16-byte read of B per kk where
+        //  four entries of their own took eight reads; every entry takes the same terms in the same kk order)
+        const int cnt = (nbk - 1) * (nbk - 1) * 64;
         for (int e = tid; e < cnt; e += NT) {
-            const int blk = e >> 8;
+            const int blk = e >> 6;
             int ba = blk / (nbk - 1), bb = blk - ba * (nbk - 1);
             ba += (ba >= r) ? 1 : 0;
             bb += (bb >= r) ? 1 : 0;
-            const int i = ba * 16 + ((e >> 4) & 15), j = bb * 16 + (e & 15);
-            float acc = dm[i * Dp + j];
-#pragma unroll 4
-            for (int kk = 0; kk < 16; kk++) acc = fminf(acc, dm[i * Dp + o + kk] + dm[(o + kk) * Dp + j]);
-            dm[i * Dp + j] = acc;
+            const int i = ba * 16 + ((e >> 2) & 15), j = bb * 16 + (e & 3) * 4;
+            float4 acc = *reinterpret_cast<const float4 *>(dm + i * Dp + j);
+#pragma unroll
+            for (int kk = 0; kk < 16; kk++) {
+                const float av = dm[i * Dp + o + kk];
+                const float4 b4 = *reinterpret_cast<const float4 *>(dm + (o + kk) * Dp + j);
+                acc.x = fminf(acc.x, av + b4.x);
+                acc.y = fminf(acc.y, av + b4.y);
+                acc.z = fminf(acc.z, av + b4.z);
+                acc.w = fminf(acc.w, av + b4.w);
+            }
+            *reinterpret_cast<float4 *>(dm + i * Dp + j) = acc;
         }
         __syncthreads();
     }
