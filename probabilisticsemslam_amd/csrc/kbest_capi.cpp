@@ -264,6 +264,13 @@ int refuse_held(kbest_ctx *ctx, const char *what, const char *largest = "call")
         if (e_ != hipSuccess) return fail(ctx, KBEST_ERR_HIP, #call, e_);    \
     } while (0)
 
+// (the same for a step that returns a KBEST_* code of its own and has said why)
+#define KB_TRY(call)                                                         \
+    do {                                                                     \
+        const int rc_ = (call);                                              \
+        if (rc_ != KBEST_OK) return rc_;                                     \
+    } while (0)
+
 // Launch shape, tuned on MI355X (DESIGN.md sections 3, 8).  The 32 KiB cost tile of a 64-row problem limits a CU to three
 // resident matrices and 80 VGPRs limit it to 24 waves: {8 waves, 6 candidates, 3 matrices/CU} is the throughput shape,
 // {12 waves, 12 candidates, 2/CU} and {16 waves, 16 candidates, 1/CU} trade throughput for latency when the batch is small.
@@ -362,9 +369,11 @@ struct Sub {  // a slice of a DevBuf
     template <class T> T *as() { return static_cast<T *>(p); }
 };
 
-// What the host-pointer probability entries (permanent, belief, clustered, hybrid) share: the scan over the caller's frames, the
-// cost blocks, the meta block and the zeroed probabilities on the device, and the way back into the caller's buffer.  The only
-// place that knows the layout of meta.  An entry's own outputs, checks, reserve call and launch stay with the entry.
+// What the host-pointer entries over frames share -- the probability entries (permanent, belief, clustered, the three hybrid ones)
+// and the draw entries (sample, clustered sample, the two hybrid samplers: probOff = nullptr, or a packed scratch): the scan over
+// the caller's frames, the cost blocks, the meta block and the zeroed probabilities on the device, and the way back into the
+// caller's buffer.  The only place that knows the layout of meta.  An entry's own outputs, checks, reserve call and launch stay
+// with the entry; the draw entries' buffers are DrawBatch's, the partial kernel of the hybrid bodies is PartialRun's.
 struct FrameBatch {
     struct Also { DevBuf *buf; size_t bytes; };  // a buffer of the entry's own, drawn in the same go (0 bytes: not drawn)
     int B = 0, maxRawRow = 1, maxCol = 1;
@@ -397,7 +406,7 @@ struct FrameBatch {
 
     // meta: costOff[B] | probOff[B] (int64) | nL[B] | nM[B] (int32).  The probabilities are zeroed with hipMemsetAsync on the
     // context's stream (the note above DevBuf says why not hipMemset): the kernels write what is not zero.
-    int upload(kbest_ctx *ctx, const char *who, const double *cost, std::initializer_list<Also> also = {})
+    int upload(kbest_ctx *ctx, const char *who, const double *cost, const std::vector<Also> &also = {})
     {
         std::vector<unsigned char> meta((size_t)B * 24);
         memcpy(meta.data(), costOff, (size_t)B * 8);
@@ -439,6 +448,200 @@ struct FrameBatch {
         dMeta.release();
         dCost.release();
     }
+    // The frame's block minimum (0 after conditionCosts): a cluster's log Z_k is in the units a = exp(-x), and m_k times this
+    // brings it to the frame's a = exp(min - x).
+    double block_min(const double *cost, int b, int condition) const
+    {
+        if (condition) return 0.0;
+        const double *x = cost + costOff[b];
+        const size_t cnt = ((size_t)nL[b] + nM[b]) * (size_t)nM[b];
+        double mn = x[0];
+        for (size_t i = 1; i < cnt; i++) mn = x[i] < mn ? x[i] : mn;
+        return mn;
+    }
+};
+
+// What the host-pointer draw entries share beside FrameBatch: the caller's draw buffers -- frame b's assign [nSample][nM] at
+// asgOff[b], its logProb [nSample] at lpOff[b] -- their offsets and the frames' keys on the device, and the way back.  The only
+// place that knows the layout of dOff.  asg(), lp() and off() go into FrameBatch::upload, at the entry's own place for them.
+struct DrawBatch {
+    int B = 0, nSample = 0;
+    size_t asgN = 0, lpN = 0;  // int32s / doubles up to the end of the last frame's draws
+    const int32_t *nM = nullptr;
+    const int64_t *asgOff = nullptr, *lpOff = nullptr;
+    bool keyed = false;
+    DevBuf dAsg, dLp, dOff;  // off: asgOff[B] | lpOff[B] | frameKey[B] (8 bytes each)
+    std::vector<int32_t> hAsg;
+    std::vector<double> hLp;
+
+    int scan(kbest_ctx *ctx, const char *who, int B_, const int32_t *nM_, int nSample_, const int64_t *asgOff_, const int64_t *lpOff_)
+    {
+        B = B_;
+        nM = nM_;
+        nSample = nSample_;
+        asgOff = asgOff_;
+        lpOff = lpOff_;
+        for (int b = 0; b < B; b++) {
+            if (asgOff[b] < 0 || lpOff[b] < 0) return fail(ctx, KBEST_ERR_BAD_ARG, (std::string(who) + ": a negative offset").c_str());
+            asgN = std::max(asgN, (size_t)asgOff[b] + draws(b));
+            lpN = std::max(lpN, (size_t)lpOff[b] + (size_t)nSample);
+        }
+        return KBEST_OK;
+    }
+    size_t draws(int b) const { return (size_t)nSample * (size_t)nM[b]; }  // int32s of frame b's [nSample][nM] rows
+    FrameBatch::Also asg() { return {&dAsg, asgN * 4}; }
+    FrameBatch::Also lp() { return {&dLp, lpN * 8}; }
+    FrameBatch::Also off() { return {&dOff, (size_t)B * 24}; }
+
+    int upload(kbest_ctx *ctx, const uint64_t *frameKey)  // (after FrameBatch::upload has drawn the three buffers)
+    {
+        keyed = frameKey != nullptr;
+        HIP_TRY(ctx, hipMemcpy(dOff.p, asgOff, (size_t)B * 8, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(dOff.as<int64_t>() + B, lpOff, (size_t)B * 8, hipMemcpyHostToDevice));
+        if (keyed) HIP_TRY(ctx, hipMemcpy(dOff.as<int64_t>() + 2 * (size_t)B, frameKey, (size_t)B * 8, hipMemcpyHostToDevice));
+        return KBEST_OK;
+    }
+    const int64_t *d_asgOff() { return dOff.as<int64_t>(); }
+    const int64_t *d_lpOff() { return dOff.as<int64_t>() + B; }
+    const uint64_t *d_frameKey() { return keyed ? dOff.as<uint64_t>() + 2 * (size_t)B : nullptr; }
+    int32_t *d_assign() { return dAsg.as<int32_t>(); }
+    double *d_logProb() { return dLp.as<double>(); }
+
+    int download(kbest_ctx *ctx)  // (after the entry's hipStreamSynchronize) into hAsg, hLp: the caller's offsets hold there too
+    {
+        hAsg.resize(asgN);
+        hLp.resize(lpN);
+        HIP_TRY(ctx, hipMemcpy(hAsg.data(), dAsg.p, asgN * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(hLp.data(), dLp.p, lpN * 8, hipMemcpyDeviceToHost));
+        return KBEST_OK;
+    }
+    // every frame's own draws only: what lies between them in the caller's buffers is the caller's
+    void scatter(int32_t *assign, double *logProb) const
+    {
+        for (int b = 0; b < B; b++) {
+            memcpy(assign + asgOff[b], hAsg.data() + asgOff[b], draws(b) * 4);
+            memcpy(logProb + lpOff[b], hLp.data() + lpOff[b], (size_t)nSample * 8);
+        }
+    }
+};
+
+// An open cluster as the partial clustered kernel hands it out: its frame, root label, measurements, landmark rows and rows that
+// count; rowAt: its landmark rows in PartialRun::hRows; from: its [cL + m][m] sub-block within the frame's, in doubles.
+struct OpenCluster {
+    int b, root, m, cL, R;
+    size_t rowAt, from;
+    size_t block() const { return (size_t)(cL + m) * m; }
+    size_t slice() const { return (size_t)m * ((size_t)cL + 1); }  // doubles of its [m][cL + 1] probabilities
+};
+
+// One run of the partial clustered kernel over a frame batch, for the two hybrid host bodies (hybrid_impl, hybrid_sample_impl):
+// its six device buffers, its call, what it hands back and the open clusters of all frames in frame and label order.  What a
+// body does with an open cluster (its tier, its place in a tier's call, its row keys) stays with the body, beside open[i].
+struct PartialRun {
+    DevBuf dOut, dLabel, dDesc, dRows, dSub, dLp;  // out: info[B] | maxCluster[B] | nOpen[B] (int32)
+    int B = 0, maxRawRow = 1, maxCol = 1;
+    bool withLp = false;
+    std::vector<int32_t> hInt, hDesc, hRows, hLabel;  // hInt: info | maxCluster | nOpen; the others only where a frame is open
+    std::vector<double> hLp;                          // the kernel's sum of log Z_k over the clusters it answered (withLp)
+    std::vector<OpenCluster> open;
+
+    // the frame batch's buffers, these six, then the body's own, in one go (withLp_ = false: dLp is not drawn)
+    int upload(kbest_ctx *ctx, const char *who, FrameBatch &fb, const double *cost, bool withLp_, const std::vector<FrameBatch::Also> &own = {})
+    {
+        B = fb.B;
+        maxRawRow = fb.maxRawRow;
+        maxCol = fb.maxCol;
+        withLp = withLp_;
+        std::vector<FrameBatch::Also> all = {{&dOut, (size_t)B * 12},           {&dLabel, (size_t)B * maxCol * 4},
+                                             {&dDesc, (size_t)B * maxCol * 16}, {&dRows, (size_t)B * maxRawRow * 4},
+                                             {&dSub, fb.costN * 8},             {&dLp, withLp ? (size_t)B * 8 : 0}};
+        all.insert(all.end(), own.begin(), own.end());
+        return fb.upload(ctx, who, cost, all);
+    }
+    int launch(kbest_ctx *ctx, FrameBatch &fb, int condition, int maxExact)
+    {
+        int32_t *o4 = dOut.as<int32_t>();
+        return kbest_clustered_partial_batch_f64_dev(ctx, B, maxRawRow, maxCol, fb.d_nL(), fb.d_nM(), fb.d_cost(), fb.d_costOff(), condition,
+                                                     maxExact, fb.d_probs(), fb.d_probOff(), withLp ? dLp.as<double>() : nullptr, o4, o4 + B,
+                                                     dLabel.as<int32_t>(), maxCol, o4 + 2 * (size_t)B, dDesc.as<int32_t>(), maxCol,
+                                                     dRows.as<int32_t>(), maxRawRow, dSub.as<double>(), nullptr);
+    }
+    int download(kbest_ctx *ctx)  // (after the body's hipStreamSynchronize)
+    {
+        hInt.resize((size_t)B * 3);
+        HIP_TRY(ctx, hipMemcpy(hInt.data(), dOut.p, (size_t)B * 12, hipMemcpyDeviceToHost));
+        if (withLp) {
+            hLp.resize(B);
+            HIP_TRY(ctx, hipMemcpy(hLp.data(), dLp.p, (size_t)B * 8, hipMemcpyDeviceToHost));
+        }
+        if (*std::max_element(nOpen(), nOpen() + B) <= 0) return KBEST_OK;  // no frame is open: nothing more to fetch
+        hDesc.resize((size_t)B * maxCol * 4);
+        hRows.resize((size_t)B * maxRawRow);
+        hLabel.resize((size_t)B * maxCol);
+        HIP_TRY(ctx, hipMemcpy(hDesc.data(), dDesc.p, hDesc.size() * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(hRows.data(), dRows.p, hRows.size() * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(hLabel.data(), dLabel.p, hLabel.size() * 4, hipMemcpyDeviceToHost));
+        for (int b = 0; b < B; b++) {
+            size_t n = 0, rowAt = (size_t)b * maxRawRow;
+            for (int j = 0; j < nOpen()[b]; j++) {
+                const int32_t *d = hDesc.data() + ((size_t)b * maxCol + j) * 4;
+                open.push_back(OpenCluster{b, d[0], d[1], d[2], d[3], rowAt, n});
+                n += open.back().block();
+                rowAt += (size_t)d[2];
+            }
+        }
+        return KBEST_OK;
+    }
+    const int32_t *info() const { return hInt.data(); }
+    const int32_t *maxCluster() const { return hInt.data() + B; }
+    const int32_t *nOpen() const { return hInt.data() + 2 * (size_t)B; }
+    const int32_t *labels(int b) const { return hLabel.data() + (size_t)b * maxCol; }
+    const int32_t *rows(const OpenCluster &o) const { return hRows.data() + o.rowAt; }
+    double *d_sub() { return dSub.as<double>(); }
+    void release()  // (hybrid_impl, after FrameBatch::release: in the order their scope's end had)
+    {
+        for (DevBuf *d : {&dLp, &dSub, &dRows, &dDesc, &dLabel, &dOut}) d->release();
+    }
+};
+
+// What a frame is before its open clusters are looked at, from the partial kernel's info: refused, infeasible, or exact so far.
+inline int32_t method_of_info(int32_t info) { return info < 0 ? -1 : info == 0 ? -2 : 0; }
+
+// An enumerated cluster's say in its frame's method: no feasible assignment (nf <= 0) makes the frame infeasible; else the frame
+// is 1 (every enumeration complete within the cutoff), or 2 once one was cut at k.
+inline void enumerated_cluster_rule(int32_t &method, int nf, int k)
+{
+    if (nf <= 0) method = -2;
+    else if (method >= 0) method = (nf >= k || method == 2) ? 2 : 1;
+}
+
+// logPerm of a frame as it goes out: -inf for an infeasible frame, NaN for a refused one.
+inline double final_log_perm(int32_t method, double sum)
+{
+    return method == -2 ? -std::numeric_limits<double>::infinity() : method == -1 ? std::numeric_limits<double>::quiet_NaN() : sum;
+}
+
+// The per-cluster outputs of the frontier tier's two entries on the device and on the host: logZ[n] (double) | info[n] | width[n].
+struct FrontierOut {
+    DevBuf d;
+    int n = 0;
+    std::vector<double> logZ;
+    std::vector<int32_t> info, width;
+    hipError_t alloc(kbest_ctx *ctx, int n_) { n = n_; return d.alloc(ctx, (size_t)n * 16); }
+    double *d_logZ() { return d.as<double>(); }
+    int32_t *d_info() { return reinterpret_cast<int32_t *>(d.as<unsigned char>() + (size_t)n * 8); }
+    int32_t *d_width() { return d_info() + n; }
+    int download(kbest_ctx *ctx)  // (after the body's hipStreamSynchronize)
+    {
+        logZ.resize(n);
+        info.resize(n);
+        width.resize(n);
+        HIP_TRY(ctx, hipMemcpy(logZ.data(), d_logZ(), (size_t)n * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(info.data(), d_info(), (size_t)n * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(width.data(), d_width(), (size_t)n * 4, hipMemcpyDeviceToHost));
+        return KBEST_OK;
+    }
+    bool took(int t, int maxWidth) const { return info[t] >= 0 && width[t] <= maxWidth; }  // else: the next tier's
 };
 
 // Workgroups of a launch = frames in flight: as many as the batch has, as the chip holds at a time (wavesPerCU: what the
@@ -2835,8 +3038,7 @@ extern "C" int kbest_permanent_probs_batch_f64_dev(kbest_ctx *ctx, int B, int ma
                                                    void *stream)
 {
     if (!ctx) return KBEST_ERR_BAD_ARG;
-    int rc = check_frame_shape(ctx, "kbest_permanent_probs_batch_f64_dev", B, maxRawRow, maxCol, KBEST_PERM_MAX_COLS, PERM_COLS_TEXT);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(check_frame_shape(ctx, "kbest_permanent_probs_batch_f64_dev", B, maxRawRow, maxCol, KBEST_PERM_MAX_COLS, PERM_COLS_TEXT));
     if (!d_nL || !d_nM || !d_cost || !d_costOff || !d_probs || !d_probOff)
         return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_permanent_probs_batch_f64_dev: bad argument");
     if (B == 0) return KBEST_OK;
@@ -2846,8 +3048,7 @@ extern "C" int kbest_permanent_probs_batch_f64_dev(kbest_ctx *ctx, int B, int ma
     if (pl.slotDoubles > 0 && ctx->permBuf.bytes < (size_t)pl.slotDoubles * 8)  // asynchronous entry: never allocates
         return fail(ctx, KBEST_ERR_NOT_RESERVED, "kbest_permanent_probs_batch_f64_dev: call kbest_reserve_permanent first");
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    rc = order_behind_last(ctx, s);  // (one work space per context)
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(order_behind_last(ctx, s));  // (one work space per context)
     const Launched mark{ctx, s};
     kb::PermParams pp;
     pp.cost = d_cost;
@@ -2888,24 +3089,18 @@ extern "C" int kbest_permanent_probs_batch_f64(kbest_ctx *ctx, int B, const int3
     if (B == 0) return KBEST_OK;
     const char *who = "kbest_permanent_probs_batch_f64";
     FrameBatch fb;
-    int rc = fb.scan(ctx, who, B, nL, nM, costOff, probOff);
-    if (rc != KBEST_OK) return rc;
-    rc = check_frame_shape(ctx, who, B, fb.maxRawRow, fb.maxCol, KBEST_PERM_MAX_COLS, PERM_COLS_TEXT);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(fb.scan(ctx, who, B, nL, nM, costOff, probOff));
+    KB_TRY(check_frame_shape(ctx, who, B, fb.maxRawRow, fb.maxCol, KBEST_PERM_MAX_COLS, PERM_COLS_TEXT));
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    rc = kbest_reserve_permanent(ctx, B, fb.maxRawRow, fb.maxCol);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(kbest_reserve_permanent(ctx, B, fb.maxRawRow, fb.maxCol));
     DevBuf dPerm;
-    rc = fb.upload(ctx, who, cost, {{&dPerm, (size_t)B * 8}});
-    if (rc != KBEST_OK) return rc;
-    rc = kbest_permanent_probs_batch_f64_dev(ctx, B, fb.maxRawRow, fb.maxCol, fb.d_nL(), fb.d_nM(), fb.d_cost(), fb.d_costOff(), condition,
-                                             fb.d_probs(), fb.d_probOff(), dPerm.as<double>(), nullptr);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(fb.upload(ctx, who, cost, {{&dPerm, (size_t)B * 8}}));
+    KB_TRY(kbest_permanent_probs_batch_f64_dev(ctx, B, fb.maxRawRow, fb.maxCol, fb.d_nL(), fb.d_nM(), fb.d_cost(), fb.d_costOff(), condition,
+                                               fb.d_probs(), fb.d_probOff(), dPerm.as<double>(), nullptr));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     std::vector<double> hp;
-    rc = fb.download(ctx, hp);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(fb.download(ctx, hp));
     fb.scatter(hp, probs);
     if (perm) HIP_TRY(ctx, hipMemcpy(perm, dPerm.p, (size_t)B * 8, hipMemcpyDeviceToHost));
     return KBEST_OK;
@@ -2925,8 +3120,7 @@ extern "C" int kbest_sample_assoc_batch_f64_dev(kbest_ctx *ctx, int B, int maxRa
 {
     if (!ctx) return KBEST_ERR_BAD_ARG;
     const char *who = "kbest_sample_assoc_batch_f64_dev";
-    int rc = check_frame_shape(ctx, who, B, maxRawRow, maxCol, KBEST_PERM_MAX_COLS, PERM_COLS_TEXT);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(check_frame_shape(ctx, who, B, maxRawRow, maxCol, KBEST_PERM_MAX_COLS, PERM_COLS_TEXT));
     if (!d_nL || !d_nM || !d_cost || !d_costOff || !d_assign || !d_asgOff || !d_logProb || !d_lpOff || nSample < 1 ||
         (uint64_t)sampleBase + (uint64_t)nSample > ((uint64_t)1 << 32))
         return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_sample_assoc_batch_f64_dev: bad argument");
@@ -2937,8 +3131,7 @@ extern "C" int kbest_sample_assoc_batch_f64_dev(kbest_ctx *ctx, int B, int maxRa
     if (pl.slotDoubles > 0 && ctx->permBuf.bytes < (size_t)pl.slotDoubles * 8)  // asynchronous entry: never allocates
         return fail(ctx, KBEST_ERR_NOT_RESERVED, "kbest_sample_assoc_batch_f64_dev: call kbest_reserve_sample first");
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    rc = order_behind_last(ctx, s);  // (one work space per context)
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(order_behind_last(ctx, s));  // (one work space per context)
     const Launched mark{ctx, s};
     kb::SampleParams sp;
     sp.cost = d_cost;
@@ -2980,41 +3173,22 @@ extern "C" int kbest_sample_assoc_batch_f64(kbest_ctx *ctx, int B, const int32_t
     if (B == 0) return KBEST_OK;
     const char *who = "kbest_sample_assoc_batch_f64";
     FrameBatch fb;
-    int rc = fb.scan(ctx, who, B, nL, nM, costOff, nullptr);
-    if (rc != KBEST_OK) return rc;
-    rc = check_frame_shape(ctx, who, B, fb.maxRawRow, fb.maxCol, KBEST_PERM_MAX_COLS, PERM_COLS_TEXT);
-    if (rc != KBEST_OK) return rc;
-    size_t asgN = 0, lpN = 0;  // int32s / doubles up to the end of the last frame's draws
-    for (int b = 0; b < B; b++) {
-        if (asgOff[b] < 0 || lpOff[b] < 0) return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_sample_assoc_batch_f64: a negative offset");
-        asgN = std::max(asgN, (size_t)asgOff[b] + (size_t)nSample * (size_t)nM[b]);
-        lpN = std::max(lpN, (size_t)lpOff[b] + (size_t)nSample);
-    }
+    KB_TRY(fb.scan(ctx, who, B, nL, nM, costOff, nullptr));
+    KB_TRY(check_frame_shape(ctx, who, B, fb.maxRawRow, fb.maxCol, KBEST_PERM_MAX_COLS, PERM_COLS_TEXT));
+    DrawBatch db;
+    KB_TRY(db.scan(ctx, who, B, nM, nSample, asgOff, lpOff));
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    rc = kbest_reserve_sample(ctx, B, fb.maxRawRow, fb.maxCol);
-    if (rc != KBEST_OK) return rc;
-    DevBuf dPerm, dAsg, dLp, dOff;  // off: asgOff[B] | lpOff[B] | frameKey[B] (8 bytes each)
-    rc = fb.upload(ctx, who, cost, {{&dPerm, (size_t)B * 8}, {&dAsg, asgN * 4}, {&dLp, lpN * 8}, {&dOff, (size_t)B * 24}});
-    if (rc != KBEST_OK) return rc;
-    HIP_TRY(ctx, hipMemcpy(dOff.p, asgOff, (size_t)B * 8, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(dOff.as<int64_t>() + B, lpOff, (size_t)B * 8, hipMemcpyHostToDevice));
-    if (frameKey) HIP_TRY(ctx, hipMemcpy(dOff.as<int64_t>() + 2 * (size_t)B, frameKey, (size_t)B * 8, hipMemcpyHostToDevice));
-    rc = kbest_sample_assoc_batch_f64_dev(ctx, B, fb.maxRawRow, fb.maxCol, fb.d_nL(), fb.d_nM(), fb.d_cost(), fb.d_costOff(), condition,
-                                          nSample, seed, sampleBase, frameKey ? dOff.as<uint64_t>() + 2 * (size_t)B : nullptr,
-                                          dAsg.as<int32_t>(), dOff.as<int64_t>(), dLp.as<double>(), dOff.as<int64_t>() + B,
-                                          dPerm.as<double>(), nullptr);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(kbest_reserve_sample(ctx, B, fb.maxRawRow, fb.maxCol));
+    DevBuf dPerm;
+    KB_TRY(fb.upload(ctx, who, cost, {{&dPerm, (size_t)B * 8}, db.asg(), db.lp(), db.off()}));
+    KB_TRY(db.upload(ctx, frameKey));
+    KB_TRY(kbest_sample_assoc_batch_f64_dev(ctx, B, fb.maxRawRow, fb.maxCol, fb.d_nL(), fb.d_nM(), fb.d_cost(), fb.d_costOff(), condition,
+                                            nSample, seed, sampleBase, db.d_frameKey(), db.d_assign(), db.d_asgOff(), db.d_logProb(),
+                                            db.d_lpOff(), dPerm.as<double>(), nullptr));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    // every frame's own draws only: what lies between them in the caller's buffers is the caller's
-    std::vector<int32_t> hAsg(asgN);
-    std::vector<double> hLp(lpN);
-    HIP_TRY(ctx, hipMemcpy(hAsg.data(), dAsg.p, asgN * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(hLp.data(), dLp.p, lpN * 8, hipMemcpyDeviceToHost));
-    for (int b = 0; b < B; b++) {
-        memcpy(assign + asgOff[b], hAsg.data() + asgOff[b], (size_t)nSample * (size_t)nM[b] * 4);
-        memcpy(logProb + lpOff[b], hLp.data() + lpOff[b], (size_t)nSample * 8);
-    }
+    KB_TRY(db.download(ctx));
+    db.scatter(assign, logProb);
     if (perm) HIP_TRY(ctx, hipMemcpy(perm, dPerm.p, (size_t)B * 8, hipMemcpyDeviceToHost));
     return KBEST_OK;
 }
@@ -3057,8 +3231,7 @@ extern "C" int kbest_belief_probs_batch_f64_dev(kbest_ctx *ctx, int B, int maxRa
                                                 const int64_t *d_probOff, int32_t *d_iters, double *d_resid, void *stream)
 {
     if (!ctx) return KBEST_ERR_BAD_ARG;
-    int rc = check_frame_shape(ctx, "kbest_belief_probs_batch_f64_dev", B, maxRawRow, maxCol, KBEST_LBP_MAX_COLS, LBP_COLS_TEXT);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(check_frame_shape(ctx, "kbest_belief_probs_batch_f64_dev", B, maxRawRow, maxCol, KBEST_LBP_MAX_COLS, LBP_COLS_TEXT));
     if (!d_nL || !d_nM || !d_cost || !d_costOff || !d_probs || !d_probOff || maxIter < 0 || tol != tol)
         return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_belief_probs_batch_f64_dev: bad argument");
     if (B == 0) return KBEST_OK;
@@ -3068,8 +3241,7 @@ extern "C" int kbest_belief_probs_batch_f64_dev(kbest_ctx *ctx, int B, int maxRa
     if (pl.slotDoubles > 0 && ctx->lbpBuf.bytes < (size_t)pl.slotDoubles * 8)  // asynchronous entry: never allocates
         return fail(ctx, KBEST_ERR_NOT_RESERVED, "kbest_belief_probs_batch_f64_dev: call kbest_reserve_belief first");
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    rc = order_behind_last(ctx, s);  // (one work space per context)
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(order_behind_last(ctx, s));  // (one work space per context)
     const Launched mark{ctx, s};
     kb::LbpParams lp;
     lp.cost = d_cost;
@@ -3105,26 +3277,20 @@ extern "C" int kbest_belief_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t
     if (B == 0) return KBEST_OK;
     const char *who = "kbest_belief_probs_batch_f64";
     FrameBatch fb;
-    int rc = fb.scan(ctx, who, B, nL, nM, costOff, probOff);
-    if (rc != KBEST_OK) return rc;
-    rc = check_frame_shape(ctx, who, B, fb.maxRawRow, fb.maxCol, KBEST_LBP_MAX_COLS, LBP_COLS_TEXT);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(fb.scan(ctx, who, B, nL, nM, costOff, probOff));
+    KB_TRY(check_frame_shape(ctx, who, B, fb.maxRawRow, fb.maxCol, KBEST_LBP_MAX_COLS, LBP_COLS_TEXT));
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    rc = kbest_reserve_belief(ctx, B, fb.maxRawRow, fb.maxCol);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(kbest_reserve_belief(ctx, B, fb.maxRawRow, fb.maxCol));
     DevBuf dOut;  // resid[B] (double) | iters[B] (int32)
-    rc = fb.upload(ctx, who, cost, {{&dOut, (size_t)B * 12}});
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(fb.upload(ctx, who, cost, {{&dOut, (size_t)B * 12}}));
     unsigned char *o8 = dOut.as<unsigned char>();
-    rc = kbest_belief_probs_batch_f64_dev(ctx, B, fb.maxRawRow, fb.maxCol, fb.d_nL(), fb.d_nM(), fb.d_cost(), fb.d_costOff(), condition, tol,
-                                          maxIter, fb.d_probs(), fb.d_probOff(), reinterpret_cast<int32_t *>(o8 + (size_t)B * 8),
-                                          reinterpret_cast<double *>(o8), nullptr);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(kbest_belief_probs_batch_f64_dev(ctx, B, fb.maxRawRow, fb.maxCol, fb.d_nL(), fb.d_nM(), fb.d_cost(), fb.d_costOff(), condition, tol,
+                                            maxIter, fb.d_probs(), fb.d_probOff(), reinterpret_cast<int32_t *>(o8 + (size_t)B * 8),
+                                            reinterpret_cast<double *>(o8), nullptr));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     std::vector<double> hp;
-    rc = fb.download(ctx, hp);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(fb.download(ctx, hp));
     fb.scatter(hp, probs);
     if (resid) HIP_TRY(ctx, hipMemcpy(resid, o8, (size_t)B * 8, hipMemcpyDeviceToHost));
     if (iters) HIP_TRY(ctx, hipMemcpy(iters, o8 + (size_t)B * 8, (size_t)B * 4, hipMemcpyDeviceToHost));
@@ -3175,8 +3341,7 @@ extern "C" int kbest_reserve_clustered(kbest_ctx *ctx, int B, int maxRawRow, int
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     kb::ClusterPlan pl;
-    rc = cluster_plan_of(ctx, maxRawRow, maxCol, pl, "kbest_reserve_clustered");
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(cluster_plan_of(ctx, maxRawRow, maxCol, pl, "kbest_reserve_clustered"));
     const int g = frames_in_flight(ctx, CLUSTER_WAVES_PER_CU, pl.threads, pl.lds, pl.slotDoubles, B, ctx->clusWorkCap);
     return raw_reserve(ctx, ctx->clusBuf, (size_t)pl.slotDoubles * 8 * (size_t)g);
 }
@@ -3195,8 +3360,7 @@ static int cluster_launch_dev(kbest_ctx *ctx, const char *who, const ClusterPart
                               int32_t *d_label, int labelStride, void *stream)
 {
     if (!ctx) return KBEST_ERR_BAD_ARG;
-    int rc = check_frame_shape(ctx, who, B, maxRawRow, maxCol, KBEST_CLUSTER_MAX_COLS, CLUSTER_COLS_TEXT);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(check_frame_shape(ctx, who, B, maxRawRow, maxCol, KBEST_CLUSTER_MAX_COLS, CLUSTER_COLS_TEXT));
     if (!d_nL || !d_nM || !d_cost || !d_costOff || !d_probs || !d_probOff || (d_label && labelStride < maxCol))
         return fail(ctx, KBEST_ERR_BAD_ARG, (std::string(who) + ": bad argument").c_str());
     if (part && (part->maxExact < 0 || part->maxExact > KBEST_CLUSTER_MAX_SIZE || !part->d_nOpen || !part->d_openDesc ||
@@ -3206,13 +3370,11 @@ static int cluster_launch_dev(kbest_ctx *ctx, const char *who, const ClusterPart
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     kb::ClusterPlan pl;
-    rc = cluster_plan_of(ctx, maxRawRow, maxCol, pl, who);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(cluster_plan_of(ctx, maxRawRow, maxCol, pl, who));
     if (ctx->clusBuf.bytes < (size_t)pl.slotDoubles * 8)  // asynchronous entry: never allocates
         return fail(ctx, KBEST_ERR_NOT_RESERVED, (std::string(who) + ": call kbest_reserve_clustered first").c_str());
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    rc = order_behind_last(ctx, s);  // (one work space per context)
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(order_behind_last(ctx, s));  // (one work space per context)
     const Launched mark{ctx, s};
     kb::ClusterParams cp;
     cp.cost = d_cost;
@@ -3285,30 +3447,24 @@ extern "C" int kbest_clustered_probs_batch_f64(kbest_ctx *ctx, int B, const int3
     if (B == 0) return KBEST_OK;
     const char *who = "kbest_clustered_probs_batch_f64";
     FrameBatch fb;
-    int rc = fb.scan(ctx, who, B, nL, nM, costOff, probOff);
-    if (rc != KBEST_OK) return rc;
-    rc = check_frame_shape(ctx, who, B, fb.maxRawRow, fb.maxCol, KBEST_CLUSTER_MAX_COLS, CLUSTER_COLS_TEXT);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(fb.scan(ctx, who, B, nL, nM, costOff, probOff));
+    KB_TRY(check_frame_shape(ctx, who, B, fb.maxRawRow, fb.maxCol, KBEST_CLUSTER_MAX_COLS, CLUSTER_COLS_TEXT));
     if (label && labelStride < fb.maxCol) return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_clustered_probs_batch_f64: labelStride below the largest nM");
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    rc = kbest_reserve_clustered(ctx, B, fb.maxRawRow, fb.maxCol);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(kbest_reserve_clustered(ctx, B, fb.maxRawRow, fb.maxCol));
     DevBuf dOut, dLabel;  // out: logPerm[B] (double) | info[B] | maxCluster[B] (int32)
     const size_t labelBytes = label ? (size_t)B * (size_t)labelStride * 4 : 0;
-    rc = fb.upload(ctx, who, cost, {{&dOut, (size_t)B * 16}, {&dLabel, labelBytes}});
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(fb.upload(ctx, who, cost, {{&dOut, (size_t)B * 16}, {&dLabel, labelBytes}}));
     unsigned char *o8 = dOut.as<unsigned char>();
-    rc = kbest_clustered_probs_batch_f64_dev(ctx, B, fb.maxRawRow, fb.maxCol, fb.d_nL(), fb.d_nM(), fb.d_cost(), fb.d_costOff(), condition,
-                                             fb.d_probs(), fb.d_probOff(), reinterpret_cast<double *>(o8),
-                                             reinterpret_cast<int32_t *>(o8 + (size_t)B * 8),
-                                             reinterpret_cast<int32_t *>(o8 + (size_t)B * 12),
-                                             labelBytes ? dLabel.as<int32_t>() : nullptr, labelStride, nullptr);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(kbest_clustered_probs_batch_f64_dev(ctx, B, fb.maxRawRow, fb.maxCol, fb.d_nL(), fb.d_nM(), fb.d_cost(), fb.d_costOff(), condition,
+                                               fb.d_probs(), fb.d_probOff(), reinterpret_cast<double *>(o8),
+                                               reinterpret_cast<int32_t *>(o8 + (size_t)B * 8),
+                                               reinterpret_cast<int32_t *>(o8 + (size_t)B * 12),
+                                               labelBytes ? dLabel.as<int32_t>() : nullptr, labelStride, nullptr));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     std::vector<double> hp;
-    rc = fb.download(ctx, hp);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(fb.download(ctx, hp));
     fb.scatter(hp, probs);
     if (logPerm) HIP_TRY(ctx, hipMemcpy(logPerm, o8, (size_t)B * 8, hipMemcpyDeviceToHost));
     if (info) HIP_TRY(ctx, hipMemcpy(info, o8 + (size_t)B * 8, (size_t)B * 4, hipMemcpyDeviceToHost));
@@ -3334,8 +3490,7 @@ static int cluster_sample_dev(kbest_ctx *ctx, int partialMaxExact, int B, int ma
 {
     if (!ctx) return KBEST_ERR_BAD_ARG;
     const char *who = "kbest_clustered_sample_assoc_batch_f64_dev";
-    int rc = check_frame_shape(ctx, who, B, maxRawRow, maxCol, KBEST_CLUSTER_MAX_COLS, CLUSTER_COLS_TEXT);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(check_frame_shape(ctx, who, B, maxRawRow, maxCol, KBEST_CLUSTER_MAX_COLS, CLUSTER_COLS_TEXT));
     if (!d_nL || !d_nM || !d_cost || !d_costOff || !d_assign || !d_asgOff || !d_logProb || !d_lpOff || nSample < 1 ||
         (uint64_t)sampleBase + (uint64_t)nSample > ((uint64_t)1 << 32))
         return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_clustered_sample_assoc_batch_f64_dev: bad argument");
@@ -3343,13 +3498,11 @@ static int cluster_sample_dev(kbest_ctx *ctx, int partialMaxExact, int B, int ma
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     kb::ClusterPlan pl;
-    rc = cluster_plan_of(ctx, maxRawRow, maxCol, pl, who);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(cluster_plan_of(ctx, maxRawRow, maxCol, pl, who));
     if (ctx->clusBuf.bytes < (size_t)pl.slotDoubles * 8)  // asynchronous entry: never allocates
         return fail(ctx, KBEST_ERR_NOT_RESERVED, "kbest_clustered_sample_assoc_batch_f64_dev: call kbest_reserve_clustered_sample first");
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    rc = order_behind_last(ctx, s);  // (one work space per context)
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(order_behind_last(ctx, s));  // (one work space per context)
     const Launched mark{ctx, s};
     kb::ClusterSampleParams sp;
     sp.cost = d_cost;
@@ -3408,44 +3561,25 @@ extern "C" int kbest_clustered_sample_assoc_batch_f64(kbest_ctx *ctx, int B, con
     if (B == 0) return KBEST_OK;
     const char *who = "kbest_clustered_sample_assoc_batch_f64";
     FrameBatch fb;
-    int rc = fb.scan(ctx, who, B, nL, nM, costOff, nullptr);
-    if (rc != KBEST_OK) return rc;
-    rc = check_frame_shape(ctx, who, B, fb.maxRawRow, fb.maxCol, KBEST_CLUSTER_MAX_COLS, CLUSTER_COLS_TEXT);
-    if (rc != KBEST_OK) return rc;
-    size_t asgN = 0, lpN = 0;  // int32s / doubles up to the end of the last frame's draws
-    for (int b = 0; b < B; b++) {
-        if (asgOff[b] < 0 || lpOff[b] < 0) return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_clustered_sample_assoc_batch_f64: a negative offset");
-        asgN = std::max(asgN, (size_t)asgOff[b] + (size_t)nSample * (size_t)nM[b]);
-        lpN = std::max(lpN, (size_t)lpOff[b] + (size_t)nSample);
-    }
+    KB_TRY(fb.scan(ctx, who, B, nL, nM, costOff, nullptr));
+    KB_TRY(check_frame_shape(ctx, who, B, fb.maxRawRow, fb.maxCol, KBEST_CLUSTER_MAX_COLS, CLUSTER_COLS_TEXT));
+    DrawBatch db;
+    KB_TRY(db.scan(ctx, who, B, nM, nSample, asgOff, lpOff));
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    rc = kbest_reserve_clustered_sample(ctx, B, fb.maxRawRow, fb.maxCol);
-    if (rc != KBEST_OK) return rc;
-    DevBuf dOut, dAsg, dLp, dOff;  // out: logPerm[B] (double) | info[B] | maxCluster[B] (int32); off: asgOff[B] | lpOff[B] | frameKey[B]
-    rc = fb.upload(ctx, who, cost, {{&dOut, (size_t)B * 16}, {&dAsg, asgN * 4}, {&dLp, lpN * 8}, {&dOff, (size_t)B * 24}});
-    if (rc != KBEST_OK) return rc;
-    HIP_TRY(ctx, hipMemcpy(dOff.p, asgOff, (size_t)B * 8, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(dOff.as<int64_t>() + B, lpOff, (size_t)B * 8, hipMemcpyHostToDevice));
-    if (frameKey) HIP_TRY(ctx, hipMemcpy(dOff.as<int64_t>() + 2 * (size_t)B, frameKey, (size_t)B * 8, hipMemcpyHostToDevice));
+    KB_TRY(kbest_reserve_clustered_sample(ctx, B, fb.maxRawRow, fb.maxCol));
+    DevBuf dOut;  // out: logPerm[B] (double) | info[B] | maxCluster[B] (int32)
+    KB_TRY(fb.upload(ctx, who, cost, {{&dOut, (size_t)B * 16}, db.asg(), db.lp(), db.off()}));
+    KB_TRY(db.upload(ctx, frameKey));
     unsigned char *o8 = dOut.as<unsigned char>();
-    rc = kbest_clustered_sample_assoc_batch_f64_dev(ctx, B, fb.maxRawRow, fb.maxCol, fb.d_nL(), fb.d_nM(), fb.d_cost(), fb.d_costOff(),
-                                                    condition, nSample, seed, sampleBase,
-                                                    frameKey ? dOff.as<uint64_t>() + 2 * (size_t)B : nullptr, dAsg.as<int32_t>(),
-                                                    dOff.as<int64_t>(), dLp.as<double>(), dOff.as<int64_t>() + B,
-                                                    reinterpret_cast<double *>(o8), reinterpret_cast<int32_t *>(o8 + (size_t)B * 8),
-                                                    reinterpret_cast<int32_t *>(o8 + (size_t)B * 12), nullptr);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(kbest_clustered_sample_assoc_batch_f64_dev(ctx, B, fb.maxRawRow, fb.maxCol, fb.d_nL(), fb.d_nM(), fb.d_cost(), fb.d_costOff(),
+                                                      condition, nSample, seed, sampleBase, db.d_frameKey(), db.d_assign(), db.d_asgOff(),
+                                                      db.d_logProb(), db.d_lpOff(), reinterpret_cast<double *>(o8),
+                                                      reinterpret_cast<int32_t *>(o8 + (size_t)B * 8),
+                                                      reinterpret_cast<int32_t *>(o8 + (size_t)B * 12), nullptr));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    // every frame's own draws only: what lies between them in the caller's buffers is the caller's
-    std::vector<int32_t> hAsg(asgN);
-    std::vector<double> hLp(lpN);
-    HIP_TRY(ctx, hipMemcpy(hAsg.data(), dAsg.p, asgN * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(hLp.data(), dLp.p, lpN * 8, hipMemcpyDeviceToHost));
-    for (int b = 0; b < B; b++) {
-        memcpy(assign + asgOff[b], hAsg.data() + asgOff[b], (size_t)nSample * (size_t)nM[b] * 4);
-        memcpy(logProb + lpOff[b], hLp.data() + lpOff[b], (size_t)nSample * 8);
-    }
+    KB_TRY(db.download(ctx));
+    db.scatter(assign, logProb);
     if (logPerm) HIP_TRY(ctx, hipMemcpy(logPerm, o8, (size_t)B * 8, hipMemcpyDeviceToHost));
     if (info) HIP_TRY(ctx, hipMemcpy(info, o8 + (size_t)B * 8, (size_t)B * 4, hipMemcpyDeviceToHost));
     if (maxCluster) HIP_TRY(ctx, hipMemcpy(maxCluster, o8 + (size_t)B * 12, (size_t)B * 4, hipMemcpyDeviceToHost));
@@ -3824,8 +3958,7 @@ static int big_reserve(kbest_ctx *ctx, size_t layerBytes, int maxM, int maxRows)
     const kb::BigClusterSmall s = kb::bigcluster_small(maxM, maxRows);
     const size_t fixed = (size_t)(s.total - (long long)maxRows * kb::bigcluster_workgroups(maxM) * maxM + (long long)maxRows * maxM);
     const size_t smallBytes = (size_t)kb::KB_BIGCLUSTER_PACK * fixed * 8 + layerBytes / 1024 * KBEST_BIGCLUSTER_MAX_SIZE + 4096;
-    int rc = raw_reserve(ctx, ctx->bigLayers, layerBytes);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(raw_reserve(ctx, ctx->bigLayers, layerBytes));
     return raw_reserve(ctx, ctx->bigSmall, smallBytes);
 }
 
@@ -3869,8 +4002,7 @@ int kbest_bigcluster_probs_f64_dev(kbest_ctx *ctx, int n, const int32_t *m, cons
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    int rc = order_behind_last(ctx, s);  // (one work space per context)
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(order_behind_last(ctx, s));  // (one work space per context)
     const Launched mark{ctx, s};
     hold_if_capturing(s, {&ctx->bigLayers, &ctx->bigSmall});
     kb::BigClusterPack pk;
@@ -3947,8 +4079,7 @@ int kbest_reserve_frontier(kbest_ctx *ctx, int n, int maxM, int maxRows)
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int g = frames_in_flight(ctx, FRONTIER_WAVES_PER_CU, kb::KB_FRONTIER_THREADS, FRONTIER_LDS, (long long)(ctx->frSlot / 8), n,
                                    ctx->frWorkCap);
-    int rc = raw_reserve(ctx, ctx->frLayers, ctx->frSlot * (size_t)g);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(raw_reserve(ctx, ctx->frLayers, ctx->frSlot * (size_t)g));
     return raw_reserve(ctx, ctx->frPlan, (size_t)g * (size_t)maxRows * kb::KB_FRONTIER_STEP_DOUBLES * 8);
 }
 
@@ -3980,8 +4111,7 @@ int kbest_frontier_probs_f64_dev(kbest_ctx *ctx, int n, const int32_t *m, const 
     w.plan = static_cast<double *>(ctx->frPlan.p);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    int rc = order_behind_last(ctx, s);  // (one work space per context)
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(order_behind_last(ctx, s));  // (one work space per context)
     const Launched mark{ctx, s};
     hold_if_capturing(s, {&ctx->frLayers, &ctx->frPlan});
     kb::FrontierPack pk;
@@ -4039,8 +4169,7 @@ int kbest_frontier_sample_f64_dev(kbest_ctx *ctx, int n, const int32_t *m, const
     w.plan = static_cast<double *>(ctx->frPlan.p);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    int rc = order_behind_last(ctx, s);  // (one work space per context)
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(order_behind_last(ctx, s));  // (one work space per context)
     const Launched mark{ctx, s};
     hold_if_capturing(s, {&ctx->frLayers, &ctx->frPlan});
     kb::FrontierSamplePack pk;
@@ -4145,6 +4274,67 @@ static long long frontier_grid(const kbest_ctx *ctx, long long n, long long plan
     return g;
 }
 
+// What the two one-stream hybrid entries work out before they launch anything, for a call of (B, maxRawRow, maxCol): where
+// everything lies in ctx->hybBuf, the sweep's work space and grid, the clustered plan, and whether what was reserved suffices
+// (the sampling entry has more to ask).  An asynchronous entry never allocates.
+struct HybridDevPlan {
+    HybridLayout L;
+    kb::FrontierWork w;
+    long long grid;
+    bool reserved;
+    unsigned char *h8;
+    int32_t *i32(size_t off) const { return reinterpret_cast<int32_t *>(h8 + off); }
+    double *f64(size_t off) const { return reinterpret_cast<double *>(h8 + off); }
+};
+static int hybrid_dev_plan(kbest_ctx *ctx, const char *who, int B, int maxRawRow, int maxCol, HybridDevPlan &d)
+{
+    d.L = hybrid_layout(B, maxRawRow, maxCol);
+    d.w.slotDoubles = (long long)(ctx->frSlot / 8);
+    d.w.planDoubles = (long long)maxRawRow * kb::KB_FRONTIER_STEP_DOUBLES;
+    d.grid = frontier_grid(ctx, d.L.cap, d.w.planDoubles);
+    kb::ClusterPlan pl;
+    KB_TRY(cluster_plan_of(ctx, maxRawRow, maxCol, pl, who));
+    d.reserved = ctx->hybBuf.bytes >= d.L.total && d.grid >= 1 && ctx->clusBuf.bytes >= (size_t)pl.slotDoubles * 8;
+    d.w.layers = static_cast<double *>(ctx->frLayers.p);
+    d.w.plan = static_cast<double *>(ctx->frPlan.p);
+    d.h8 = static_cast<unsigned char *>(ctx->hybBuf.p);
+    return KBEST_OK;
+}
+
+// The fields kb::HybridParams and kb::HybridSampleParams share, by name: the caller's frames and per-frame outputs, and the parts
+// of ctx->hybBuf the partial kernel, the gather and the sweep write.  (extern "C++": a template inside this file's extern "C".)
+extern "C++" template <class P>
+void hybrid_common_params(P &p, const HybridDevPlan &d, int B, int maxRawRow, int maxCol, int condition, int maxWidth,
+                                 const int32_t *d_nL, const int32_t *d_nM, const double *d_cost, const int64_t *d_costOff,
+                                 double *d_logPerm, int32_t *d_method, int32_t *d_nOpen, int32_t *d_nFrontier)
+{
+    p.nL = d_nL;
+    p.nM = d_nM;
+    p.costOff = reinterpret_cast<const long long *>(d_costOff);
+    p.cost = d_cost;
+    p.logPerm = d_logPerm;
+    p.method = d_method;
+    p.nOpenOut = d_nOpen;
+    p.nFrontier = d_nFrontier;
+    p.info = d.i32(d.L.info);
+    p.nOpen = d.i32(d.L.nOpen);
+    p.label = d.i32(d.L.label);
+    p.openDesc = d.i32(d.L.desc);
+    p.openRows = d.i32(d.L.rows);
+    p.list = reinterpret_cast<kb::HybridItem *>(d.h8 + d.L.list);
+    p.count = d.i32(d.L.count);
+    p.first = d.i32(d.L.first);
+    p.logZ = d.f64(d.L.logZ);
+    p.finfo = d.i32(d.L.finfo);
+    p.width = d.i32(d.L.width);
+    p.packStride = d.L.packStride;
+    p.B = B;
+    p.maxRawRow = maxRawRow;
+    p.maxCol = maxCol;
+    p.condition = condition ? 1 : 0;
+    p.maxWidth = maxWidth;
+}
+
 int kbest_reserve_hybrid_dev(kbest_ctx *ctx, int B, int maxRawRow, int maxCol)
 {
     if (!ctx) return KBEST_ERR_BAD_ARG;
@@ -4152,12 +4342,10 @@ int kbest_reserve_hybrid_dev(kbest_ctx *ctx, int B, int maxRawRow, int maxCol)
     if (rc != KBEST_OK || B == 0) return rc;
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    rc = kbest_reserve_clustered(ctx, B, maxRawRow, maxCol);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(kbest_reserve_clustered(ctx, B, maxRawRow, maxCol));
     const HybridLayout L = hybrid_layout(B, maxRawRow, maxCol);
-    rc = kbest_reserve_frontier(ctx, L.cap > (1 << 30) ? (1 << 30) : (int)L.cap, maxCol < KBEST_FRONTIER_MAX_COLS ? maxCol : KBEST_FRONTIER_MAX_COLS,
-                                maxRawRow);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(kbest_reserve_frontier(ctx, L.cap > (1 << 30) ? (1 << 30) : (int)L.cap, maxCol < KBEST_FRONTIER_MAX_COLS ? maxCol : KBEST_FRONTIER_MAX_COLS,
+                                  maxRawRow));
     return raw_reserve(ctx, ctx->hybBuf, L.total);
 }
 
@@ -4169,8 +4357,7 @@ int kbest_hybrid_frontier_probs_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawR
 {
     if (!ctx) return KBEST_ERR_BAD_ARG;
     const char *who = "kbest_hybrid_frontier_probs_batch_f64_dev";
-    int rc = check_frame_shape(ctx, who, B, maxRawRow, maxCol, KBEST_CLUSTER_MAX_COLS, CLUSTER_COLS_TEXT);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(check_frame_shape(ctx, who, B, maxRawRow, maxCol, KBEST_CLUSTER_MAX_COLS, CLUSTER_COLS_TEXT));
     if (maxExact < 0 || maxExact > KBEST_CLUSTER_MAX_SIZE || maxWidth < 1 || maxWidth > KBEST_FRONTIER_MAX_WIDTH)
         return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_hybrid_frontier_probs_batch_f64_dev: bad argument (maxExact 0 .. 16, maxWidth 1 .. 16; "
                                             "maxWidth = 0 would turn the frontier tier off, and nothing else answers an open cluster here)");
@@ -4179,62 +4366,28 @@ int kbest_hybrid_frontier_probs_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawR
         return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_hybrid_frontier_probs_batch_f64_dev: bad argument");
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // everything is checked before anything is launched; an asynchronous entry never allocates
-    const HybridLayout L = hybrid_layout(B, maxRawRow, maxCol);
-    kb::FrontierWork w;
-    w.slotDoubles = (long long)(ctx->frSlot / 8);
-    w.planDoubles = (long long)maxRawRow * kb::KB_FRONTIER_STEP_DOUBLES;
-    const long long g = frontier_grid(ctx, L.cap, w.planDoubles);
-    kb::ClusterPlan pl;
-    rc = cluster_plan_of(ctx, maxRawRow, maxCol, pl, who);
-    if (rc != KBEST_OK) return rc;
-    if (ctx->hybBuf.bytes < L.total || g < 1 || ctx->clusBuf.bytes < (size_t)pl.slotDoubles * 8)
-        return fail(ctx, KBEST_ERR_NOT_RESERVED, "kbest_hybrid_frontier_probs_batch_f64_dev: call kbest_reserve_hybrid_dev first");
-    w.layers = static_cast<double *>(ctx->frLayers.p);
-    w.plan = static_cast<double *>(ctx->frPlan.p);
+    // everything is checked before anything is launched
+    HybridDevPlan d;
+    KB_TRY(hybrid_dev_plan(ctx, who, B, maxRawRow, maxCol, d));
+    if (!d.reserved) return fail(ctx, KBEST_ERR_NOT_RESERVED, "kbest_hybrid_frontier_probs_batch_f64_dev: call kbest_reserve_hybrid_dev first");
+    const HybridLayout &L = d.L;
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    unsigned char *h8 = static_cast<unsigned char *>(ctx->hybBuf.p);
-    auto i32 = [h8](size_t off) { return reinterpret_cast<int32_t *>(h8 + off); };
     // the partial kernel: orders the stream behind the context's last launch and marks its own
-    rc = kbest_clustered_partial_batch_f64_dev(ctx, B, maxRawRow, maxCol, d_nL, d_nM, d_cost, d_costOff, condition, maxExact, d_probs,
-                                               d_probOff, d_logPerm, i32(L.info), d_maxCluster, i32(L.label), maxCol, i32(L.nOpen),
-                                               i32(L.desc), maxCol, i32(L.rows), maxRawRow, d_sub, stream);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(kbest_clustered_partial_batch_f64_dev(ctx, B, maxRawRow, maxCol, d_nL, d_nM, d_cost, d_costOff, condition, maxExact, d_probs,
+                                                 d_probOff, d_logPerm, d.i32(L.info), d_maxCluster, d.i32(L.label), maxCol, d.i32(L.nOpen),
+                                                 d.i32(L.desc), maxCol, d.i32(L.rows), maxRawRow, d_sub, stream));
     const Launched mark{ctx, s};
     hold_if_capturing(s, {&ctx->hybBuf, &ctx->frLayers, &ctx->frPlan});  // (the clustered work space: by the partial kernel's entry)
     kb::HybridParams hp;
-    hp.nL = d_nL;
-    hp.nM = d_nM;
-    hp.costOff = reinterpret_cast<const long long *>(d_costOff);
+    hybrid_common_params(hp, d, B, maxRawRow, maxCol, condition, maxWidth, d_nL, d_nM, d_cost, d_costOff, d_logPerm, d_method, d_nOpen,
+                         d_nFrontier);
     hp.probOff = reinterpret_cast<const long long *>(d_probOff);
-    hp.cost = d_cost;
     hp.probs = d_probs;
-    hp.logPerm = d_logPerm;
-    hp.method = d_method;
-    hp.nOpenOut = d_nOpen;
-    hp.nFrontier = d_nFrontier;
-    hp.info = i32(L.info);
-    hp.nOpen = i32(L.nOpen);
-    hp.label = i32(L.label);
-    hp.openDesc = i32(L.desc);
-    hp.openRows = i32(L.rows);
-    hp.list = reinterpret_cast<kb::HybridItem *>(h8 + L.list);
-    hp.count = i32(L.count);
-    hp.first = i32(L.first);
-    double *packed = reinterpret_cast<double *>(h8 + L.packed), *logZ = reinterpret_cast<double *>(h8 + L.logZ);
-    hp.packed = packed;
-    hp.logZ = logZ;
-    hp.finfo = i32(L.finfo);
-    hp.width = i32(L.width);
-    hp.packStride = L.packStride;
-    hp.B = B;
-    hp.maxRawRow = maxRawRow;
-    hp.maxCol = maxCol;
-    hp.condition = condition ? 1 : 0;
-    hp.maxWidth = maxWidth;
+    hp.packed = d.f64(L.packed);
     hipError_t e = kb::launch_hybrid_gather(hp, s);
     if (e == hipSuccess)
-        e = kb::launch_frontier_list(hp.list, hp.count, d_sub, packed, logZ, i32(L.finfo), i32(L.width), w, (int)g, s);
+        e = kb::launch_frontier_list(hp.list, hp.count, d_sub, d.f64(L.packed), d.f64(L.logZ), d.i32(L.finfo), d.i32(L.width), d.w,
+                                     (int)d.grid, s);
     if (e == hipSuccess) e = kb::launch_hybrid_scatter(hp, s);
     if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "hybrid kernel launch", e);
     return KBEST_OK;
@@ -4253,67 +4406,33 @@ static int hybrid_impl(kbest_ctx *ctx, const char *who, int B, const int32_t *nL
                        int32_t *maxCluster)
 {
     FrameBatch fb;
-    int rc = fb.scan(ctx, who, B, nL, nM, costOff, probOff);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(fb.scan(ctx, who, B, nL, nM, costOff, probOff));
     const int maxRawRow = fb.maxRawRow, maxCol = fb.maxCol;
-    rc = check_frame_shape(ctx, who, B, maxRawRow, maxCol, KBEST_CLUSTER_MAX_COLS, CLUSTER_COLS_TEXT);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(check_frame_shape(ctx, who, B, maxRawRow, maxCol, KBEST_CLUSTER_MAX_COLS, CLUSTER_COLS_TEXT));
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    rc = kbest_reserve_clustered(ctx, B, maxRawRow, maxCol);
-    if (rc != KBEST_OK) return rc;
-    std::vector<double> hp, hLp;
-    std::vector<int32_t> hInt((size_t)B * 3), hDesc, hRows, hLabel;  // info | maxCluster | nOpen
-    // tier: 0 enumerated, 1 big-cluster, 2 frontier; at: its place among the clusters of its tier; from: its sub-block in the frame's
-    struct Open { int b, root, m, cL; size_t rowAt, from; int tier, at; };
-    std::vector<Open> open;
+    KB_TRY(kbest_reserve_clustered(ctx, B, maxRawRow, maxCol));
+    PartialRun pr;
+    const std::vector<OpenCluster> &open = pr.open;
+    struct Place { int tier = 0, at = -1; };  // tier: 0 enumerated, 1 big-cluster, 2 frontier; at: its place among the clusters of its tier
+    std::vector<Place> place;                 // beside open
+    std::vector<double> hp;
     std::vector<double> sub;      // the enumerated clusters' sub-blocks, packed
     std::vector<int64_t> sCo, sPo;
     std::vector<double> bigP, bigLogZ;  // the big clusters' [m][nL_k + 1] probabilities, packed, and their log Z_k
     std::vector<int32_t> bigInfo;
     std::vector<int64_t> bPo;
-    std::vector<double> frP, frLogZ;    // the same of the frontier tier
-    std::vector<int32_t> frInfo;
+    std::vector<double> frP;            // the same of the frontier tier
+    FrontierOut fr;
     std::vector<int64_t> fPo;
-    const size_t descStride = (size_t)maxCol, rowStride = (size_t)maxRawRow;
     {
-        DevBuf dOut, dLabel, dDesc, dRows, dSub, dLp;  // out: info[B] | maxCluster[B] | nOpen[B] (int32)
-        rc = fb.upload(ctx, who, cost, {{&dOut, (size_t)B * 12}, {&dLabel, (size_t)B * maxCol * 4}, {&dDesc, (size_t)B * descStride * 16},
-                                        {&dRows, (size_t)B * rowStride * 4}, {&dSub, fb.costN * 8}, {&dLp, logPerm ? (size_t)B * 8 : 0}});
-        if (rc != KBEST_OK) return rc;
-        int32_t *o4 = dOut.as<int32_t>();
-        rc = kbest_clustered_partial_batch_f64_dev(ctx, B, maxRawRow, maxCol, fb.d_nL(), fb.d_nM(), fb.d_cost(), fb.d_costOff(), condition,
-                                                   maxExact, fb.d_probs(), fb.d_probOff(), logPerm ? dLp.as<double>() : nullptr, o4, o4 + B,
-                                                   dLabel.as<int32_t>(), maxCol, o4 + 2 * (size_t)B, dDesc.as<int32_t>(),
-                                                   (int)descStride, dRows.as<int32_t>(), (int)rowStride, dSub.as<double>(), nullptr);
-        if (rc != KBEST_OK) return rc;
+        KB_TRY(pr.upload(ctx, who, fb, cost, logPerm != nullptr));
+        KB_TRY(pr.launch(ctx, fb, condition, maxExact));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        rc = fb.download(ctx, hp);
-        if (rc != KBEST_OK) return rc;
-        HIP_TRY(ctx, hipMemcpy(hInt.data(), dOut.p, (size_t)B * 12, hipMemcpyDeviceToHost));
-        if (logPerm) {
-            hLp.resize(B);
-            HIP_TRY(ctx, hipMemcpy(hLp.data(), dLp.p, (size_t)B * 8, hipMemcpyDeviceToHost));
-        }
-        const int32_t *hOpen = hInt.data() + 2 * (size_t)B;
-        bool any = false;
-        for (int b = 0; b < B; b++) any = any || hOpen[b] > 0;
-        if (any) {  // the descriptors (small), then the sub-blocks of the frames that have open clusters and nothing else
-            hDesc.resize((size_t)B * descStride * 4);
-            hRows.resize((size_t)B * rowStride);
-            hLabel.resize((size_t)B * maxCol);
-            HIP_TRY(ctx, hipMemcpy(hDesc.data(), dDesc.p, hDesc.size() * 4, hipMemcpyDeviceToHost));
-            HIP_TRY(ctx, hipMemcpy(hRows.data(), dRows.p, hRows.size() * 4, hipMemcpyDeviceToHost));
-            HIP_TRY(ctx, hipMemcpy(hLabel.data(), dLabel.p, hLabel.size() * 4, hipMemcpyDeviceToHost));
-            for (int b = 0; b < B; b++) {  // every open cluster, in frame and label order
-                size_t n = 0, rowAt = (size_t)b * rowStride;
-                for (int j = 0; j < hOpen[b]; j++) {
-                    const int32_t *d = hDesc.data() + ((size_t)b * descStride + j) * 4;
-                    open.push_back(Open{b, d[0], d[1], d[2], rowAt, n, 0, -1});
-                    n += (size_t)(d[2] + d[1]) * d[1];
-                    rowAt += (size_t)d[2];
-                }
-            }
+        KB_TRY(fb.download(ctx, hp));
+        KB_TRY(pr.download(ctx));
+        place.resize(open.size());
+        if (!open.empty()) {  // then the sub-blocks of the frames that have open clusters and nothing else
             if (maxWidth > 0) {  // the frontier tier first: the open clusters of all frames in one call
                 std::vector<int32_t> fM, fL;
                 std::vector<int64_t> fSo;
@@ -4321,51 +4440,41 @@ static int hybrid_impl(kbest_ctx *ctx, const char *who, int B, const int32_t *nL
                 size_t fpat = 0;
                 int frM = 1, frRows = 1;
                 for (size_t i = 0; i < open.size(); i++) {
-                    const Open &o = open[i];
+                    const OpenCluster &o = open[i];
                     if (o.m > KBEST_FRONTIER_MAX_COLS) continue;
                     fWho.push_back(i);
                     fM.push_back(o.m);
                     fL.push_back(o.cL);
                     fSo.push_back(costOff[o.b] + (int64_t)o.from);
                     fPo.push_back((int64_t)fpat);
-                    fpat += (size_t)o.m * ((size_t)o.cL + 1);
+                    fpat += o.slice();
                     if (o.m > frM) frM = o.m;
                     if (o.cL + o.m > frRows) frRows = o.cL + o.m;
                 }
                 if (!fM.empty()) {
                     const int nf = (int)fM.size();
-                    rc = kbest_reserve_frontier(ctx, nf, frM, frRows);
-                    if (rc != KBEST_OK) return rc;
-                    DevBuf dFrP, dFrOut;  // out: logZ[nf] (double) | info[nf] | width[nf] (int32)
+                    KB_TRY(kbest_reserve_frontier(ctx, nf, frM, frRows));
+                    DevBuf dFrP;
                     hipError_t e;
-                    if ((e = dFrP.alloc(ctx, fpat * 8)) != hipSuccess || (e = dFrOut.alloc(ctx, (size_t)nf * 16)) != hipSuccess)
+                    if ((e = dFrP.alloc(ctx, fpat * 8)) != hipSuccess || (e = fr.alloc(ctx, nf)) != hipSuccess)
                         return fail(ctx, KBEST_ERR_NOMEM, (std::string(who) + ": device buffers").c_str(), e);
-                    unsigned char *f8 = dFrOut.as<unsigned char>();
-                    int32_t *f4 = reinterpret_cast<int32_t *>(f8 + (size_t)nf * 8);
-                    rc = kbest_frontier_probs_f64_dev(ctx, nf, fM.data(), fL.data(), fSo.data(), fPo.data(), dSub.as<double>(),
-                                                      dFrP.as<double>(), reinterpret_cast<double *>(f8), f4, f4 + nf, nullptr);
-                    if (rc != KBEST_OK) return rc;
+                    KB_TRY(kbest_frontier_probs_f64_dev(ctx, nf, fM.data(), fL.data(), fSo.data(), fPo.data(), pr.d_sub(), dFrP.as<double>(),
+                                                        fr.d_logZ(), fr.d_info(), fr.d_width(), nullptr));
                     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                    std::vector<int32_t> frWidth(nf);
                     frP.resize(fpat);
-                    frLogZ.resize(nf);
-                    frInfo.resize(nf);
                     HIP_TRY(ctx, hipMemcpy(frP.data(), dFrP.p, fpat * 8, hipMemcpyDeviceToHost));
-                    HIP_TRY(ctx, hipMemcpy(frLogZ.data(), f8, (size_t)nf * 8, hipMemcpyDeviceToHost));
-                    HIP_TRY(ctx, hipMemcpy(frInfo.data(), f4, (size_t)nf * 4, hipMemcpyDeviceToHost));
-                    HIP_TRY(ctx, hipMemcpy(frWidth.data(), f4 + nf, (size_t)nf * 4, hipMemcpyDeviceToHost));
+                    KB_TRY(fr.download(ctx));
                     for (int t = 0; t < nf; t++)
-                        if (frInfo[t] >= 0 && frWidth[t] <= maxWidth) {
-                            open[fWho[t]].tier = 2;
-                            open[fWho[t]].at = t;
-                        }
+                        if (fr.took(t, maxWidth)) place[fWho[t]] = Place{2, t};
+                    fr.d.release();  // (back to the cache with dFrP: the big-cluster tier draws next)
                 }
             }
             size_t total = 0;
-            for (Open &o : open) {
-                if (o.tier != 0) continue;
-                if (maxBig > 0 && o.m <= maxBig && big_layers_bytes(o.m, o.cL + o.m) <= ctx->bigWorkCap) o.tier = 1;
-                else total += (size_t)(o.cL + o.m) * o.m;
+            for (size_t i = 0; i < open.size(); i++) {
+                const OpenCluster &o = open[i];
+                if (place[i].tier != 0) continue;
+                if (maxBig > 0 && o.m <= maxBig && big_layers_bytes(o.m, o.cL + o.m) <= ctx->bigWorkCap) place[i].tier = 1;
+                else total += o.block();
             }
             sub.resize(total);
             std::vector<int32_t> bM, bL;
@@ -4379,37 +4488,36 @@ static int hybrid_impl(kbest_ctx *ctx, const char *who, int B, const int32_t *nL
                 size_t n = 0, nKeep = 0;
                 bool onlyEnumerated = true;
                 for (size_t t = i; t < e; t++) {
-                    Open &o = open[t];
-                    const size_t sz = (size_t)(o.cL + o.m) * o.m;
-                    n += sz;
-                    if (o.tier == 1) {
-                        o.at = (int)bM.size();
+                    const OpenCluster &o = open[t];
+                    Place &p = place[t];
+                    n += o.block();
+                    if (p.tier == 1) {
+                        p.at = (int)bM.size();
                         bM.push_back(o.m);
                         bL.push_back(o.cL);
                         bSo.push_back(costOff[b] + (int64_t)o.from);
                         bPo.push_back((int64_t)bpat);
-                        bpat += (size_t)o.m * ((size_t)o.cL + 1);
+                        bpat += o.slice();
                         bigLayers += big_layers_bytes(o.m, o.cL + o.m);
                         if (o.m > bigM) bigM = o.m;
                         if (o.cL + o.m > bigRows) bigRows = o.cL + o.m;
-                    } else if (o.tier == 0) {
-                        o.at = (int)sCo.size();
+                    } else if (p.tier == 0) {
+                        p.at = (int)sCo.size();
                         sCo.push_back((int64_t)(at + nKeep));
                         sPo.push_back((int64_t)pat);
-                        pat += (size_t)o.m * ((size_t)o.cL + 1);
-                        nKeep += sz;
+                        pat += o.slice();
+                        nKeep += o.block();
                     }
-                    onlyEnumerated = onlyEnumerated && o.tier == 0;
+                    onlyEnumerated = onlyEnumerated && p.tier == 0;
                 }
                 if (k >= 1 && nKeep > 0) {
                     if (onlyEnumerated) {
-                        HIP_TRY(ctx, hipMemcpy(sub.data() + at, dSub.as<double>() + costOff[b], n * 8, hipMemcpyDeviceToHost));
+                        HIP_TRY(ctx, hipMemcpy(sub.data() + at, pr.d_sub() + costOff[b], n * 8, hipMemcpyDeviceToHost));
                     } else {  // the enumerated clusters of a frame that has exactly answered ones too: one by one
                         for (size_t t = i; t < e; t++) {
-                            const Open &o = open[t];
-                            if (o.tier != 0) continue;
-                            HIP_TRY(ctx, hipMemcpy(sub.data() + sCo[o.at], dSub.as<double>() + costOff[b] + o.from,
-                                                   (size_t)(o.cL + o.m) * o.m * 8, hipMemcpyDeviceToHost));
+                            if (place[t].tier != 0) continue;
+                            HIP_TRY(ctx, hipMemcpy(sub.data() + sCo[place[t].at], pr.d_sub() + costOff[b] + open[t].from,
+                                                   open[t].block() * 8, hipMemcpyDeviceToHost));
                         }
                     }
                 }
@@ -4418,17 +4526,15 @@ static int hybrid_impl(kbest_ctx *ctx, const char *who, int B, const int32_t *nL
             }
             if (!bM.empty()) {  // the big clusters of all frames: from the sub-blocks where they lie
                 const int nb = (int)bM.size();
-                rc = big_reserve(ctx, bigLayers < ctx->bigWorkCap ? bigLayers : ctx->bigWorkCap, bigM, bigRows);
-                if (rc != KBEST_OK) return rc;
+                KB_TRY(big_reserve(ctx, bigLayers < ctx->bigWorkCap ? bigLayers : ctx->bigWorkCap, bigM, bigRows));
                 DevBuf dBigP, dBigOut;  // out: logZ[nb] (double) | info[nb] (int32)
                 hipError_t e;
                 if ((e = dBigP.alloc(ctx, bpat * 8)) != hipSuccess || (e = dBigOut.alloc(ctx, (size_t)nb * 12)) != hipSuccess)
                     return fail(ctx, KBEST_ERR_NOMEM, (std::string(who) + ": device buffers").c_str(), e);
                 unsigned char *b8 = dBigOut.as<unsigned char>();
-                rc = kbest_bigcluster_probs_f64_dev(ctx, nb, bM.data(), bL.data(), bSo.data(), bPo.data(), dSub.as<double>(),
-                                                    dBigP.as<double>(), reinterpret_cast<double *>(b8),
-                                                    reinterpret_cast<int32_t *>(b8 + (size_t)nb * 8), nullptr);
-                if (rc != KBEST_OK) return rc;
+                KB_TRY(kbest_bigcluster_probs_f64_dev(ctx, nb, bM.data(), bL.data(), bSo.data(), bPo.data(), pr.d_sub(),
+                                                      dBigP.as<double>(), reinterpret_cast<double *>(b8),
+                                                      reinterpret_cast<int32_t *>(b8 + (size_t)nb * 8), nullptr));
                 HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
                 bigP.resize(bpat);
                 bigLogZ.resize(nb);
@@ -4439,50 +4545,48 @@ static int hybrid_impl(kbest_ctx *ctx, const char *who, int B, const int32_t *nL
             }
         }
         fb.release();  // with the buffers above: the enumeration below draws from the same cache
+        pr.release();
     }
-    const int32_t *hInfo = hInt.data(), *hOpen = hInt.data() + 2 * (size_t)B;
-    for (int b = 0; b < B; b++) method[b] = hInfo[b] < 0 ? -1 : hInfo[b] == 0 ? -2 : 0;
-    if (nBig)
-        for (int b = 0; b < B; b++) nBig[b] = 0;
-    if (nFrontier)
-        for (int b = 0; b < B; b++) nFrontier[b] = 0;
+    const int32_t *hOpen = pr.nOpen();
+    for (int b = 0; b < B; b++) method[b] = method_of_info(pr.info()[b]);
+    if (nBig) std::fill(nBig, nBig + B, 0);
+    if (nFrontier) std::fill(nFrontier, nFrontier + B, 0);
     if (!open.empty()) {
         const int S = (int)sCo.size();
         std::vector<int32_t> sL(S), sM(S), sNf(S, 0);
         size_t pn = 0;
-        for (const Open &o : open)
-            if (o.tier == 0) {
-                sL[o.at] = o.cL;
-                sM[o.at] = o.m;
-                pn += (size_t)o.m * ((size_t)o.cL + 1);
+        for (size_t i = 0; i < open.size(); i++)
+            if (place[i].tier == 0) {
+                sL[place[i].at] = open[i].cL;
+                sM[place[i].at] = open[i].m;
+                pn += open[i].slice();
             }
         std::vector<double> sp(pn, 0.0);
         if (S > 0 && k >= 1) {
-            rc = weights_entry(ctx, S, sL.data(), sM.data(), sub.data(), sCo.data(), k, sp.data(), sPo.data(), sNf.data(), false, nullptr, false);
-            if (rc != KBEST_OK) return rc;
+            KB_TRY(weights_entry(ctx, S, sL.data(), sM.data(), sub.data(), sCo.data(), k, sp.data(), sPo.data(), sNf.data(), false, nullptr, false));
         }
         std::vector<char> refused(B, 0);
-        for (const Open &o : open) {  // slot nL_k -> slot nL, landmark rows through the row list, columns through the labels
-            const int b = o.b;
+        for (size_t i = 0; i < open.size(); i++) {  // slot nL_k -> slot nL, landmark rows through the row list, columns through the labels
+            const OpenCluster &o = open[i];
+            const int b = o.b, tier = place[i].tier, at = place[i].at;
             const double *q;
-            if (o.tier == 2) {
-                if (frInfo[o.at] <= 0) method[b] = -2;
+            if (tier == 2) {
+                if (fr.info[at] <= 0) method[b] = -2;
                 else if (nFrontier) nFrontier[b]++;
-                q = frP.data() + fPo[o.at];
-            } else if (o.tier == 1) {
-                if (bigInfo[o.at] <= 0) method[b] = -2;
+                q = frP.data() + fPo[at];
+            } else if (tier == 1) {
+                if (bigInfo[at] <= 0) method[b] = -2;
                 else if (nBig) nBig[b]++;
-                q = bigP.data() + bPo[o.at];
+                q = bigP.data() + bPo[at];
             } else if (k < 1) {  // (kbest_hybrid_exact_probs_batch_f64 with k = 0: nothing enumerates it)
                 refused[b] = 1;
                 continue;
             } else {
-                if (sNf[o.at] <= 0) method[b] = -2;
-                else if (method[b] >= 0) method[b] = (sNf[o.at] >= k || method[b] == 2) ? 2 : 1;
-                q = sp.data() + sPo[o.at];
+                enumerated_cluster_rule(method[b], sNf[at], k);
+                q = sp.data() + sPo[at];
             }
             double *fp = hp.data() + probOff[b];
-            const int32_t *lab = hLabel.data() + (size_t)b * maxCol, *rows = hRows.data() + o.rowAt;
+            const int32_t *lab = pr.labels(b), *rows = pr.rows(o);
             int j = 0;
             for (int c = 0; c < nM[b] && j < o.m; c++) {
                 if (lab[c] != o.root) continue;
@@ -4502,28 +4606,20 @@ static int hybrid_impl(kbest_ctx *ctx, const char *who, int B, const int32_t *nL
         }
     }
     if (logPerm) {
-        // the partial kernel's sum over the clusters it answered, then the big clusters in label order; their log Z_k are in the
-        // units a = exp(-x): m_k times the frame's block minimum (0 after conditionCosts) brings them to the frame's a = exp(min - x)
-        for (int b = 0; b < B; b++) logPerm[b] = hLp[b];
-        for (const Open &o : open) {
-            if (o.tier == 0 || method[o.b] < 0) continue;
-            double mn = 0.0;
-            if (!condition) {
-                const double *x = cost + costOff[o.b];
-                const size_t cnt = ((size_t)nL[o.b] + nM[o.b]) * (size_t)nM[o.b];
-                mn = x[0];
-                for (size_t i = 1; i < cnt; i++) mn = x[i] < mn ? x[i] : mn;
-            }
-            logPerm[o.b] = logPerm[o.b] + ((o.tier == 2 ? frLogZ[o.at] : bigLogZ[o.at]) + (double)o.m * mn);
+        // the partial kernel's sum over the clusters it answered, then the exactly answered open clusters in label order, each
+        // brought to the frame's units (FrameBatch::block_min)
+        for (int b = 0; b < B; b++) logPerm[b] = pr.hLp[b];
+        for (size_t i = 0; i < open.size(); i++) {
+            const OpenCluster &o = open[i];
+            if (place[i].tier == 0 || method[o.b] < 0) continue;
+            const double mn = fb.block_min(cost, o.b, condition);
+            logPerm[o.b] = logPerm[o.b] + ((place[i].tier == 2 ? fr.logZ[place[i].at] : bigLogZ[place[i].at]) + (double)o.m * mn);
         }
-        for (int b = 0; b < B; b++) {
-            if (method[b] == -2) logPerm[b] = -std::numeric_limits<double>::infinity();
-            if (method[b] == -1) logPerm[b] = std::numeric_limits<double>::quiet_NaN();
-        }
+        for (int b = 0; b < B; b++) logPerm[b] = final_log_perm(method[b], logPerm[b]);
     }
     fb.scatter(hp, probs);
     if (nOpen) memcpy(nOpen, hOpen, (size_t)B * 4);
-    if (maxCluster) memcpy(maxCluster, hInt.data() + B, (size_t)B * 4);
+    if (maxCluster) memcpy(maxCluster, pr.maxCluster(), (size_t)B * 4);
     return KBEST_OK;
 }
 
@@ -4627,143 +4723,101 @@ static int hybrid_sample_impl(kbest_ctx *ctx, const char *who, int B, const int3
         }
     }
     FrameBatch fb;
-    int rc = fb.scan(ctx, who, B, nL, nM, costOff, pOff.data());
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(fb.scan(ctx, who, B, nL, nM, costOff, pOff.data()));
     const int maxRawRow = fb.maxRawRow, maxCol = fb.maxCol;
-    rc = check_frame_shape(ctx, who, B, maxRawRow, maxCol, KBEST_CLUSTER_MAX_COLS, CLUSTER_COLS_TEXT);
-    if (rc != KBEST_OK) return rc;
-    size_t asgN = 0, lpN = 0;  // int32s / doubles up to the end of the last frame's draws
-    for (int b = 0; b < B; b++) {
-        if (asgOff[b] < 0 || lpOff[b] < 0) return fail(ctx, KBEST_ERR_BAD_ARG, (std::string(who) + ": a negative offset").c_str());
-        asgN = std::max(asgN, (size_t)asgOff[b] + (size_t)nSample * (size_t)nM[b]);
-        lpN = std::max(lpN, (size_t)lpOff[b] + (size_t)nSample);
-    }
+    KB_TRY(check_frame_shape(ctx, who, B, maxRawRow, maxCol, KBEST_CLUSTER_MAX_COLS, CLUSTER_COLS_TEXT));
+    DrawBatch db;
+    KB_TRY(db.scan(ctx, who, B, nM, nSample, asgOff, lpOff));
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    rc = kbest_reserve_clustered(ctx, B, maxRawRow, maxCol);
-    if (rc != KBEST_OK) return rc;
-    const size_t descStride = (size_t)maxCol, rowStride = (size_t)maxRawRow;
-    // out: info[B] | maxCluster[B] | nOpen[B] (int32), the partial kernel's;  sOut: logPerm[B] (double) | info[B] (int32), the
-    // sampler's;  off: asgOff[B] | lpOff[B] | frameKey[B]
-    DevBuf dOut, dLabel, dDesc, dRows, dSub, dLp, dSOut, dAsg, dLpS, dOff;
-    rc = fb.upload(ctx, who, cost, {{&dOut, (size_t)B * 12}, {&dLabel, (size_t)B * maxCol * 4}, {&dDesc, (size_t)B * descStride * 16},
-                                    {&dRows, (size_t)B * rowStride * 4}, {&dSub, fb.costN * 8}, {&dLp, (size_t)B * 8},
-                                    {&dSOut, (size_t)B * 12}, {&dAsg, asgN * 4}, {&dLpS, lpN * 8}, {&dOff, (size_t)B * 24}});
-    if (rc != KBEST_OK) return rc;
-    HIP_TRY(ctx, hipMemcpy(dOff.p, asgOff, (size_t)B * 8, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(dOff.as<int64_t>() + B, lpOff, (size_t)B * 8, hipMemcpyHostToDevice));
-    if (frameKey) HIP_TRY(ctx, hipMemcpy(dOff.as<int64_t>() + 2 * (size_t)B, frameKey, (size_t)B * 8, hipMemcpyHostToDevice));
-    int32_t *o4 = dOut.as<int32_t>();
-    rc = kbest_clustered_partial_batch_f64_dev(ctx, B, maxRawRow, maxCol, fb.d_nL(), fb.d_nM(), fb.d_cost(), fb.d_costOff(), condition,
-                                               maxExact, fb.d_probs(), fb.d_probOff(), dLp.as<double>(), o4, o4 + B, dLabel.as<int32_t>(),
-                                               maxCol, o4 + 2 * (size_t)B, dDesc.as<int32_t>(), (int)descStride, dRows.as<int32_t>(),
-                                               (int)rowStride, dSub.as<double>(), nullptr);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(kbest_reserve_clustered(ctx, B, maxRawRow, maxCol));
+    PartialRun pr;
+    DevBuf dSOut;  // sOut: logPerm[B] (double) | info[B] (int32), the sampler's
+    KB_TRY(pr.upload(ctx, who, fb, cost, true, {{&dSOut, (size_t)B * 12}, db.asg(), db.lp(), db.off()}));
+    KB_TRY(db.upload(ctx, frameKey));
+    KB_TRY(pr.launch(ctx, fb, condition, maxExact));
     unsigned char *s8 = dSOut.as<unsigned char>();
-    rc = cluster_sample_dev(ctx, maxExact ? maxExact : KBEST_CLUSTER_MAX_SIZE, B, maxRawRow, maxCol, fb.d_nL(), fb.d_nM(), fb.d_cost(), fb.d_costOff(), condition, nSample, seed,
-                            sampleBase, frameKey ? dOff.as<uint64_t>() + 2 * (size_t)B : nullptr, dAsg.as<int32_t>(), dOff.as<int64_t>(),
-                            dLpS.as<double>(), dOff.as<int64_t>() + B, reinterpret_cast<double *>(s8),
-                            reinterpret_cast<int32_t *>(s8 + (size_t)B * 8), nullptr, nullptr);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(cluster_sample_dev(ctx, maxExact ? maxExact : KBEST_CLUSTER_MAX_SIZE, B, maxRawRow, maxCol, fb.d_nL(), fb.d_nM(), fb.d_cost(),
+                              fb.d_costOff(), condition, nSample, seed, sampleBase, db.d_frameKey(), db.d_assign(), db.d_asgOff(),
+                              db.d_logProb(), db.d_lpOff(), reinterpret_cast<double *>(s8), reinterpret_cast<int32_t *>(s8 + (size_t)B * 8),
+                              nullptr, nullptr));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<int32_t> hInt((size_t)B * 3), hDesc, hRows, hLabel;  // info | maxCluster | nOpen
-    std::vector<double> hLp(B), sLp(B);
-    HIP_TRY(ctx, hipMemcpy(hInt.data(), dOut.p, (size_t)B * 12, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(hLp.data(), dLp.p, (size_t)B * 8, hipMemcpyDeviceToHost));
+    std::vector<double> sLp(B);
     HIP_TRY(ctx, hipMemcpy(sLp.data(), s8, (size_t)B * 8, hipMemcpyDeviceToHost));
-    const int32_t *hInfo = hInt.data(), *hOpen = hInt.data() + 2 * (size_t)B;
-    // every open cluster, in frame and label order; at: its place in the frontier sampler's call (at most 64 measurements), taken:
-    // answered there; en: its place in the enumeration (k >= 1: whatever that sampler leaves); keyAt: its row keys in rowKey
-    struct Open { int b, root, m, cL, R; size_t rowAt, from; int at; bool taken; int en; int64_t keyAt; };
-    std::vector<Open> open;
-    bool any = false;
-    for (int b = 0; b < B; b++) any = any || hOpen[b] > 0;
-    std::vector<int32_t> fM, fL, rowKey, fInfo, fWidth, hLocal;
+    KB_TRY(pr.download(ctx));
+    const std::vector<OpenCluster> &open = pr.open;
+    const int32_t *hInfo = pr.info(), *hOpen = pr.nOpen();
+    // beside open -- at: its place in the frontier sampler's call (at most 64 measurements), taken: answered there; en: its place
+    // in the enumeration (k >= 1: whatever that sampler leaves); keyAt: its row keys in rowKey
+    struct Place { int at = -1; bool taken = false; int en = -1; int64_t keyAt = -1; };
+    std::vector<Place> place(open.size());
+    std::vector<int32_t> fM, fL, rowKey, hLocal;
     std::vector<int64_t> fSo, fKo, fAo, fLo;
     std::vector<uint64_t> fKey;
-    std::vector<double> fLogZ, hTerm;
+    FrontierOut fr;
+    std::vector<double> hTerm;
     std::vector<int32_t> eNf, eInfo, eLocal;  // the enumerated clusters: the counts of their tables, the table sampler's info and rows
     std::vector<int64_t> eAo;                 // ... and where the rows of each lie
     std::vector<double> eTerm;
-    if (any) {
-        hDesc.resize((size_t)B * descStride * 4);
-        hRows.resize((size_t)B * rowStride);
-        hLabel.resize((size_t)B * maxCol);
-        HIP_TRY(ctx, hipMemcpy(hDesc.data(), dDesc.p, hDesc.size() * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(hRows.data(), dRows.p, hRows.size() * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(hLabel.data(), dLabel.p, hLabel.size() * 4, hipMemcpyDeviceToHost));
+    if (!open.empty()) {
         size_t asgAt = 0;
         int frM = 1, frRows = 1;
         FrameGate gate;
-        for (int b = 0; b < B; b++) {
-            size_t n = 0, rowAt = (size_t)b * rowStride;
-            if (hOpen[b] > 0) gate.make(cost + costOff[b], nL[b], nM[b], condition != 0);
-            for (int j = 0; j < hOpen[b]; j++) {
-                const int32_t *d = hDesc.data() + ((size_t)b * descStride + j) * 4;
-                Open o{b, d[0], d[1], d[2], d[3], rowAt, n, -1, false, -1, -1};
-                n += (size_t)(o.cL + o.m) * o.m;
-                rowAt += (size_t)o.cL;
-                const bool toFrontier = o.m <= KBEST_FRONTIER_MAX_COLS;
-                if (toFrontier || k >= 1) {
-                    // q of every row of the sub-block: the RAW row of the caller's block (the all-+inf rows behind them are no steps)
-                    o.keyAt = (int64_t)rowKey.size();
-                    if (toFrontier) {
-                        o.at = (int)fM.size();
-                        fM.push_back(o.m);
-                        fL.push_back(o.cL);
-                        fSo.push_back(costOff[b] + (int64_t)o.from);
-                        fKo.push_back(o.keyAt);
-                        fAo.push_back((int64_t)asgAt);
-                        fLo.push_back((int64_t)o.at * nSample);
-                        fKey.push_back(frameKey ? frameKey[b] : (uint64_t)b);
-                        asgAt += (size_t)nSample * o.m;
-                    }
-                    for (int r = 0; r < o.cL; r++) rowKey.push_back(hRows[o.rowAt + r]);
-                    int found = 0;
-                    const int32_t *lab = hLabel.data() + (size_t)b * maxCol;
-                    for (int r = nL[b]; r < nL[b] + nM[b]; r++) {
-                        bool in = false;
-                        for (int c = 0; c < nM[b] && !in; c++) in = lab[c] == o.root && gate.nonzero(c, r);
-                        if (in && found < o.m) rowKey.push_back(r);
-                        found += in ? 1 : 0;
-                    }
-                    if (found != o.R - o.cL) return fail(ctx, KBEST_ERR_INTERNAL, (std::string(who) + ": the rows of an open cluster").c_str());
-                    for (int r = o.R; r < o.cL + o.m; r++) rowKey.push_back(0);
-                    if (toFrontier && o.m > frM) frM = o.m;
-                    if (toFrontier && o.cL + o.m > frRows) frRows = o.cL + o.m;
-                }
-                open.push_back(o);
+        for (size_t i = 0; i < open.size(); i++) {
+            const OpenCluster &o = open[i];
+            Place &p = place[i];
+            const int b = o.b;
+            if (i == 0 || open[i - 1].b != b) gate.make(cost + costOff[b], nL[b], nM[b], condition != 0);
+            const bool toFrontier = o.m <= KBEST_FRONTIER_MAX_COLS;
+            if (!toFrontier && k < 1) continue;
+            // q of every row of the sub-block: the RAW row of the caller's block (the all-+inf rows behind them are no steps)
+            p.keyAt = (int64_t)rowKey.size();
+            if (toFrontier) {
+                p.at = (int)fM.size();
+                fM.push_back(o.m);
+                fL.push_back(o.cL);
+                fSo.push_back(costOff[b] + (int64_t)o.from);
+                fKo.push_back(p.keyAt);
+                fAo.push_back((int64_t)asgAt);
+                fLo.push_back((int64_t)p.at * nSample);
+                fKey.push_back(frameKey ? frameKey[b] : (uint64_t)b);
+                asgAt += (size_t)nSample * o.m;
             }
+            for (int r = 0; r < o.cL; r++) rowKey.push_back(pr.rows(o)[r]);
+            int found = 0;
+            const int32_t *lab = pr.labels(b);
+            for (int r = nL[b]; r < nL[b] + nM[b]; r++) {
+                bool in = false;
+                for (int c = 0; c < nM[b] && !in; c++) in = lab[c] == o.root && gate.nonzero(c, r);
+                if (in && found < o.m) rowKey.push_back(r);
+                found += in ? 1 : 0;
+            }
+            if (found != o.R - o.cL) return fail(ctx, KBEST_ERR_INTERNAL, (std::string(who) + ": the rows of an open cluster").c_str());
+            for (int r = o.R; r < o.cL + o.m; r++) rowKey.push_back(0);
+            if (toFrontier && o.m > frM) frM = o.m;
+            if (toFrontier && o.cL + o.m > frRows) frRows = o.cL + o.m;
         }
         if (!fM.empty() && maxWidth > 0) {
             const int nf = (int)fM.size();
-            rc = kbest_reserve_frontier_sample(ctx, nf, frM, frRows);
-            if (rc != KBEST_OK) return rc;
-            DevBuf dKey, dLocal, dTerm, dFrOut;  // frOut: logZ[nf] (double) | info[nf] | width[nf] (int32)
+            KB_TRY(kbest_reserve_frontier_sample(ctx, nf, frM, frRows));
+            DevBuf dKey, dLocal, dTerm;
             hipError_t e;
             if ((e = dKey.alloc(ctx, rowKey.size() * 4)) != hipSuccess || (e = dLocal.alloc(ctx, asgAt * 4)) != hipSuccess ||
-                (e = dTerm.alloc(ctx, (size_t)nf * nSample * 8)) != hipSuccess || (e = dFrOut.alloc(ctx, (size_t)nf * 16)) != hipSuccess)
+                (e = dTerm.alloc(ctx, (size_t)nf * nSample * 8)) != hipSuccess || (e = fr.alloc(ctx, nf)) != hipSuccess)
                 return fail(ctx, KBEST_ERR_NOMEM, (std::string(who) + ": device buffers").c_str(), e);
             HIP_TRY(ctx, hipMemcpy(dKey.p, rowKey.data(), rowKey.size() * 4, hipMemcpyHostToDevice));
-            unsigned char *f8 = dFrOut.as<unsigned char>();
-            int32_t *f4 = reinterpret_cast<int32_t *>(f8 + (size_t)nf * 8);
-            rc = kbest_frontier_sample_f64_dev(ctx, nf, fM.data(), fL.data(), fSo.data(), dSub.as<double>(), dKey.as<int32_t>(), fKo.data(),
-                                               fKey.data(), nSample, seed, sampleBase, dLocal.as<int32_t>(), fAo.data(), dTerm.as<double>(),
-                                               fLo.data(), reinterpret_cast<double *>(f8), f4, f4 + nf, nullptr);
-            if (rc != KBEST_OK) return rc;
+            KB_TRY(kbest_frontier_sample_f64_dev(ctx, nf, fM.data(), fL.data(), fSo.data(), pr.d_sub(), dKey.as<int32_t>(), fKo.data(),
+                                                 fKey.data(), nSample, seed, sampleBase, dLocal.as<int32_t>(), fAo.data(), dTerm.as<double>(),
+                                                 fLo.data(), fr.d_logZ(), fr.d_info(), fr.d_width(), nullptr));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            fLogZ.resize(nf);
-            fInfo.resize(nf);
-            fWidth.resize(nf);
+            KB_TRY(fr.download(ctx));
             hLocal.resize(asgAt);
             hTerm.resize((size_t)nf * nSample);
-            HIP_TRY(ctx, hipMemcpy(fLogZ.data(), f8, (size_t)nf * 8, hipMemcpyDeviceToHost));
-            HIP_TRY(ctx, hipMemcpy(fInfo.data(), f4, (size_t)nf * 4, hipMemcpyDeviceToHost));
-            HIP_TRY(ctx, hipMemcpy(fWidth.data(), f4 + nf, (size_t)nf * 4, hipMemcpyDeviceToHost));
             HIP_TRY(ctx, hipMemcpy(hLocal.data(), dLocal.p, asgAt * 4, hipMemcpyDeviceToHost));
             HIP_TRY(ctx, hipMemcpy(hTerm.data(), dTerm.p, hTerm.size() * 8, hipMemcpyDeviceToHost));
-            for (Open &o : open)
-                if (o.at >= 0 && fInfo[o.at] >= 0 && fWidth[o.at] <= maxWidth) o.taken = true;
+            for (Place &p : place)
+                if (p.at >= 0 && fr.took(p.at, maxWidth)) p.taken = true;
+            fr.d.release();  // (back to the cache with the three above: the enumeration draws next)
         }
         if (k >= 1) {
             // the k-best leg: every open cluster nobody took, of the frames the partial kernel answered -- the sub-blocks come to the
@@ -4783,21 +4837,21 @@ static int hybrid_sample_impl(kbest_ctx *ctx, const char *who, int B, const int3
                 size_t n = 0;
                 bool need = false;
                 for (size_t t = i; t < e; t++) {
-                    n += (size_t)(open[t].cL + open[t].m) * open[t].m;
-                    need = need || !open[t].taken;
+                    n += open[t].block();
+                    need = need || !place[t].taken;
                 }
                 if (need && hInfo[b] > 0) {
                     const size_t base = sub.size();
                     sub.resize(base + n);
-                    HIP_TRY(ctx, hipMemcpy(sub.data() + base, dSub.as<double>() + costOff[b], n * 8, hipMemcpyDeviceToHost));
+                    HIP_TRY(ctx, hipMemcpy(sub.data() + base, pr.d_sub() + costOff[b], n * 8, hipMemcpyDeviceToHost));
                     for (size_t t = i; t < e; t++) {
-                        Open &o = open[t];
-                        if (o.taken) continue;
-                        o.en = (int)eRow.size();
+                        const OpenCluster &o = open[t];
+                        if (place[t].taken) continue;
+                        place[t].en = (int)eRow.size();
                         eRow.push_back(o.cL + o.m);
                         eCol.push_back(o.m);
                         eCo.push_back((int64_t)(base + o.from));
-                        eLo.push_back((int64_t)o.en * nSample);
+                        eLo.push_back((int64_t)place[t].en * nSample);
                         eKeyC.push_back((uint32_t)o.root);
                         eKeyF.push_back(frameKey ? frameKey[b] : (uint64_t)b);
                         eAo.push_back((int64_t)eAsg);
@@ -4818,9 +4872,8 @@ static int hybrid_sample_impl(kbest_ctx *ctx, const char *who, int B, const int3
                 op.use_cutoff = 1;  // assignment.cpp:594: kBest2DCutoff(..., cutoff = 42)
                 op.cutoff = 42.0;
                 op.flags |= KBEST_FLAG_CANONICAL_TIES;
-                rc = kbest_batch_f64(ctx, &op, E, eMaxRow, eMaxCol, eRow.data(), eCol.data(), sub.data(), eCo.data(), k, r4c.data(), nullptr,
-                                     gain.data(), eNf.data(), nullptr);
-                if (rc != KBEST_OK) return rc;
+                KB_TRY(kbest_batch_f64(ctx, &op, E, eMaxRow, eMaxCol, eRow.data(), eCol.data(), sub.data(), eCo.data(), k, r4c.data(), nullptr,
+                                       gain.data(), eNf.data(), nullptr));
                 DevBuf dTab, dGain, dNf, dELocal, dETerm, dEInfo;
                 hipError_t e;
                 if ((e = dTab.alloc(ctx, r4c.size() * 4)) != hipSuccess || (e = dGain.alloc(ctx, gain.size() * 8)) != hipSuccess ||
@@ -4830,10 +4883,9 @@ static int hybrid_sample_impl(kbest_ctx *ctx, const char *who, int B, const int3
                 HIP_TRY(ctx, hipMemcpy(dTab.p, r4c.data(), r4c.size() * 4, hipMemcpyHostToDevice));
                 HIP_TRY(ctx, hipMemcpy(dGain.p, gain.data(), gain.size() * 8, hipMemcpyHostToDevice));
                 HIP_TRY(ctx, hipMemcpy(dNf.p, eNf.data(), (size_t)E * 4, hipMemcpyHostToDevice));
-                rc = kbest_table_sample_f64_dev(ctx, E, k, eMaxCol, eCol.data(), dTab.as<int32_t>(), dGain.as<double>(), dNf.as<int32_t>(), 42.0,
-                                                eKeyC.data(), eKeyF.data(), nSample, seed, sampleBase, dELocal.as<int32_t>(), eAo.data(),
-                                                dETerm.as<double>(), eLo.data(), nullptr, dEInfo.as<int32_t>(), nullptr);
-                if (rc != KBEST_OK) return rc;
+                KB_TRY(kbest_table_sample_f64_dev(ctx, E, k, eMaxCol, eCol.data(), dTab.as<int32_t>(), dGain.as<double>(), dNf.as<int32_t>(), 42.0,
+                                                  eKeyC.data(), eKeyF.data(), nSample, seed, sampleBase, dELocal.as<int32_t>(), eAo.data(),
+                                                  dETerm.as<double>(), eLo.data(), nullptr, dEInfo.as<int32_t>(), nullptr));
                 HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
                 eLocal.resize(eAsg);
                 eTerm.resize((size_t)E * nSample);
@@ -4844,25 +4896,24 @@ static int hybrid_sample_impl(kbest_ctx *ctx, const char *who, int B, const int3
             }
         }
     }
-    std::vector<int32_t> hAsg(asgN);
-    std::vector<double> hLpS(lpN);
-    HIP_TRY(ctx, hipMemcpy(hAsg.data(), dAsg.p, asgN * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(hLpS.data(), dLpS.p, lpN * 8, hipMemcpyDeviceToHost));
-    // method, nFrontier: as kbest_hybrid_frontier_probs_batch_f64(k = 0, maxBig = 0) decides them
-    for (int b = 0; b < B; b++) method[b] = hInfo[b] < 0 ? -1 : hInfo[b] == 0 ? -2 : 0;
-    // (k >= 1: an enumerated cluster decides as in kbest_hybrid_frontier_probs_batch_f64(k, maxBig = 0) -- 1: complete within the
-    //  cutoff, 2: cut at k, -2: no feasible assignment; a cluster left alone belongs to a frame that is -1 or -2 already)
+    KB_TRY(db.download(ctx));
+    std::vector<int32_t> &hAsg = db.hAsg;  // (edited below, before they go out)
+    std::vector<double> &hLpS = db.hLp;
+    // method, nFrontier: hybrid_impl's (maxBig = 0), through the same rules; an enumerated cluster whose table the sampler refuses
+    // counts as one without a feasible assignment, and a cluster left alone belongs to a frame that is -1 or -2 already
+    for (int b = 0; b < B; b++) method[b] = method_of_info(hInfo[b]);
     std::vector<int32_t> nFr(B, 0), nEn(B, 0);
     std::vector<char> refused(B, 0);
-    for (const Open &o : open) {
-        if (o.taken) {
-            if (fInfo[o.at] <= 0) method[o.b] = -2;
+    for (size_t i = 0; i < open.size(); i++) {
+        const OpenCluster &o = open[i];
+        const Place &p = place[i];
+        if (p.taken) {
+            if (fr.info[p.at] <= 0) method[o.b] = -2;
             else nFr[o.b]++;
         } else if (k < 1) {
             refused[o.b] = 1;
-        } else if (o.en >= 0) {
-            if (eNf[o.en] <= 0 || eInfo[o.en] <= 0) method[o.b] = -2;
-            else if (method[o.b] >= 0) method[o.b] = (eNf[o.en] >= k || method[o.b] == 2) ? 2 : 1;
+        } else if (p.en >= 0) {
+            enumerated_cluster_rule(method[o.b], eInfo[p.en] <= 0 ? 0 : eNf[p.en], k);
             nEn[o.b]++;
         }
     }
@@ -4874,12 +4925,14 @@ static int hybrid_sample_impl(kbest_ctx *ctx, const char *who, int B, const int3
     // the draws: the small clusters' columns and terms are the sampler's; the open clusters' follow, in label order, whichever
     // tier answered
     const double QNAN = std::numeric_limits<double>::quiet_NaN();
-    for (const Open &o : open) {
+    for (size_t i = 0; i < open.size(); i++) {
+        const OpenCluster &o = open[i];
+        const Place &p = place[i];
         if (method[o.b] < 0) continue;
         const int b = o.b, M = nM[b];
-        const int32_t *lab = hLabel.data() + (size_t)b * maxCol, *keys = rowKey.data() + o.keyAt;
-        const int32_t *loc = o.taken ? hLocal.data() + fAo[o.at] : eLocal.data() + eAo[o.en];
-        const double *term = o.taken ? hTerm.data() + fLo[o.at] : eTerm.data() + (size_t)o.en * nSample;
+        const int32_t *lab = pr.labels(b), *keys = rowKey.data() + p.keyAt;
+        const int32_t *loc = p.taken ? hLocal.data() + fAo[p.at] : eLocal.data() + eAo[p.en];
+        const double *term = p.taken ? hTerm.data() + fLo[p.at] : eTerm.data() + (size_t)p.en * nSample;
         int32_t *fa = hAsg.data() + asgOff[b];
         double *fl = hLpS.data() + lpOff[b];
         std::vector<int> cols;
@@ -4898,38 +4951,29 @@ static int hybrid_sample_impl(kbest_ctx *ctx, const char *who, int B, const int3
             std::fill(hAsg.begin() + asgOff[b], hAsg.begin() + asgOff[b] + (size_t)nSample * (size_t)nM[b], -1);
             std::fill(hLpS.begin() + lpOff[b], hLpS.begin() + lpOff[b] + (size_t)nSample, QNAN);
         }
-        memcpy(assign + asgOff[b], hAsg.data() + asgOff[b], (size_t)nSample * (size_t)nM[b] * 4);
-        memcpy(logProb + lpOff[b], hLpS.data() + lpOff[b], (size_t)nSample * 8);
     }
+    db.scatter(assign, logProb);
     if (logPerm) {
         // a frame without an open cluster: the sampler's own sum.  Else the partial kernel's sum over the clusters it answered, then
-        // the open clusters in label order, as kbest_hybrid_frontier_probs_batch_f64 adds them
-        for (int b = 0; b < B; b++) logPerm[b] = hOpen[b] > 0 ? hLp[b] : sLp[b];
+        // the open clusters the frontier sampler answered in label order, as hybrid_impl adds them
+        for (int b = 0; b < B; b++) logPerm[b] = hOpen[b] > 0 ? pr.hLp[b] : sLp[b];
         int lastB = -1;
         double mn = 0.0;
-        for (const Open &o : open) {
-            if (!o.taken || method[o.b] < 0) continue;
+        for (size_t i = 0; i < open.size(); i++) {
+            const OpenCluster &o = open[i];
+            if (!place[i].taken || method[o.b] < 0) continue;
             if (o.b != lastB) {
                 lastB = o.b;
-                mn = 0.0;
-                if (!condition) {
-                    const double *x = cost + costOff[o.b];
-                    const size_t cnt = ((size_t)nL[o.b] + nM[o.b]) * (size_t)nM[o.b];
-                    mn = x[0];
-                    for (size_t i = 1; i < cnt; i++) mn = x[i] < mn ? x[i] : mn;
-                }
+                mn = fb.block_min(cost, o.b, condition);
             }
-            logPerm[o.b] = logPerm[o.b] + (fLogZ[o.at] + (double)o.m * mn);
+            logPerm[o.b] = logPerm[o.b] + (fr.logZ[place[i].at] + (double)o.m * mn);
         }
-        for (int b = 0; b < B; b++) {
-            if (method[b] == -2) logPerm[b] = -std::numeric_limits<double>::infinity();
-            if (method[b] == -1) logPerm[b] = QNAN;
-        }
+        for (int b = 0; b < B; b++) logPerm[b] = final_log_perm(method[b], logPerm[b]);
     }
     if (nOpen) memcpy(nOpen, hOpen, (size_t)B * 4);
     if (nFrontier) memcpy(nFrontier, nFr.data(), (size_t)B * 4);
     if (nEnum) memcpy(nEnum, nEn.data(), (size_t)B * 4);
-    if (maxCluster) memcpy(maxCluster, hInt.data() + B, (size_t)B * 4);
+    if (maxCluster) memcpy(maxCluster, pr.maxCluster(), (size_t)B * 4);
     return KBEST_OK;
 }
 
@@ -5000,8 +5044,7 @@ int kbest_reserve_hybrid_sample_dev(kbest_ctx *ctx, int B, int maxRawRow, int ma
 {
     if (!ctx) return KBEST_ERR_BAD_ARG;
     const char *who = "kbest_reserve_hybrid_sample_dev";
-    int rc = check_frame_shape(ctx, who, B, maxRawRow, maxCol, KBEST_CLUSTER_MAX_COLS, CLUSTER_COLS_TEXT);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(check_frame_shape(ctx, who, B, maxRawRow, maxCol, KBEST_CLUSTER_MAX_COLS, CLUSTER_COLS_TEXT));
     if (nSample < 1) return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_reserve_hybrid_sample_dev: bad argument (nSample >= 1)");
     if (B == 0) return KBEST_OK;
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
@@ -5010,10 +5053,8 @@ int kbest_reserve_hybrid_sample_dev(kbest_ctx *ctx, int B, int maxRawRow, int ma
     maxRawRow = std::max(ctx->hybSampRow, maxRawRow);
     maxCol = std::max(ctx->hybSampCol, maxCol);
     nSample = std::max(ctx->hybSampN, nSample);
-    rc = kbest_reserve_hybrid_dev(ctx, B, maxRawRow, maxCol);  // (with it kbest_reserve_clustered: the clustered sampler's too)
-    if (rc != KBEST_OK) return rc;
-    rc = raw_reserve(ctx, ctx->hybSampBuf, hybrid_sample_layout(B, maxRawRow, maxCol, nSample).total);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(kbest_reserve_hybrid_dev(ctx, B, maxRawRow, maxCol));  // (with it kbest_reserve_clustered: the clustered sampler's too)
+    KB_TRY(raw_reserve(ctx, ctx->hybSampBuf, hybrid_sample_layout(B, maxRawRow, maxCol, nSample).total));
     ctx->hybSampB = B;
     ctx->hybSampRow = maxRawRow;
     ctx->hybSampCol = maxCol;
@@ -5031,8 +5072,7 @@ int kbest_hybrid_frontier_sample_assoc_batch_f64_dev(kbest_ctx *ctx, int B, int 
 {
     if (!ctx) return KBEST_ERR_BAD_ARG;
     const std::string who = "kbest_hybrid_frontier_sample_assoc_batch_f64_dev";
-    int rc = check_frame_shape(ctx, who.c_str(), B, maxRawRow, maxCol, KBEST_CLUSTER_MAX_COLS, CLUSTER_COLS_TEXT);
-    if (rc != KBEST_OK) return rc;
+    KB_TRY(check_frame_shape(ctx, who.c_str(), B, maxRawRow, maxCol, KBEST_CLUSTER_MAX_COLS, CLUSTER_COLS_TEXT));
     if (maxExact < 0 || maxExact > KBEST_CLUSTER_MAX_SIZE || maxWidth < 0 || maxWidth > KBEST_FRONTIER_MAX_WIDTH || nSample < 1 ||
         (uint64_t)sampleBase + (uint64_t)nSample > ((uint64_t)1 << 32))
         return fail(ctx, KBEST_ERR_BAD_ARG, (who + HYBRID_SAMPLE_ARGS_TEXT).c_str());
@@ -5041,99 +5081,56 @@ int kbest_hybrid_frontier_sample_assoc_batch_f64_dev(kbest_ctx *ctx, int B, int 
         return fail(ctx, KBEST_ERR_BAD_ARG, (who + ": bad argument").c_str());
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // everything is checked before anything is launched; an asynchronous entry never allocates
-    const HybridLayout L = hybrid_layout(B, maxRawRow, maxCol);
+    // everything is checked before anything is launched
+    HybridDevPlan d;
+    KB_TRY(hybrid_dev_plan(ctx, who.c_str(), B, maxRawRow, maxCol, d));
+    const HybridLayout &L = d.L;
     const HybridSampleLayout S = hybrid_sample_layout(B, maxRawRow, maxCol, nSample);
-    kb::FrontierWork w;
-    w.slotDoubles = (long long)(ctx->frSlot / 8);
-    w.planDoubles = (long long)maxRawRow * kb::KB_FRONTIER_STEP_DOUBLES;
-    const long long g = frontier_grid(ctx, L.cap, w.planDoubles);
-    kb::ClusterPlan pl;
-    rc = cluster_plan_of(ctx, maxRawRow, maxCol, pl, who.c_str());
-    if (rc != KBEST_OK) return rc;
     if (B > ctx->hybSampB || maxRawRow > ctx->hybSampRow || maxCol > ctx->hybSampCol || nSample > ctx->hybSampN ||
-        ctx->hybSampBuf.bytes < S.total || ctx->hybBuf.bytes < L.total || g < 1 || ctx->clusBuf.bytes < (size_t)pl.slotDoubles * 8)
+        ctx->hybSampBuf.bytes < S.total || !d.reserved)
         return fail(ctx, KBEST_ERR_NOT_RESERVED, (who + ": call kbest_reserve_hybrid_sample_dev first").c_str());
-    w.layers = static_cast<double *>(ctx->frLayers.p);
-    w.plan = static_cast<double *>(ctx->frPlan.p);
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    unsigned char *h8 = static_cast<unsigned char *>(ctx->hybBuf.p), *s8 = static_cast<unsigned char *>(ctx->hybSampBuf.p);
-    auto i32 = [h8](size_t off) { return reinterpret_cast<int32_t *>(h8 + off); };
-    auto f64 = [](unsigned char *base, size_t off) { return reinterpret_cast<double *>(base + off); };
-    rc = order_behind_last(ctx, s);  // (one work space per context)
-    if (rc != KBEST_OK) return rc;
+    unsigned char *s8 = static_cast<unsigned char *>(ctx->hybSampBuf.p);
+    auto f64 = [s8](size_t off) { return reinterpret_cast<double *>(s8 + off); };
+    KB_TRY(order_behind_last(ctx, s));  // (one work space per context)
     const Launched mark{ctx, s};
     // (the clustered work space: by the partial kernel's and the clustered sampler's entries)
     hold_if_capturing(s, {&ctx->hybBuf, &ctx->hybSampBuf, &ctx->frLayers, &ctx->frPlan});
     kb::HybridSampleParams sp;
-    sp.nL = d_nL;
-    sp.nM = d_nM;
-    sp.costOff = reinterpret_cast<const long long *>(d_costOff);
+    hybrid_common_params(sp, d, B, maxRawRow, maxCol, condition, maxWidth, d_nL, d_nM, d_cost, d_costOff, d_logPerm, d_method, d_nOpen,
+                         d_nFrontier);
     sp.asgOff = reinterpret_cast<const long long *>(d_asgOff);
     sp.lpOff = reinterpret_cast<const long long *>(d_lpOff);
-    sp.cost = d_cost;
     sp.frameKey = reinterpret_cast<const kb::u64 *>(d_frameKey);
     sp.assign = d_assign;
     sp.logProb = d_logProb;
-    sp.logPerm = d_logPerm;
-    sp.method = d_method;
-    sp.nOpenOut = d_nOpen;
-    sp.nFrontier = d_nFrontier;
-    sp.info = i32(L.info);
-    sp.nOpen = i32(L.nOpen);
-    sp.label = i32(L.label);
-    sp.openDesc = i32(L.desc);
-    sp.openRows = i32(L.rows);
-    sp.partLogPerm = f64(s8, S.partLp);
-    sp.drawLogPerm = f64(s8, S.drawLp);
+    sp.partLogPerm = f64(S.partLp);
+    sp.drawLogPerm = f64(S.drawLp);
     sp.probOff = reinterpret_cast<long long *>(s8 + S.probOff);
-    sp.list = reinterpret_cast<kb::HybridItem *>(h8 + L.list);
-    sp.count = i32(L.count);
-    sp.first = i32(L.first);
     sp.keys = reinterpret_cast<kb::HybridKeyItem *>(s8 + S.keys);
     sp.rowKey = reinterpret_cast<int32_t *>(s8 + S.rowKey);
     sp.local = reinterpret_cast<int32_t *>(s8 + S.local);
-    sp.term = f64(s8, S.term);
-    sp.logZ = f64(h8, L.logZ);
-    sp.finfo = i32(L.finfo);
-    sp.width = i32(L.width);
-    sp.packStride = L.packStride;
-    sp.B = B;
-    sp.maxRawRow = maxRawRow;
-    sp.maxCol = maxCol;
-    sp.condition = condition ? 1 : 0;
-    sp.maxWidth = maxWidth;
+    sp.term = f64(S.term);
     sp.nSample = nSample;
     hipError_t e = kb::launch_hybrid_sample_prepare(sp, s);
     if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "hybrid sampling kernel launch", e);
     // the partial kernel (its probabilities: packed, and dropped), then the clustered sampler's second instantiation
-    rc = kbest_clustered_partial_batch_f64_dev(ctx, B, maxRawRow, maxCol, d_nL, d_nM, d_cost, d_costOff, condition, maxExact,
-                                               f64(h8, L.packed), reinterpret_cast<const int64_t *>(s8 + S.probOff), f64(s8, S.partLp),
-                                               i32(L.info), d_maxCluster, i32(L.label), maxCol, i32(L.nOpen), i32(L.desc), maxCol,
-                                               i32(L.rows), maxRawRow, d_sub, stream);
-    if (rc != KBEST_OK) return rc;
-    rc = cluster_sample_dev(ctx, maxExact ? maxExact : KBEST_CLUSTER_MAX_SIZE, B, maxRawRow, maxCol, d_nL, d_nM, d_cost, d_costOff,
-                            condition, nSample, seed, sampleBase, d_frameKey, d_assign, d_asgOff, d_logProb, d_lpOff, f64(s8, S.drawLp),
-                            reinterpret_cast<int32_t *>(s8 + S.drawInfo), nullptr, stream);
-    if (rc != KBEST_OK) return rc;
-    kb::HybridParams hp{};  // the gather of kbest_hybrid.hip reads the partial kernel's outputs and writes list, first and count
-    hp.nL = d_nL;
-    hp.nM = d_nM;
-    hp.costOff = sp.costOff;
-    hp.nOpen = sp.nOpen;
-    hp.openDesc = sp.openDesc;
-    hp.list = reinterpret_cast<kb::HybridItem *>(h8 + L.list);
-    hp.count = i32(L.count);
-    hp.first = i32(L.first);
-    hp.packStride = L.packStride;
-    hp.B = B;
-    hp.maxRawRow = maxRawRow;
-    hp.maxCol = maxCol;
+    KB_TRY(kbest_clustered_partial_batch_f64_dev(ctx, B, maxRawRow, maxCol, d_nL, d_nM, d_cost, d_costOff, condition, maxExact,
+                                                 d.f64(L.packed), reinterpret_cast<const int64_t *>(s8 + S.probOff), f64(S.partLp),
+                                                 d.i32(L.info), d_maxCluster, d.i32(L.label), maxCol, d.i32(L.nOpen), d.i32(L.desc), maxCol,
+                                                 d.i32(L.rows), maxRawRow, d_sub, stream));
+    KB_TRY(cluster_sample_dev(ctx, maxExact ? maxExact : KBEST_CLUSTER_MAX_SIZE, B, maxRawRow, maxCol, d_nL, d_nM, d_cost, d_costOff,
+                              condition, nSample, seed, sampleBase, d_frameKey, d_assign, d_asgOff, d_logProb, d_lpOff, f64(S.drawLp),
+                              reinterpret_cast<int32_t *>(s8 + S.drawInfo), nullptr, stream));
+    // the gather of kbest_hybrid.hip reads the partial kernel's outputs and writes list, first and count: all among the shared fields
+    kb::HybridParams hp{};
+    hybrid_common_params(hp, d, B, maxRawRow, maxCol, condition, maxWidth, d_nL, d_nM, d_cost, d_costOff, d_logPerm, d_method, d_nOpen,
+                         d_nFrontier);
     e = kb::launch_hybrid_gather(hp, s);
     if (e == hipSuccess) e = kb::launch_hybrid_sample_keys(sp, s);
     if (e == hipSuccess && maxWidth > 0)  // (maxWidth = 0: nothing goes through the sampler, as on the host)
         e = kb::launch_frontier_sample_list(sp.list, sp.keys, sp.count, d_sub, sp.rowKey, nSample, seed, sampleBase, sp.local, sp.term,
-                                            f64(h8, L.logZ), i32(L.finfo), i32(L.width), w, (int)g, s);
+                                            d.f64(L.logZ), d.i32(L.finfo), d.i32(L.width), d.w, (int)d.grid, s);
     if (e == hipSuccess) e = kb::launch_hybrid_sample_join(sp, s);
     if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "hybrid sampling kernel launch", e);
     return KBEST_OK;

@@ -281,6 +281,26 @@ def _split_probs(probs, probOff, psizes, nL, nM):
     return [probs[probOff[b]: probOff[b] + psizes[b]].reshape(int(nM[b]), int(nL[b]) + 1) for b in range(len(nL))]
 
 
+def _pack_draws(nM, B, n_sample, frame_key, who):
+    """The draw buffers of the sampling entries, frame after frame: n_sample as int, asgOff[B], lpOff[B], assign (int32, every
+    frame's [n_sample, nM]), logp (float64, every frame's [n_sample]), both zeroed, and the keys as uint64[B] (None: no keys)."""
+    n_sample = int(n_sample)
+    sizes = nM.astype(np.int64) * max(n_sample, 0)
+    asgOff = np.zeros(B, np.int64)
+    asgOff[1:] = np.cumsum(sizes)[:-1]
+    lpOff = np.arange(B, dtype=np.int64) * n_sample
+    key = None if frame_key is None else np.ascontiguousarray(frame_key, dtype=np.uint64)
+    if key is not None and key.shape != (B,):
+        raise KBestError(f"{who}: frame_key must hold one key per frame")
+    return n_sample, asgOff, lpOff, np.zeros(int(sizes.sum()), np.int32), np.zeros(B * max(n_sample, 0), np.float64), key
+
+
+def _split_draws(assign, asgOff, logp, lpOff, nM, n_sample):
+    """The frames' [n_sample, nM] views of assign and [n_sample] views of logp."""
+    return ([assign[asgOff[b]: asgOff[b] + n_sample * int(nM[b])].reshape(n_sample, int(nM[b])) for b in range(len(nM))],
+            [logp[lpOff[b]: lpOff[b] + n_sample] for b in range(len(nM))])
+
+
 class KBestEngine:
     """One engine context = one GPU, one stream, one hypothesis-state workspace."""
 
@@ -465,21 +485,12 @@ class KBestEngine:
         the raw row of the frame's block every measurement takes, a row >= nL is a miss; list of logProb [n_sample] arrays; perm[B]).
         A frame whose permanent is 0 has assign -1 and logProb NaN."""
         nL, nM, B, flat, costOff, _, _, _ = _pack_frames(costs, nL, nM, "sample_assoc")
-        n_sample = int(n_sample)
-        asgOff = np.zeros(B, np.int64)
-        asgOff[1:] = np.cumsum(nM.astype(np.int64) * n_sample)[:-1]
-        lpOff = np.arange(B, dtype=np.int64) * n_sample
-        assign = np.zeros(int(nM.astype(np.int64).sum()) * max(n_sample, 0), np.int32)
-        logp = np.zeros(B * max(n_sample, 0), np.float64)
+        n_sample, asgOff, lpOff, assign, logp, key = _pack_draws(nM, B, n_sample, frame_key, "sample_assoc")
         perm = np.zeros(B, np.float64)
-        key = None if frame_key is None else np.ascontiguousarray(frame_key, dtype=np.uint64)
-        if key is not None and key.shape != (B,):
-            raise KBestError("sample_assoc: frame_key must hold one key per frame")
         self._check(self.lib.kbest_sample_assoc_batch_f64(self.ctx, B, _ptr(nL), _ptr(nM), _ptr(flat), _ptr(costOff), int(bool(condition)),
                                                           n_sample, int(seed), int(sample_base), _ptr(key), _ptr(assign), _ptr(asgOff),
                                                           _ptr(logp), _ptr(lpOff), _ptr(perm)))
-        return ([assign[asgOff[b]: asgOff[b] + n_sample * int(nM[b])].reshape(n_sample, int(nM[b])) for b in range(B)],
-                [logp[lpOff[b]: lpOff[b] + n_sample] for b in range(B)], perm)
+        return (*_split_draws(assign, asgOff, logp, lpOff, nM, n_sample), perm)
 
     def belief_probs(self, costs, nL, nM, condition=False, tol=1e-12, max_iter=10000):
         """Batched beliefProb (kbest_lbp.hip): the association probabilities by loopy belief propagation, nM <= 128 and
@@ -526,24 +537,15 @@ class KBestEngine:
         [n_sample] arrays; logPerm[B], info[B], maxCluster[B] as clustered_probs()).  A refused (info -2 / -3) or infeasible
         (info 0) frame has assign -1 and logProb NaN."""
         nL, nM, B, flat, costOff, _, _, _ = _pack_frames(costs, nL, nM, "clustered_sample_assoc")
-        n_sample = int(n_sample)
-        asgOff = np.zeros(B, np.int64)
-        asgOff[1:] = np.cumsum(nM.astype(np.int64) * n_sample)[:-1]
-        lpOff = np.arange(B, dtype=np.int64) * n_sample
-        assign = np.zeros(int(nM.astype(np.int64).sum()) * max(n_sample, 0), np.int32)
-        logp = np.zeros(B * max(n_sample, 0), np.float64)
+        n_sample, asgOff, lpOff, assign, logp, key = _pack_draws(nM, B, n_sample, frame_key, "clustered_sample_assoc")
         logPerm = np.zeros(B, np.float64)
         info = np.zeros(B, np.int32)
         maxCluster = np.zeros(B, np.int32)
-        key = None if frame_key is None else np.ascontiguousarray(frame_key, dtype=np.uint64)
-        if key is not None and key.shape != (B,):
-            raise KBestError("clustered_sample_assoc: frame_key must hold one key per frame")
         self._check(self.lib.kbest_clustered_sample_assoc_batch_f64(self.ctx, B, _ptr(nL), _ptr(nM), _ptr(flat), _ptr(costOff),
                                                                     int(bool(condition)), n_sample, int(seed), int(sample_base),
                                                                     _ptr(key), _ptr(assign), _ptr(asgOff), _ptr(logp), _ptr(lpOff),
                                                                     _ptr(logPerm), _ptr(info), _ptr(maxCluster)))
-        return ([assign[asgOff[b]: asgOff[b] + n_sample * int(nM[b])].reshape(n_sample, int(nM[b])) for b in range(B)],
-                [logp[lpOff[b]: lpOff[b] + n_sample] for b in range(B)], logPerm, info, maxCluster)
+        return (*_split_draws(assign, asgOff, logp, lpOff, nM, n_sample), logPerm, info, maxCluster)
 
     def exact_or_belief_probs(self, costs, nL, nM, condition=False, tol=1e-12, max_iter=10000):
         """The exact probabilities wherever the gate leaves clusters of at most 16 measurements, belief propagation elsewhere:
@@ -681,23 +683,14 @@ class KBestEngine:
         Returns (list of int32 [n_sample, nM] arrays: the raw row every measurement takes, list of logProb [n_sample], logPerm[B],
         method[B]: 0 drawn, -1 refused (assign -1, logProb NaN), -2 infeasible (likewise), nOpen[B], nFrontier[B], maxCluster[B])."""
         nL, nM, B, flat, costOff, _, _, _ = _pack_frames(costs, nL, nM, "hybrid_frontier_sample_assoc")
-        n_sample = int(n_sample)
-        sizes = n_sample * nM.astype(np.int64)
-        asgOff = np.concatenate(([0], np.cumsum(sizes)[:-1])).astype(np.int64) if B else np.zeros(0, np.int64)
-        lpOff = (np.arange(B, dtype=np.int64) * n_sample)
-        assign = np.zeros(int(sizes.sum()) if B else 0, np.int32)
-        logp = np.zeros(B * n_sample, np.float64)
+        n_sample, asgOff, lpOff, assign, logp, key = _pack_draws(nM, B, n_sample, frame_key, "hybrid_frontier_sample_assoc")
         logPerm = np.zeros(B, np.float64)
         method, nOpen, nFrontier, maxCluster = (np.zeros(B, np.int32) for _ in range(4))
-        key = None if frame_key is None else np.ascontiguousarray(frame_key, dtype=np.uint64)
-        if key is not None and len(key) != B:
-            raise ValueError("hybrid_frontier_sample_assoc: one frame key per frame")
         self._check(self.lib.kbest_hybrid_frontier_sample_assoc_batch_f64(
             self.ctx, B, _ptr(nL), _ptr(nM), _ptr(flat), _ptr(costOff), int(bool(condition)), int(max_exact), int(max_width), n_sample,
             int(seed), int(sample_base), _ptr(key), _ptr(assign), _ptr(asgOff), _ptr(logp), _ptr(lpOff), _ptr(logPerm), _ptr(method),
             _ptr(nOpen), _ptr(nFrontier), _ptr(maxCluster)))
-        return ([assign[asgOff[b]: asgOff[b] + n_sample * int(nM[b])].reshape(n_sample, int(nM[b])) for b in range(B)],
-                [logp[lpOff[b]: lpOff[b] + n_sample] for b in range(B)], logPerm, method, nOpen, nFrontier, maxCluster)
+        return (*_split_draws(assign, asgOff, logp, lpOff, nM, n_sample), logPerm, method, nOpen, nFrontier, maxCluster)
 
     def hybrid_sample_assoc(self, costs, nL, nM, n_sample, k, seed=0, condition=False, frame_key=None, sample_base=0, max_exact=16,
                             max_width=16):
@@ -708,23 +701,14 @@ class KBestEngine:
         answered clusters only), method[B]: 0 all exact, 1 every enumeration complete, 2 some cut at k, -1 refused, -2 infeasible
         (assign -1, logProb NaN), nOpen[B], nFrontier[B], nEnum[B], maxCluster[B])."""
         nL, nM, B, flat, costOff, _, _, _ = _pack_frames(costs, nL, nM, "hybrid_sample_assoc")
-        n_sample = int(n_sample)
-        sizes = n_sample * nM.astype(np.int64)
-        asgOff = np.concatenate(([0], np.cumsum(sizes)[:-1])).astype(np.int64) if B else np.zeros(0, np.int64)
-        lpOff = (np.arange(B, dtype=np.int64) * n_sample)
-        assign = np.zeros(int(sizes.sum()) if B else 0, np.int32)
-        logp = np.zeros(B * n_sample, np.float64)
+        n_sample, asgOff, lpOff, assign, logp, key = _pack_draws(nM, B, n_sample, frame_key, "hybrid_sample_assoc")
         logPerm = np.zeros(B, np.float64)
         method, nOpen, nFrontier, nEnum, maxCluster = (np.zeros(B, np.int32) for _ in range(5))
-        key = None if frame_key is None else np.ascontiguousarray(frame_key, dtype=np.uint64)
-        if key is not None and len(key) != B:
-            raise ValueError("hybrid_sample_assoc: one frame key per frame")
         self._check(self.lib.kbest_hybrid_sample_assoc_batch_f64(
             self.ctx, B, _ptr(nL), _ptr(nM), _ptr(flat), _ptr(costOff), int(bool(condition)), int(k), int(max_exact), int(max_width),
             n_sample, int(seed), int(sample_base), _ptr(key), _ptr(assign), _ptr(asgOff), _ptr(logp), _ptr(lpOff), _ptr(logPerm),
             _ptr(method), _ptr(nOpen), _ptr(nFrontier), _ptr(nEnum), _ptr(maxCluster)))
-        return ([assign[asgOff[b]: asgOff[b] + n_sample * int(nM[b])].reshape(n_sample, int(nM[b])) for b in range(B)],
-                [logp[lpOff[b]: lpOff[b] + n_sample] for b in range(B)], logPerm, method, nOpen, nFrontier, nEnum, maxCluster)
+        return (*_split_draws(assign, asgOff, logp, lpOff, nM, n_sample), logPerm, method, nOpen, nFrontier, nEnum, maxCluster)
 
     def table_sample_dev(self, k, maxCol, m, d_row4col, d_gain, d_nf, n_sample, d_assignLocal, asgOff, d_logTerm, ltOff, d_pick=None,
                          d_info=None, cutoff=42.0, cluster_key=None, frame_key=None, seed=0, sample_base=0, stream=None):

@@ -1,4 +1,4 @@
-"""GPU: the slice contract of the five host-pointer probability entries of include/kbest_c.h -- a frame's cost block and its
+"""GPU: the slice contract of the six host-pointer probability entries of include/kbest_c.h -- a frame's cost block and its
 probability slice may lie anywhere in the caller's buffers, in any order; the answer does not depend on where, bit for bit, and
 what lies between the slices (and behind the last one) in the caller's probs buffer is the caller's.  Through ctypes, so that the
 offsets are the test's own."""
@@ -74,6 +74,10 @@ ENTRIES = {
     "kbest_hybrid_exact_probs_batch_f64": (  # k = 0, maxExact = 4, maxBig = 20
         [("logPerm", np.float64), ("method", np.int32), ("nOpen", np.int32), ("nBig", np.int32), ("maxCluster", np.int32)],
         lambda lib, ctx, h, p, po, o: lib.kbest_hybrid_exact_probs_batch_f64(ctx, *h, 0, 4, 20, p, po, *o)),
+    "kbest_hybrid_frontier_probs_batch_f64": (  # k = 200, maxExact = 4, maxBig = 5, maxWidth = 4: all three tiers in one call
+        [("logPerm", np.float64), ("method", np.int32), ("nOpen", np.int32), ("nBig", np.int32), ("maxCluster", np.int32),
+         ("nFrontier", np.int32)],
+        lambda lib, ctx, h, p, po, o: lib.kbest_hybrid_frontier_probs_batch_f64(ctx, *h, 200, 4, 5, 4, p, po, *o)),
 }
 
 
@@ -117,6 +121,12 @@ def test_slices_do_not_depend_on_the_layout(eng, name):
     if name == "kbest_hybrid_exact_probs_batch_f64":  # ... and the big-cluster tier
         assert (sa["nBig"] >= 1).any(), sa["nBig"]
         assert sa["method"][4] == 0 and sa["nBig"][4] == 1, sa
+    if name == "kbest_hybrid_frontier_probs_batch_f64":  # ... and frontier, big-cluster and enumeration side by side
+        # (tests/frontier_check.hybrid_frontier_probs on these frames)
+        assert sa["method"].tolist() == [0, 0, 2, 0, 0, 0, 0, 0], sa
+        assert sa["nFrontier"].tolist() == [1, 0, 0, 1, 1, 0, 0, 0], sa
+        assert sa["nBig"].tolist() == [0, 1, 0, 0, 0, 0, 0, 0], sa
+        assert sa["nOpen"].tolist() == [1, 1, 1, 1, 1, 0, 0, 0], sa
 
 
 @pytest.mark.parametrize("name", list(ENTRIES))
