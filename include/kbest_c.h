@@ -641,16 +641,24 @@ int kbest_hybrid_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const
  * doubles) and a structural one (one workgroup does a whole cluster).  This tier lifts both.  Per cluster it works on
  * a'[r][c] = exp(colMin_c - x[r][c]), colMin_c the smallest finite entry of column c INSIDE the sub-block: a column factor is the
  * only rescaling that commutes with the recurrence, it leaves the marginals alone, and log Z_k = log Z'_k - sum_c colMin_c in the
- * units a = exp(-x).  What remains: every a' lies in (0, 1] and every column holds a 1, so Z'_k underflows only when EVERY complete
- * assignment of the cluster costs about 700 more than the sum of its column minima; such a cluster reports Z = 0 (info 0).
+ * units a = exp(-x).  What remains: every a' lies in (0, 1] and every column holds a 1, so Z'_k leaves the normal doubles only when
+ * EVERY complete assignment of the cluster costs about 700 more than the sum of its column minima.
+ * RANGE (this tier, the frontier tier and the frontier sampler below): a cluster is answered while Z'_k >= 2^-970 = e^-672.3 --
+ * every term within 2^-52 of Z'_k is then a normal double.  Below that, Z'_k = 0 included, the tier counts the complete assignments
+ * of the pattern a' > 0 (the same recurrence with every non-zero entry 1: a sum of ones cannot underflow).  None, and no finite
+ * entry whose a' underflowed to 0: info 0, INFEASIBLE -- info 0, method -2, logPerm -inf and assign -1 always mean that the cluster
+ * has no complete assignment.  Else the cluster is DECLINED: info KBEST_INFO_OUT_OF_RANGE (-5), its outputs untouched, as with the
+ * refusals -3 and -4.  In the host frame entries a declined cluster goes on to the next tier (frontier -> big-cluster -> k-best
+ * path; with k = 0 it refuses its frame: method -1, logPerm NaN); in the one-stream device entries it refuses its frame.
  *
  * kbest_bigcluster_probs_f64_dev: n clusters.  m[k] (1 .. KBEST_BIGCLUSTER_MAX_SIZE), nLk[k], subOff[k], probOff[k] are HOST arrays
  * (the launches are planned from them); the data is on the device: cluster k is the (nLk + m) x m column-major block at
  * d_sub + subOff[k] in the format of d_sub above (+inf: zero; rows that are all +inf are left out), d_probs + probOff[k] takes its
  * [m][nLk + 1] probabilities (sub-block row i < nLk -> slot i, rows >= nLk -> slot nLk), d_logZ[k] (may be NULL) its log Z_k in
  * the units a = exp(-x) -- add m * (the frame's block minimum) for the frame's units a = exp(min - x) --, d_info[k] (may be NULL):
- * 1 answered;  0: Z_k = 0 (zeros, log Z_k = -inf);  -3: its layers, (nLk + m + 3) * 2^m * 8 bytes (R_k counted as the sub-block's
- * rows), exceed the work cap: its outputs are untouched.
+ * 1 answered;  0: no complete assignment (zeros, log Z_k = -inf);  KBEST_INFO_OUT_OF_RANGE (-5): declined, Z'_k < 2^-970 (RANGE
+ * above);  -3: its layers, (nLk + m + 3) * 2^m * 8 bytes (R_k counted as the sub-block's rows), exceed the work cap.  After -5 and
+ * -3 its outputs are untouched.
  * One launch per row forward and backward: launches of one stream order the layers, no kernel waits for another workgroup.  The
  * workgroups of every launch follow from m alone and no floating-point atomics are used: a cluster gives the same bits alone, in
  * any batch and under any cap.  Clusters share launches as far as the work space holds their layers (at most KBEST_BIGCLUSTER_WORK_CAP
@@ -660,9 +668,11 @@ int kbest_hybrid_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const
  *
  * kbest_hybrid_exact_probs_batch_f64 (host buffers, synchronous): kbest_hybrid_probs_batch_f64 with this tier between the two.  The
  * partial kernel runs as there; every open cluster of at most maxBig (0 .. 20) measurements whose layers fit the work cap is
- * answered by the tier from the sub-block that already lies on the device; the remaining open clusters go through the k-best path
- * unchanged when k >= 1; with k = 0 a frame that has one is refused (method -1, zeros, logPerm NaN).
- *   method[b]:  0: every cluster exact (either tier);  1 / 2 / -2 / -1: as kbest_hybrid_probs_batch_f64; a big cluster with Z = 0: -2;
+ * answered by the tier from the sub-block that already lies on the device; the remaining open clusters, those the tier declines
+ * (-5) among them, go through the k-best path unchanged when k >= 1; with k = 0 a frame that has one is refused (method -1, zeros,
+ * logPerm NaN).
+ *   method[b]:  0: every cluster exact (either tier);  1 / 2 / -2 / -1: as kbest_hybrid_probs_batch_f64; a big cluster without a
+ *       complete assignment (info 0): -2;
  *   nOpen[b] (may be NULL): the clusters the partial kernel left open;  nBig[b] (may be NULL): those of them this tier answered;
  *   logPerm[b] (may be NULL): the sum of log Z_k over all exactly answered clusters in the frame's units (method 0: the definition
  *       of kbest_clustered_probs_batch_f64);  -inf for method -2, NaN for method -1.
@@ -670,6 +680,7 @@ int kbest_hybrid_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const
  * outside 0 .. 16 or k < 0: KBEST_ERR_BAD_ARG.
  */
 #define KBEST_BIGCLUSTER_MAX_SIZE 20
+#define KBEST_INFO_OUT_OF_RANGE (-5)  /* d_info of the column-scaled tiers: declined, Z' < 2^-970 although an assignment exists */
 #define KBEST_BIGCLUSTER_WORK_CAP ((size_t)1 << 30)  /* the layers of the clusters in flight */
 /* (a work space a captured launch holds does not grow: "WORK SPACES UNDER A CAPTURED LAUNCH" at kbest_reserve) */
 int kbest_reserve_bigcluster(kbest_ctx *ctx, int maxM, int maxRows);
@@ -696,9 +707,11 @@ int kbest_hybrid_exact_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL,
  *
  * kbest_frontier_probs_f64_dev: n clusters, arguments as kbest_bigcluster_probs_f64_dev with m[k] in 1 .. KBEST_FRONTIER_MAX_COLS
  * and nLk[k] in 0 .. 1024, plus d_width[k] (may be NULL): the cluster's W, written for every cluster.  d_info[k]: 1 answered;
- * 0: Z_k = 0 (zeros, log Z_k = -inf) -- fewer counting rows than columns, or two columns whose only row is the same row;
+ * 0: no complete assignment (zeros, log Z_k = -inf) -- fewer counting rows than columns, or two columns whose only row is the same
+ * row;  KBEST_INFO_OUT_OF_RANGE (-5): declined, Z'_k < 2^-970 although the pattern has a complete assignment (RANGE at the
+ * big-cluster tier; the count is one more forward sweep with every non-zero entry 1, run only for such a cluster);
  * -4: W > KBEST_FRONTIER_MAX_WIDTH;  -3: its layers exceed the slot (KBEST_FRONTIER_SLOT bytes).  A refused cluster's probabilities
- * and log Z_k are untouched, and both refusals follow from the cluster alone -- never from the device, the batch or the cap.
+ * and log Z_k are untouched, and all three refusals follow from the cluster alone -- never from the device, the batch or the cap.
  * One workgroup takes a cluster at a time and the grid strides over the clusters: ONE launch per KB_FRONTIER_PACK = 128 clusters (the
  * descriptors travel as a kernel argument), no workgroup waits for another, no floating-point atomics: a cluster gives the same bits
  * alone, anywhere in a batch and under any work cap.  Asynchronous on `stream` (NULL: the context's), allocates nothing: needs
@@ -708,7 +721,7 @@ int kbest_hybrid_exact_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL,
  *
  * kbest_hybrid_frontier_probs_batch_f64 (host buffers, synchronous): kbest_hybrid_exact_probs_batch_f64 with this tier first among
  * the open clusters.  The partial kernel runs as there; every open cluster of at most 64 measurements goes through the tier from
- * the sub-block that already lies on the device; what it refuses (-3, -4, or W > maxWidth, 0 .. 16) goes to the big-cluster tier
+ * the sub-block that already lies on the device; what it refuses (-3, -4, -5, or W > maxWidth, 0 .. 16) goes to the big-cluster tier
  * when it has at most maxBig measurements, the rest to the k-best path when k >= 1; with k = 0 a frame that has one is refused.
  *   method[b], nOpen[b], nBig[b], maxCluster[b], logPerm[b]: as kbest_hybrid_exact_probs_batch_f64 (method 0: every cluster exact by
  *       any tier; logPerm sums log Z_k over all exactly answered clusters);  nFrontier[b] (may be NULL): the clusters this tier answered.
@@ -736,7 +749,7 @@ int kbest_hybrid_frontier_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *
  * Draws from the exact posterior of sparse clusters (kbest_frontier_sample.hip; not in the reference): whole joint associations of a
  * cluster the frontier tier answers, drawn by a backward walk over the forward layers that tier keeps.  Nothing new is summed: the
  * plan, the scaling a'[r][c] = exp(colMin_c - x[r][c]) and the forward sweep are kbest_frontier.hip's, and d_logZ[k], d_info[k]
- * (1 / 0 / -3 / -4) and d_width[k] carry the bits of kbest_frontier_probs_f64_dev on the same cluster.  No backward sweep.
+ * (1 / 0 / -3 / -4 / -5) and d_width[k] carry the bits of kbest_frontier_probs_f64_dev on the same cluster.  No backward sweep.
  *
  * The walk of one draw: S = empty after the last row; from the last step of the plan to the first, with row r of step i:
  * T = S | closing_i, tot = F_{i+1}[S], Tt = u tot; where T holds no new column, acc = F_i[T] and Tt < acc leaves the row
@@ -752,9 +765,9 @@ int kbest_hybrid_frontier_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *
  * kbest_frontier_sample_f64_dev: n clusters; m, nLk, subOff and d_sub as kbest_frontier_probs_f64_dev; frameKeyOfCluster[k] (host,
  * may be NULL: 0) the frame key of the cluster's frame.  Out, on the device: d_assignLocal + asgOff[k]: int32 [nSample][m_k], the
  * row of the sub-block every column takes; d_logTerm + ltOff[k]: double [nSample], sum_c (colMin_c - x[r_c][c]) - log Z'_k over the
- * cluster's columns in ascending order -- every log from the cost itself, no log of a product.  d_info[k] = 0 (Z_k = 0): -1 and
- * NaN; a refused cluster (-3, -4): neither is touched.  One workgroup takes a cluster at a time, the grid strides over the
- * clusters, ONE launch per 64 clusters, no workgroup waits for another, no floating-point atomics: a cluster's outputs are a
+ * cluster's columns in ascending order -- every log from the cost itself, no log of a product.  d_info[k] = 0 (no complete
+ * assignment): -1 and NaN; a refused cluster (-3, -4, or -5: declined, Z'_k < 2^-970): neither is touched.  One workgroup takes a
+ * cluster at a time, the grid strides over the clusters, ONE launch per 64 clusters, no workgroup waits for another, no floating-point atomics: a cluster's outputs are a
  * function of (cluster, row keys, seed, frame key, draw index) alone -- the same bits alone, anywhere in a batch and under any
  * work cap.  Asynchronous on `stream` (NULL: the context's), allocates nothing: kbest_reserve_frontier_sample reserves exactly
  * what kbest_reserve_frontier does, and without it the entry returns KBEST_ERR_NOT_RESERVED; kbest_set_frontier_work_cap and
@@ -773,7 +786,7 @@ int kbest_hybrid_frontier_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *
  * mapped back to raw rows.  logProb[s] is built in two passes: the small clusters' terms in label order from 0.0, then the open
  * clusters' terms in label order.  method[b], nOpen[b], nFrontier[b], maxCluster[b] (the last three may be NULL) and logPerm[b]
  * (may be NULL): those of kbest_hybrid_frontier_probs_batch_f64(k = 0, maxBig = 0) on the same frames, bit for bit.  A frame with
- * a cluster nobody takes (more than 64 measurements, -3, -4, or W > maxWidth): method -1, every assign -1, every logProb NaN; an
+ * a cluster nobody takes (more than 64 measurements, -3, -4, -5, or W > maxWidth): method -1, every assign -1, every logProb NaN; an
  * infeasible frame: method -2, -1s and NaNs; the call itself succeeds in both cases.
  * NOTE: the draws with condition = 1 on a raw block and with condition = 0 on its conditioned block are NOT equal for the open
  * clusters, because q is a raw row and conditionCosts renumbers the rows it keeps.  Both are exact draws from the same posterior.
@@ -862,9 +875,10 @@ int kbest_hybrid_sample_assoc_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL
  * buffer, sized and addressed like d_cost: the host does not know the extent of the cost buffer) as in
  * kbest_clustered_partial_batch_f64_dev.  maxExact 0 .. 16 (0 = 16), maxWidth 1 .. 16: maxWidth = 0 would turn the tier off, which
  * with k = 0 answers nothing new -- KBEST_ERR_BAD_ARG, as everything outside those ranges.
- *   d_method[b] (required):  0: every cluster exact;  -2: an answered or frontier cluster with Z = 0: the frame is zeros, logPerm
- *       -inf;  -1: the partial kernel's d_info < 0, or an open cluster nobody took (more than 64 measurements, frontier info -3 or
- *       -4, or W > maxWidth): a frame with open clusters is zeros, nFrontier 0, logPerm NaN;
+ *   d_method[b] (required):  0: every cluster exact;  -2: an answered or frontier cluster without a complete assignment (Z = 0 /
+ *       info 0): the frame is zeros, logPerm -inf;  -1: the partial kernel's d_info < 0, or an open cluster nobody took (more than
+ *       64 measurements, frontier info -3, -4 or -5 (declined, out of range), or W > maxWidth): a frame with open clusters is zeros,
+ *       nFrontier 0, logPerm NaN;
  *   d_logPerm[b], d_nOpen[b], d_nFrontier[b], d_maxCluster[b] (each may be NULL): as kbest_hybrid_frontier_probs_batch_f64.
  * d_probs: the entry writes EVERY element of the slice of every frame within the launch bounds (the partial kernel zeroes the slice
  * before anything else), and nothing outside the slices.  A frame beyond the bounds (nM < 1, nM > maxCol, nL < 0 or

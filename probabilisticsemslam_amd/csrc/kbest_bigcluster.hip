@@ -8,10 +8,13 @@
 // with the recurrence (rows may stay unassigned, so a row factor is not uniform; F[empty set] = 1 in every layer, so a layer factor
 // is none), it leaves the marginals alone and log Z = log Z' - sum_c colMin_c in the units a = exp(-x).  Every entry lies in
 // (0, 1] and every column holds a 1: Z' leaves the normal doubles only when every complete assignment of the cluster costs about
-// 700 more than the sum of its column minima.
+// 700 more than the sum of its column minima.  The tier answers while Z' >= KB_RANGE_MIN_Z = 2^-970 (every term within 2^-52 of
+// Z' is then a normal double).  Below that, Z' = 0 included, bc_verdict counts the complete assignments of the pattern a' > 0 by
+// the same recurrence with every non-zero entry 1 -- a sum of ones cannot underflow: none, and no finite entry whose a' is 0, is
+// info 0 (zeros, log Z = -inf); else the cluster is declined, info KB_INFO_OUT_OF_RANGE = -5, its outputs untouched.
 //
 // Launches of one stream order the layers; no kernel waits for another workgroup (no grid barrier, no flag, no cooperative launch):
-//   bc_setup      one workgroup per cluster: column minima, the rows that count, a', the row masks; the outputs zeroed
+//   bc_setup      one workgroup per cluster: column minima, the rows that count, a', the row masks
 //   bc_init       F_0 = G_R = the indicator of the empty set
 //   bc_forward    one launch per row i, one thread per column subset S:
 //                     F_{i+1}[S] = F_i[S] + sum_{c in S, a'[i][c] > 0, c ascending} a'[i][c] F_i[S \ c];  all layers F_0 .. F_R stay
@@ -19,6 +22,8 @@
 //                 non-zero column, and G_i from G_{i+1} in the other of two buffers.  The sum has a fixed shape: a thread takes
 //                 BC_SPT subsets BC_THREADS apart, the wave butterfly, the four waves in ascending order, then one partial per
 //                 workgroup in HBM
+//   bc_verdict    one workgroup per cluster: answered (the outputs zeroed), infeasible or out of range (above); the count takes
+//                 the two buffers of G, which the backward sweep is done with
 //   bc_rows       sums the partials of a row in ascending workgroup order and writes the landmark rows back
 //   bc_finish     the rows >= nL_k into slot nL_k, log Z, info
 // Workgroups per cluster follow from m_k alone -- never from the device -- and there are no floating-point atomics: the order of
@@ -80,15 +85,13 @@ __device__ __forceinline__ BcView bc_view(const BigClusterPack &p, int k, double
 }
 
 __global__ void __launch_bounds__(BC_THREADS)
-bc_setup_kernel(BigClusterPack p, const double *sub, double *probs, double *layers, double *small)
+bc_setup_kernel(BigClusterPack p, const double *sub, double *layers, double *small)
 {
     const int k = blockIdx.x, tid = threadIdx.x;
     const BcView v = bc_view(p, k, layers, small);
     const double *x = sub + p.c[k].subOff;
-    double *out = probs + p.c[k].probOff;
     const int m = v.m, nr = v.rows;
     const double INF = d_inf();
-    for (int i = tid; i < m * (v.nL + 1); i += BC_THREADS) out[i] = 0.0;
     for (int i = tid; i < m * m; i += BC_THREADS) v.miss[i] = 0.0;
     for (int c = tid; c < m; c += BC_THREADS) {  // the column's smallest finite entry
         double mn = INF;
@@ -222,6 +225,61 @@ bc_backward_kernel(BigClusterPack p, int t, double *layers, double *small)
     }
 }
 
+// After the sweeps, one workgroup per cluster.  Z' >= KB_RANGE_MIN_Z: the zeros the answer is written over.  Else the complete
+// assignments of the pattern are counted, C_{i+1}[S] = C_i[S] + sum_{c in S & N_i} C_i[S \ c] in the two buffers of G: none (and no
+// finite entry lost to a' = 0): zeros, log Z = -inf, info 0; else info KB_INFO_OUT_OF_RANGE and nothing else is written.
+__global__ void __launch_bounds__(BC_THREADS)
+bc_verdict_kernel(BigClusterPack p, const double *sub, double *probs, double *logZ, int *info, double *layers, double *small)
+{
+    __shared__ int lost;
+    const int k = blockIdx.x, tid = threadIdx.x;
+    const BcView v = bc_view(p, k, layers, small);
+    const int m = v.m, nr = v.rows, R = *v.R, nsub = v.nsub;
+    const double Z = v.F[(long long)R * nsub + (nsub - 1)];
+    if (!(Z >= KB_RANGE_MIN_Z)) {  // (uniform)
+        const double INF = d_inf();
+        const double *x = sub + p.c[k].subOff;
+        double *cur = v.G, *nxt = v.G + nsub;
+        if (tid == 0) lost = 0;
+        for (int S = tid; S < nsub; S += BC_THREADS) cur[S] = (S == 0) ? 1.0 : 0.0;
+        __syncthreads();
+        for (int i = 0; i < R; i++) {
+            const unsigned mk = (unsigned)v.mask[i];
+            for (int S = tid; S < nsub; S += BC_THREADS) {
+                double val = cur[S];
+                unsigned cols = (unsigned)S & mk;
+                while (cols) {
+                    const int c = __ffs(cols) - 1;
+                    cols &= cols - 1u;
+                    val = val + cur[S ^ (1 << c)];
+                }
+                nxt[S] = val;
+            }
+            __syncthreads();
+            double *t = cur;
+            cur = nxt;
+            nxt = t;
+        }
+        for (int i = tid; i < nr * m; i += BC_THREADS) {  // a finite entry whose a' is 0 took no part in the count
+            const double e = x[i];
+            if (e < INF && !(exp(v.colMin[i / nr] - e) > 0.0)) lost = 1;
+        }
+        __syncthreads();
+        bool none = R < m;  // fewer rows than columns, or a column without a finite entry: whatever was lost
+        for (int c = 0; c < m; c++) none = none | !(v.colMin[c] < INF);
+        if (!none && (cur[nsub - 1] > 0.0 || lost)) {
+            if (tid == 0 && info) info[p.c[k].idx] = KB_INFO_OUT_OF_RANGE;
+            return;
+        }
+        if (tid == 0) {
+            if (logZ) logZ[p.c[k].idx] = -INF;
+            if (info) info[p.c[k].idx] = 0;
+        }
+    }
+    double *out = probs + p.c[k].probOff;
+    for (int i = tid; i < m * (v.nL + 1); i += BC_THREADS) out[i] = 0.0;
+}
+
 // one wave per (row, cluster): lane c sums the partials of column c in ascending workgroup order
 __global__ void __launch_bounds__(64)
 bc_rows_kernel(BigClusterPack p, double *probs, double *layers, double *small)
@@ -230,7 +288,7 @@ bc_rows_kernel(BigClusterPack p, double *probs, double *layers, double *small)
     const int R = *v.R, r = blockIdx.x, c = threadIdx.x, m = v.m;
     if (r >= R || c >= m || !(((unsigned)v.mask[r] >> c) & 1u)) return;
     const double Z = v.F[(long long)R * v.nsub + (v.nsub - 1)];
-    if (!(Z > 0.0)) return;  // (the zeros of bc_setup stay)
+    if (!(Z >= KB_RANGE_MIN_Z)) return;  // (bc_verdict has answered)
     const double *pp = v.part + (long long)r * v.nwg * m + c;
     double s = pp[0];
     for (int w = 1; w < v.nwg; w++) s = s + pp[(long long)w * m];
@@ -247,15 +305,15 @@ bc_finish_kernel(BigClusterPack p, double *probs, double *logZ, int *info, doubl
     const BcView v = bc_view(p, k, layers, small);
     const int m = v.m;
     const double Z = v.F[(long long)(*v.R) * v.nsub + (v.nsub - 1)];
-    const bool ok = Z > 0.0;
+    const bool ok = Z >= KB_RANGE_MIN_Z;  // (else bc_verdict has answered)
     if (c < m && ok) {  // the rows >= nL_k in ascending order
         double s = v.miss[c];
         for (int t = 1; t < m; t++) s = s + v.miss[t * m + c];
         probs[p.c[k].probOff + (long long)c * (v.nL + 1) + v.nL] = s / Z;
     }
-    if (c == 0) {
-        if (logZ) logZ[p.c[k].idx] = ok ? log(Z) - *v.sumCol : -d_inf();
-        if (info) info[p.c[k].idx] = ok ? 1 : 0;
+    if (c == 0 && ok) {
+        if (logZ) logZ[p.c[k].idx] = log(Z) - *v.sumCol;
+        if (info) info[p.c[k].idx] = 1;
     }
 }
 
@@ -272,12 +330,13 @@ hipError_t launch_bigcluster_pack(const BigClusterPack &p, const double *sub, do
         if (p.c[k].rows > maxRows) maxRows = p.c[k].rows;
     }
     const int nsub = 1 << maxM, gx = (nsub + BC_THREADS - 1) / BC_THREADS;
-    hipLaunchKernelGGL(bc_setup_kernel, dim3(p.n), dim3(BC_THREADS), 0, stream, p, sub, probs, layers, small);
+    hipLaunchKernelGGL(bc_setup_kernel, dim3(p.n), dim3(BC_THREADS), 0, stream, p, sub, layers, small);
     hipLaunchKernelGGL(bc_init_kernel, dim3(gx, p.n), dim3(BC_THREADS), 0, stream, p, layers, small);
     for (int i = 0; i < maxRows; i++)
         hipLaunchKernelGGL(bc_forward_kernel, dim3(gx, p.n), dim3(BC_THREADS), 0, stream, p, i, layers, small);
     for (int t = 0; t < maxRows; t++)
         hipLaunchKernelGGL(bc_backward_kernel, dim3(bigcluster_workgroups(maxM), p.n), dim3(BC_THREADS), 0, stream, p, t, layers, small);
+    hipLaunchKernelGGL(bc_verdict_kernel, dim3(p.n), dim3(BC_THREADS), 0, stream, p, sub, probs, logZ, info, layers, small);
     if (maxRows > 0) hipLaunchKernelGGL(bc_rows_kernel, dim3(maxRows, p.n), dim3(64), 0, stream, p, probs, layers, small);
     hipLaunchKernelGGL(bc_finish_kernel, dim3(p.n), dim3(64), 0, stream, p, probs, logZ, info, layers, small);
     return hipGetLastError();

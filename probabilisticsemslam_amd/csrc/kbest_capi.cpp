@@ -4049,7 +4049,7 @@ int kbest_bigcluster_probs_f64_dev(kbest_ctx *ctx, int n, const int32_t *m, cons
 
 
 // ---- the frontier tier (kbest_frontier.hip): one workgroup per open cluster, a slot of layers and a plan each --------------------
-// frames_in_flight: the kernel's 151 VGPRs give 3 waves per SIMD, 12 per CU; the slots stay under ctx->frWorkCap
+// frames_in_flight: the kernel's 153 VGPRs give 3 waves per SIMD, 12 per CU; the slots stay under ctx->frWorkCap
 static const int FRONTIER_WAVES_PER_CU = 12;
 static const int FRONTIER_LDS = 16384;
 
@@ -4399,7 +4399,8 @@ int kbest_hybrid_frontier_probs_batch_f64_dev(kbest_ctx *ctx, int B, int maxRawR
 // through the big-cluster tier first, from the sub-blocks that already lie on the device; k = 0: whatever else is open refuses
 // its frame.  maxBig = 0, k >= 1: kbest_hybrid_probs_batch_f64, step for step.
 // maxWidth > 0 (kbest_hybrid_frontier_probs_batch_f64): before that, every open cluster of at most 64 columns goes through the
-// frontier tier, again from the sub-blocks on the device; what it refuses (-3, -4, or a width beyond maxWidth) goes on as above.
+// frontier tier, again from the sub-blocks on the device; what it refuses (-3, -4, -5, or a width beyond maxWidth) goes on as above.
+// What the big-cluster tier declines (-5) goes on to the enumeration in the same way: with k = 0 it refuses its frame.
 static int hybrid_impl(kbest_ctx *ctx, const char *who, int B, const int32_t *nL, const int32_t *nM, const double *cost,
                        const int64_t *costOff, int condition, int k, int maxExact, int maxBig, int maxWidth, double *probs,
                        const int64_t *probOff, double *logPerm, int32_t *method, int32_t *nOpen, int32_t *nBig, int32_t *nFrontier,
@@ -4469,18 +4470,50 @@ static int hybrid_impl(kbest_ctx *ctx, const char *who, int B, const int32_t *nL
                     fr.d.release();  // (back to the cache with dFrP: the big-cluster tier draws next)
                 }
             }
-            size_t total = 0;
-            for (size_t i = 0; i < open.size(); i++) {
-                const OpenCluster &o = open[i];
-                if (place[i].tier != 0) continue;
-                if (maxBig > 0 && o.m <= maxBig && big_layers_bytes(o.m, o.cL + o.m) <= ctx->bigWorkCap) place[i].tier = 1;
-                else total += o.block();
-            }
-            sub.resize(total);
             std::vector<int32_t> bM, bL;
             std::vector<int64_t> bSo;
-            size_t at = 0, pat = 0, bpat = 0, bigLayers = 0;
+            size_t bpat = 0, bigLayers = 0;
             int bigM = 1, bigRows = 1;
+            for (size_t i = 0; i < open.size(); i++) {  // the big-cluster tier next: in frame order, then label order
+                const OpenCluster &o = open[i];
+                Place &p = place[i];
+                if (p.tier != 0 || !(maxBig > 0 && o.m <= maxBig && big_layers_bytes(o.m, o.cL + o.m) <= ctx->bigWorkCap)) continue;
+                p = Place{1, (int)bM.size()};
+                bM.push_back(o.m);
+                bL.push_back(o.cL);
+                bSo.push_back(costOff[o.b] + (int64_t)o.from);
+                bPo.push_back((int64_t)bpat);
+                bpat += o.slice();
+                bigLayers += big_layers_bytes(o.m, o.cL + o.m);
+                if (o.m > bigM) bigM = o.m;
+                if (o.cL + o.m > bigRows) bigRows = o.cL + o.m;
+            }
+            if (!bM.empty()) {  // the big clusters of all frames: from the sub-blocks where they lie
+                const int nb = (int)bM.size();
+                KB_TRY(big_reserve(ctx, bigLayers < ctx->bigWorkCap ? bigLayers : ctx->bigWorkCap, bigM, bigRows));
+                DevBuf dBigP, dBigOut;  // out: logZ[nb] (double) | info[nb] (int32)
+                hipError_t e;
+                if ((e = dBigP.alloc(ctx, bpat * 8)) != hipSuccess || (e = dBigOut.alloc(ctx, (size_t)nb * 12)) != hipSuccess)
+                    return fail(ctx, KBEST_ERR_NOMEM, (std::string(who) + ": device buffers").c_str(), e);
+                unsigned char *b8 = dBigOut.as<unsigned char>();
+                KB_TRY(kbest_bigcluster_probs_f64_dev(ctx, nb, bM.data(), bL.data(), bSo.data(), bPo.data(), pr.d_sub(),
+                                                      dBigP.as<double>(), reinterpret_cast<double *>(b8),
+                                                      reinterpret_cast<int32_t *>(b8 + (size_t)nb * 8), nullptr));
+                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+                bigP.resize(bpat);
+                bigLogZ.resize(nb);
+                bigInfo.resize(nb);
+                HIP_TRY(ctx, hipMemcpy(bigP.data(), dBigP.p, bpat * 8, hipMemcpyDeviceToHost));
+                HIP_TRY(ctx, hipMemcpy(bigLogZ.data(), b8, (size_t)nb * 8, hipMemcpyDeviceToHost));
+                HIP_TRY(ctx, hipMemcpy(bigInfo.data(), b8 + (size_t)nb * 8, (size_t)nb * 4, hipMemcpyDeviceToHost));
+                for (Place &p : place)  // what the tier declines (KBEST_INFO_OUT_OF_RANGE) goes on to the enumeration
+                    if (p.tier == 1 && bigInfo[p.at] < 0) p = Place{};
+            }
+            size_t total = 0;
+            for (size_t i = 0; i < open.size(); i++)
+                if (place[i].tier == 0) total += open[i].block();
+            sub.resize(total);
+            size_t at = 0, pat = 0;
             for (size_t i = 0; i < open.size();) {  // frame by frame
                 size_t e = i;
                 while (e < open.size() && open[e].b == open[i].b) e++;
@@ -4491,17 +4524,7 @@ static int hybrid_impl(kbest_ctx *ctx, const char *who, int B, const int32_t *nL
                     const OpenCluster &o = open[t];
                     Place &p = place[t];
                     n += o.block();
-                    if (p.tier == 1) {
-                        p.at = (int)bM.size();
-                        bM.push_back(o.m);
-                        bL.push_back(o.cL);
-                        bSo.push_back(costOff[b] + (int64_t)o.from);
-                        bPo.push_back((int64_t)bpat);
-                        bpat += o.slice();
-                        bigLayers += big_layers_bytes(o.m, o.cL + o.m);
-                        if (o.m > bigM) bigM = o.m;
-                        if (o.cL + o.m > bigRows) bigRows = o.cL + o.m;
-                    } else if (p.tier == 0) {
+                    if (p.tier == 0) {
                         p.at = (int)sCo.size();
                         sCo.push_back((int64_t)(at + nKeep));
                         sPo.push_back((int64_t)pat);
@@ -4523,25 +4546,6 @@ static int hybrid_impl(kbest_ctx *ctx, const char *who, int B, const int32_t *nL
                 }
                 at += nKeep;
                 i = e;
-            }
-            if (!bM.empty()) {  // the big clusters of all frames: from the sub-blocks where they lie
-                const int nb = (int)bM.size();
-                KB_TRY(big_reserve(ctx, bigLayers < ctx->bigWorkCap ? bigLayers : ctx->bigWorkCap, bigM, bigRows));
-                DevBuf dBigP, dBigOut;  // out: logZ[nb] (double) | info[nb] (int32)
-                hipError_t e;
-                if ((e = dBigP.alloc(ctx, bpat * 8)) != hipSuccess || (e = dBigOut.alloc(ctx, (size_t)nb * 12)) != hipSuccess)
-                    return fail(ctx, KBEST_ERR_NOMEM, (std::string(who) + ": device buffers").c_str(), e);
-                unsigned char *b8 = dBigOut.as<unsigned char>();
-                KB_TRY(kbest_bigcluster_probs_f64_dev(ctx, nb, bM.data(), bL.data(), bSo.data(), bPo.data(), pr.d_sub(),
-                                                      dBigP.as<double>(), reinterpret_cast<double *>(b8),
-                                                      reinterpret_cast<int32_t *>(b8 + (size_t)nb * 8), nullptr));
-                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                bigP.resize(bpat);
-                bigLogZ.resize(nb);
-                bigInfo.resize(nb);
-                HIP_TRY(ctx, hipMemcpy(bigP.data(), dBigP.p, bpat * 8, hipMemcpyDeviceToHost));
-                HIP_TRY(ctx, hipMemcpy(bigLogZ.data(), b8, (size_t)nb * 8, hipMemcpyDeviceToHost));
-                HIP_TRY(ctx, hipMemcpy(bigInfo.data(), b8 + (size_t)nb * 8, (size_t)nb * 4, hipMemcpyDeviceToHost));
             }
         }
         fb.release();  // with the buffers above: the enumeration below draws from the same cache

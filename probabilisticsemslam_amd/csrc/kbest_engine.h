@@ -666,6 +666,12 @@ hipError_t launch_kbest_cluster_sample(const ClusterSampleParams &p, const Clust
 hipError_t launch_kbest_cluster_sample_partial(const ClusterSampleParams &p, int maxExact, const ClusterPlan &pl, int grid,
                                                hipStream_t stream);
 
+// The column-scaled exact tiers (kbest_bigcluster.hip, kbest_frontier.hip, kbest_frontier_sample.hip) answer a cluster only while
+// Z' >= 2^-970: there every term within 2^-52 of Z' is still a normal double.  Below it (Z' = 0 included) a cluster that has a
+// complete assignment is declined with KB_INFO_OUT_OF_RANGE, its outputs untouched; info 0 is left to the clusters that have none.
+constexpr double KB_RANGE_MIN_Z = 0x1.0p-970;
+constexpr int KB_INFO_OUT_OF_RANGE = -5;       // KBEST_INFO_OUT_OF_RANGE
+
 // kbest_bigcluster.hip: one open cluster of up to 20 measurements over the whole chip, its layers in HBM (kbest_c.h, "Exact
 // association probabilities of clusters of 17 .. 20 measurements").  The clusters of a pack share every launch (grid.y).
 constexpr int KB_BIGCLUSTER_PACK = 32;

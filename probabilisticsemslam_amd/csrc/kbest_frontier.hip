@@ -5,6 +5,9 @@
 // Input and scaling are those of kbest_bigcluster.hip: the (nL_k + m_k) x m_k column-major sub-block of
 // kbest_clustered_partial_batch_f64_dev, +inf for a zero, rows that are all +inf left out, a'[r][c] = exp(colMin_c - x[r][c]),
 // log Z = log Z' - sum_c colMin_c.  a' is not stored: a step needs the at most 16 entries of its row and computes them again.
+// The tier answers while Z' >= KB_RANGE_MIN_Z = 2^-970 (every term within 2^-52 of Z' is then a normal double).  Below that, Z' = 0
+// included, the forward sweep runs once more with every non-zero entry 1: it counts the complete assignments of the pattern, and a
+// sum of ones cannot underflow.  None (and no finite entry whose a' is 0): info 0.  Else the cluster is declined, info -5.
 //
 // A column is a state bit only between its first and its last non-zero row: before, it is unused; after, it must be used.
 //   plan      N_r = the non-zero columns of row r (one 64-bit word), left[c] = unprocessed rows with c in N_r, seen = the union of
@@ -24,8 +27,8 @@
 //             order of the sweep.
 // No workgroup waits for another (no grid barrier, no flag, no cooperative launch) and there are no floating-point atomics: the
 // order of every sum depends on the cluster alone, so a cluster gives the same bits alone, anywhere in a batch and under any cap.
-// info: 1 answered; 0: Z' = 0 (zeros, log Z = -inf); -4: W > 16; -3: the layers sum_i 2^|Phi_i| + 2 2^W doubles exceed the
-// slot -- both from the cluster alone, and a refused cluster's outputs are not touched.
+// info: 1 answered; 0: no complete assignment (zeros, log Z = -inf); -5: Z' < 2^-970 although there is one; -4: W > 16; -3: the
+// layers sum_i 2^|Phi_i| + 2 2^W doubles exceed the slot -- all from the cluster alone, and a refused cluster's outputs are not touched.
 // Two entry points, one sweep (frontier_sweep<Source>): frontier_kernel takes its clusters from a kernel-argument pack,
 // frontier_list_kernel from the list kbest_hybrid.hip gathers on the device.
 #include <hip/hip_runtime.h>
@@ -99,11 +102,12 @@ struct FrShared {
     unsigned key[FR_THREADS / 64];
     unsigned nrM, newM, closeM;  // bits of Psi_i: in N_r / not in Phi_i / not in Phi_{i+1}
     int R, W, emptyCol;
+    int lost;                    // a finite entry whose a' is 0
     FrontierStep st;
 };
 
-// the step's description from the plan, its a' and its masks: wave 0; a barrier follows
-__device__ __forceinline__ void load_step(FrShared &sh, const FrontierStep *plan, int i, const double *x, int nr, int tid)
+// the step's description from the plan, its a' (unit: 1 for every non-zero one) and its masks: wave 0; a barrier follows
+__device__ __forceinline__ void load_step(FrShared &sh, const FrontierStep *plan, int i, const double *x, int nr, int tid, bool unit)
 {
     if (tid < 64) {
         const FrontierStep &g = plan[i];
@@ -117,7 +121,7 @@ __device__ __forceinline__ void load_step(FrShared &sh, const FrontierStep *plan
             inN = (sh.mask[g.row] >> c) & 1ull;
             isNew = pp < 0;
             closes = pn < 0;
-            sh.aval[tid] = inN ? exp(sh.colMin[c] - x[(long long)c * nr + sh.rowIdx[g.row]]) : 0.0;
+            sh.aval[tid] = !inN ? 0.0 : unit ? 1.0 : exp(sh.colMin[c] - x[(long long)c * nr + sh.rowIdx[g.row]]);
         }
         const u64 bN = __ballot(inN), bNew = __ballot(isNew), bClose = __ballot(closes);
         if (tid == 0) {
@@ -130,6 +134,42 @@ __device__ __forceinline__ void load_step(FrShared &sh, const FrontierStep *plan
             sh.newM = (unsigned)bNew;
             sh.closeM = (unsigned)bClose;
         }
+    }
+}
+
+// F_0 .. F_R of a planned cluster into its slot; unit: every non-zero a' is 1, and F_R[empty] counts the complete assignments
+__device__ __forceinline__ void forward_sweep(FrShared &sh, const FrontierStep *plan, const double *x, int nr, int R, double *slot,
+                                              long long offR, int tid, bool unit)
+{
+    if (tid == 0) slot[0] = 1.0;
+    __syncthreads();
+    for (int i = 0; i < R; i++) {
+        load_step(sh, plan, i, x, nr, tid, unit);
+        __syncthreads();
+        const unsigned psiM = (1u << sh.st.nPsi) - 1u, newM = sh.newM, closeM = sh.closeM, nrM = sh.nrM;
+        const unsigned keepM = psiM & ~closeM, phiM = psiM & ~newM;
+        const double *Fi = slot + sh.st.off;
+        double *Fn = slot + (i + 1 < R ? plan[i + 1].off : offR);
+        const int nS = 1 << sh.st.nNext;
+        for (int S = tid; S < nS; S += FR_THREADS) {
+            const unsigned T = spread_bits((unsigned)S, keepM) | closeM;
+            const unsigned nw = T & newM;
+            const unsigned base = pack_bits(T, phiM);
+            double val = 0.0;
+            if (nw == 0) {
+                val = Fi[base];
+                unsigned cols = T & nrM;
+                while (cols) {
+                    const int j = __ffs(cols) - 1;
+                    cols &= cols - 1u;
+                    val = val + sh.aval[j] * Fi[base ^ (1u << sh.st.posPhi[j])];
+                }
+            } else if ((nw & (nw - 1u)) == 0) {  // one new column: the row takes it
+                val = sh.aval[__ffs(nw) - 1] * Fi[base];
+            }
+            Fn[S] = val;
+        }
+        __syncthreads();
     }
 }
 
@@ -183,6 +223,7 @@ __device__ __forceinline__ void frontier_sweep(FrShared &sh, const Source &src, 
             sh.colMin[tid] = mn;
         }
         if (tid < KB_FRONTIER_MAX_COLS) sh.miss[tid] = 0.0;
+        if (tid == 0) sh.lost = 0;
         __syncthreads();
         for (int r = tid; r < nr; r += FR_THREADS) {
             u64 mk = 0;
@@ -191,6 +232,7 @@ __device__ __forceinline__ void frontier_sweep(FrShared &sh, const Source &src, 
                 const double e = x[(long long)c * nr + r];
                 any = any | (e < INF);
                 if (e < INF && exp(sh.colMin[c] - e) > 0.0) mk |= 1ull << c;
+                else if (e < INF) sh.lost = 1;
             }
             sh.mask[r] = mk;
             sh.done[r] = any ? 1 : 0;  // (until the rows are counted below)
@@ -288,40 +330,21 @@ __device__ __forceinline__ void frontier_sweep(FrShared &sh, const Source &src, 
             if (tid == 0 && info) info[idx] = -3;
             continue;
         }
-        for (int i = tid; i < m * (nL + 1); i += FR_THREADS) out[i] = 0.0;
-        // ---- forward -----------------------------------------------------------------------------------------------------------
-        if (tid == 0) slot[0] = 1.0;
-        __syncthreads();
-        for (int i = 0; i < R; i++) {
-            load_step(sh, plan, i, x, nr, tid);
-            __syncthreads();
-            const unsigned psiM = (1u << sh.st.nPsi) - 1u, newM = sh.newM, closeM = sh.closeM, nrM = sh.nrM;
-            const unsigned keepM = psiM & ~closeM, phiM = psiM & ~newM;
-            const double *Fi = slot + sh.st.off;
-            double *Fn = slot + (i + 1 < R ? plan[i + 1].off : offR);
-            const int nS = 1 << sh.st.nNext;
-            for (int S = tid; S < nS; S += FR_THREADS) {
-                const unsigned T = spread_bits((unsigned)S, keepM) | closeM;
-                const unsigned nw = T & newM;
-                const unsigned base = pack_bits(T, phiM);
-                double val = 0.0;
-                if (nw == 0) {
-                    val = Fi[base];
-                    unsigned cols = T & nrM;
-                    while (cols) {
-                        const int j = __ffs(cols) - 1;
-                        cols &= cols - 1u;
-                        val = val + sh.aval[j] * Fi[base ^ (1u << sh.st.posPhi[j])];
-                    }
-                } else if ((nw & (nw - 1u)) == 0) {  // one new column: the row takes it
-                    val = sh.aval[__ffs(nw) - 1] * Fi[base];
-                }
-                Fn[S] = val;
-            }
-            __syncthreads();
-        }
+        // ---- forward: the sums; where they end below the range, the count of the complete assignments over the same layers ----------
+        forward_sweep(sh, plan, x, nr, R, slot, offR, tid, false);
         const double Z = slot[offR];
-        const bool ok = Z > 0.0 && !sh.emptyCol;
+        const bool ok = Z >= KB_RANGE_MIN_Z && !sh.emptyCol;
+        bool declined = false;
+        if (!ok) {  // (uniform)
+            __syncthreads();
+            forward_sweep(sh, plan, x, nr, R, slot, offR, tid, true);
+            declined = !sh.emptyCol && (slot[offR] > 0.0 || sh.lost);
+        }
+        if (declined) {
+            if (tid == 0 && info) info[idx] = KB_INFO_OUT_OF_RANGE;
+            continue;
+        }
+        for (int i = tid; i < m * (nL + 1); i += FR_THREADS) out[i] = 0.0;
         if (!ok) {
             if (tid == 0) {
                 if (logZ) logZ[idx] = -INF;
@@ -333,7 +356,7 @@ __device__ __forceinline__ void frontier_sweep(FrShared &sh, const Source &src, 
         double *Gbuf = slot + total;
         if (tid == 0) Gbuf[0] = 1.0;
         for (int i = R - 1, t = 0; i >= 0; i--, t++) {
-            load_step(sh, plan, i, x, nr, tid);
+            load_step(sh, plan, i, x, nr, tid, false);
             __syncthreads();
             const unsigned psiM = (1u << sh.st.nPsi) - 1u, newM = sh.newM, closeM = sh.closeM, nrM = sh.nrM;
             const unsigned keepM = psiM & ~closeM, phiM = psiM & ~newM;

@@ -10,9 +10,9 @@
 // lines and with them its code objects): the (nL_k + m_k) x m_k column-major sub-block, a'[r][c] = exp(colMin_c - x[r][c]), the
 // greedy row order, Phi_i / Psi_i / closing_i / new_i, F_0 = {empty: 1},
 //     F_{i+1}[S] = [T & new = 0] F_i[T] + sum_{c in T & N_r, (T \ c) & new = 0, c ascending} a'[r][c] F_i[T \ c],   T = S | closing_i
-// Z' = F_R[empty]; logZ, info (1 / 0 / -3 / -4) and width are that tier's, bit for bit -- the slot is counted with the two
-// buffers of its backward sweep although nothing is swept backward here, so that a cluster is refused here exactly when it is
-// refused there.
+// Z' = F_R[empty]; logZ, info (1 / 0 / -3 / -4 / -5, the range check and the count of that file included) and width are that tier's,
+// bit for bit -- the slot is counted with the two buffers of its backward sweep although nothing is swept backward here, so that a
+// cluster is refused here exactly when it is refused there.
 //
 // The walk: thread t owns FS_DPT draws of a round of FS_THREADS * FS_DPT; all threads go through the steps of the plan together,
 // from the last to the first, and wave 0 stages a step (its description, its a', its masks, its row key) in LDS once per round for
@@ -25,7 +25,8 @@
 // counter (sampleBase + s, 0x80000000 | (q >> 1), frameKey low, frameKey high), words 0, 1 for an even q and 2, 3 for an odd one,
 // q = rowKey[row of the sub-block]: bit 31 of the second word keeps these uniforms apart from kbest_cluster_sample.hip's.
 // Out: assignLocal[s][c] = the row of the sub-block column c takes; logTerm[s] = sum_c (colMin_c - x[r_c][c]) - log Z', the columns
-// in ascending order, no log of a product.  info 0 (Z' = 0): assignLocal -1, logTerm NaN; a refusal (-3, -4): neither is touched.
+// in ascending order, no log of a product.  info 0 (no complete assignment): assignLocal -1, logTerm NaN; a refusal (-3, -4, -5):
+// neither is touched.
 // No workgroup waits for another (no grid barrier, no flag), no floating-point atomics, no sum over threads: a cluster's outputs
 // are a function of (cluster, row keys, seed, frame key, draw index) alone, anywhere in a batch and under any cap.
 #include <hip/hip_runtime.h>
@@ -89,13 +90,16 @@ struct FsShared {
     unsigned key[FS_THREADS / 64];
     unsigned nrM, newM, closeM;  // bits of Psi_i: in N_r / not in Phi_i / not in Phi_{i+1}
     int R, W, emptyCol;
+    int lost;                    // a finite entry whose a' is 0
     int subRow;                  // the walk: the step's row in the sub-block ...
     unsigned q;                  // ... and its key
     FsStep st;
 };
 
-// the step's description from the plan, its a' and its masks: wave 0; a barrier follows.  rowKey: the walk's (or nullptr)
-__device__ __forceinline__ void fs_load_step(FsShared &sh, const FsStep *plan, int i, const double *x, int nr, int tid, const int *rowKey)
+// the step's description from the plan, its a' (unit: 1 for every non-zero one) and its masks: wave 0; a barrier follows.
+// rowKey: the walk's (or nullptr)
+__device__ __forceinline__ void fs_load_step(FsShared &sh, const FsStep *plan, int i, const double *x, int nr, int tid, const int *rowKey,
+                                             bool unit)
 {
     if (tid < 64) {
         const FsStep &g = plan[i];
@@ -109,7 +113,7 @@ __device__ __forceinline__ void fs_load_step(FsShared &sh, const FsStep *plan, i
             inN = (sh.mask[g.row] >> c) & 1ull;
             isNew = pp < 0;
             closes = pn < 0;
-            sh.aval[tid] = inN ? exp(sh.colMin[c] - x[(long long)c * nr + sh.rowIdx[g.row]]) : 0.0;
+            sh.aval[tid] = !inN ? 0.0 : unit ? 1.0 : exp(sh.colMin[c] - x[(long long)c * nr + sh.rowIdx[g.row]]);
         }
         const u64 bN = __ballot(inN), bNew = __ballot(isNew), bClose = __ballot(closes);
         if (tid == 0) {
@@ -125,6 +129,42 @@ __device__ __forceinline__ void fs_load_step(FsShared &sh, const FsStep *plan, i
             sh.subRow = sr;
             sh.q = rowKey ? (unsigned)rowKey[sr] : 0u;
         }
+    }
+}
+
+// F_0 .. F_R of a planned cluster into its slot; unit: every non-zero a' is 1, and F_R[empty] counts the complete assignments
+__device__ __forceinline__ void fs_forward_sweep(FsShared &sh, const FsStep *plan, const double *x, int nr, int R, double *slot,
+                                                 long long offR, int tid, bool unit)
+{
+    if (tid == 0) slot[0] = 1.0;
+    __syncthreads();
+    for (int i = 0; i < R; i++) {
+        fs_load_step(sh, plan, i, x, nr, tid, nullptr, unit);
+        __syncthreads();
+        const unsigned psiM = (1u << sh.st.nPsi) - 1u, newM = sh.newM, closeM = sh.closeM, nrM = sh.nrM;
+        const unsigned keepM = psiM & ~closeM, phiM = psiM & ~newM;
+        const double *Fi = slot + sh.st.off;
+        double *Fn = slot + (i + 1 < R ? plan[i + 1].off : offR);
+        const int nS = 1 << sh.st.nNext;
+        for (int S = tid; S < nS; S += FS_THREADS) {
+            const unsigned T = fs_spread_bits((unsigned)S, keepM) | closeM;
+            const unsigned nw = T & newM;
+            const unsigned base = fs_pack_bits(T, phiM);
+            double val = 0.0;
+            if (nw == 0) {
+                val = Fi[base];
+                unsigned cols = T & nrM;
+                while (cols) {
+                    const int j = __ffs(cols) - 1;
+                    cols &= cols - 1u;
+                    val = val + sh.aval[j] * Fi[base ^ (1u << sh.st.posPhi[j])];
+                }
+            } else if ((nw & (nw - 1u)) == 0) {  // one new column: the row takes it
+                val = sh.aval[__ffs(nw) - 1] * Fi[base];
+            }
+            Fn[S] = val;
+        }
+        __syncthreads();
     }
 }
 
@@ -189,6 +229,7 @@ __device__ __forceinline__ void frontier_sample_walk(FsShared &sh, const Source 
             for (int r = 0; r < nr; r++) mn = min_keep(mn, x[(long long)tid * nr + r]);
             sh.colMin[tid] = mn;
         }
+        if (tid == 0) sh.lost = 0;
         __syncthreads();
         for (int r = tid; r < nr; r += FS_THREADS) {
             u64 mk = 0;
@@ -197,6 +238,7 @@ __device__ __forceinline__ void frontier_sample_walk(FsShared &sh, const Source 
                 const double e = x[(long long)c * nr + r];
                 any = any | (e < INF);
                 if (e < INF && exp(sh.colMin[c] - e) > 0.0) mk |= 1ull << c;
+                else if (e < INF) sh.lost = 1;
             }
             sh.mask[r] = mk;
             sh.done[r] = any ? 1 : 0;  // (until the rows are counted below)
@@ -294,39 +336,18 @@ __device__ __forceinline__ void frontier_sample_walk(FsShared &sh, const Source 
             if (tid == 0 && info) info[idx] = -3;
             continue;
         }
-        // ---- forward -----------------------------------------------------------------------------------------------------------
-        if (tid == 0) slot[0] = 1.0;
-        __syncthreads();
-        for (int i = 0; i < R; i++) {
-            fs_load_step(sh, plan, i, x, nr, tid, nullptr);
-            __syncthreads();
-            const unsigned psiM = (1u << sh.st.nPsi) - 1u, newM = sh.newM, closeM = sh.closeM, nrM = sh.nrM;
-            const unsigned keepM = psiM & ~closeM, phiM = psiM & ~newM;
-            const double *Fi = slot + sh.st.off;
-            double *Fn = slot + (i + 1 < R ? plan[i + 1].off : offR);
-            const int nS = 1 << sh.st.nNext;
-            for (int S = tid; S < nS; S += FS_THREADS) {
-                const unsigned T = fs_spread_bits((unsigned)S, keepM) | closeM;
-                const unsigned nw = T & newM;
-                const unsigned base = fs_pack_bits(T, phiM);
-                double val = 0.0;
-                if (nw == 0) {
-                    val = Fi[base];
-                    unsigned cols = T & nrM;
-                    while (cols) {
-                        const int j = __ffs(cols) - 1;
-                        cols &= cols - 1u;
-                        val = val + sh.aval[j] * Fi[base ^ (1u << sh.st.posPhi[j])];
-                    }
-                } else if ((nw & (nw - 1u)) == 0) {  // one new column: the row takes it
-                    val = sh.aval[__ffs(nw) - 1] * Fi[base];
-                }
-                Fn[S] = val;
-            }
-            __syncthreads();
-        }
+        // ---- forward: the sums; where they end below the range, the count of the complete assignments over the same layers ----------
+        fs_forward_sweep(sh, plan, x, nr, R, slot, offR, tid, false);
         const double Z = slot[offR];
-        const bool ok = Z > 0.0 && !sh.emptyCol;
+        const bool ok = Z >= KB_RANGE_MIN_Z && !sh.emptyCol;
+        if (!ok) {  // (uniform)
+            __syncthreads();
+            fs_forward_sweep(sh, plan, x, nr, R, slot, offR, tid, true);
+            if (!sh.emptyCol && (slot[offR] > 0.0 || sh.lost)) {
+                if (tid == 0 && info) info[idx] = KB_INFO_OUT_OF_RANGE;
+                continue;
+            }
+        }
         if (!ok) {  // no draw: every thread answers the draws it owns
             for (int s = tid; s < nSample; s += FS_THREADS) {
                 for (int c = 0; c < m; c++) asg[(long long)s * m + c] = -1;
@@ -352,7 +373,7 @@ __device__ __forceinline__ void frontier_sample_walk(FsShared &sh, const Source 
                     for (int c = 0; c < m; c++) asg[(long long)s * m + c] = -1;
             }
             for (int i = R - 1; i >= 0; i--) {
-                fs_load_step(sh, plan, i, x, nr, tid, rowKey);
+                fs_load_step(sh, plan, i, x, nr, tid, rowKey, false);
                 __syncthreads();
                 const unsigned psiM = (1u << sh.st.nPsi) - 1u, newM = sh.newM, closeM = sh.closeM, nrM = sh.nrM;
                 const unsigned keepM = psiM & ~closeM, phiM = psiM & ~newM;

@@ -613,7 +613,8 @@ class KBestEngine:
         """kbest_bigcluster_probs_f64_dev, asynchronous on `stream`: m, nLk, subOff, probOff are HOST sequences (one entry per
         cluster), d_sub / d_probs / d_logZ / d_info torch CUDA tensors: cluster k is the (nLk + m) x m column-major block at
         d_sub[subOff[k]:] (the format the partial clustered kernel hands out) and gets [m][nLk + 1] probabilities at
-        d_probs[probOff[k]:], log Z_k and info (1 answered, 0 infeasible, -3 beyond the work cap)."""
+        d_probs[probOff[k]:], log Z_k and info (1 answered, 0 no complete assignment, -5 declined: Z' below 2^-970 although there is
+        one, -3 beyond the work cap; after -5 and -3 the outputs are untouched)."""
         m = np.ascontiguousarray(m, dtype=np.int32)
         nLk = np.ascontiguousarray(nLk, dtype=np.int32)
         subOff = np.ascontiguousarray(subOff, dtype=np.int64)
@@ -663,8 +664,8 @@ class KBestEngine:
     def frontier_probs_dev(self, m, nLk, subOff, probOff, d_sub, d_probs, d_logZ=None, d_info=None, d_width=None, stream=None,
                            reserve=True):
         """kbest_frontier_probs_f64_dev, asynchronous on `stream`: arguments as bigcluster_probs_dev() with up to 64 measurements a
-        cluster, plus d_width (the cluster's frontier width W).  info: 1 answered, 0 infeasible, -4 W > 16, -3 layers beyond the
-        slot (refused: probabilities and log Z untouched)."""
+        cluster, plus d_width (the cluster's frontier width W).  info: 1 answered, 0 no complete assignment, -5 declined (Z' below
+        2^-970 although there is one), -4 W > 16, -3 layers beyond the slot (refused: probabilities and log Z untouched)."""
         m = np.ascontiguousarray(m, dtype=np.int32)
         nLk = np.ascontiguousarray(nLk, dtype=np.int32)
         subOff = np.ascontiguousarray(subOff, dtype=np.int64)

@@ -5,9 +5,13 @@ the tests.
     a'[r][c] = exp(colMin_c - x[r][c]), colMin_c the column's smallest finite entry inside the sub-block; all-+inf rows left out
     the recurrences of permanent_check on a' (vectorised over the subsets by halves, so that 20 columns take seconds)
     probs[c][min(r, nL_k)] += w[r][c] / Z';  log Z_k = log Z' - sum_c colMin_c  in the units a = exp(-x)
+    answered (info 1) while Z' >= RANGE_MIN = 2^-970.  Below it, Z' = 0 included: the complete assignments of the pattern a' > 0 are
+    counted by the same recurrence on ones; none, and no finite entry whose a' is 0: info 0 (zeros, log Z = -inf); else the cluster
+    is declined, info OUT_OF_RANGE = -5, nothing written
     the frame: clusters as cluster_check.clusters_of; a cluster of at most max_exact columns whose layers fit the slot: exactly as
     cluster_check; an open one of at most max_big columns whose layers (nL_k + m_k + 3) 2^m_k 8 bytes fit work_cap: the sums
-    above; whatever else is open: hybrid_check's assignmentProb(k) on the sub-block, or, with k = 0, the frame is refused
+    above; whatever else is open, a cluster the tier declines included: hybrid_check's assignmentProb(k) on the sub-block, or,
+    with k = 0, the frame is refused
     logPerm = sum of log Z_k over the exactly answered clusters in the frame's units a = exp(min - x): + m_k min for a big one
 
 Cost blocks are column-major (nL+nM) x nM, as everywhere in this project."""
@@ -22,6 +26,8 @@ import permanent_check as pc
 
 MAX_BIG = 20          # KBEST_BIGCLUSTER_MAX_SIZE
 WORK_CAP = 1 << 30    # KBEST_BIGCLUSTER_WORK_CAP
+RANGE_MIN = 2.0 ** -970   # KB_RANGE_MIN_Z: the column-scaled tiers answer while Z' >= this
+OUT_OF_RANGE = -5         # KBEST_INFO_OUT_OF_RANGE
 
 
 def layers_bytes(m, nLk):
@@ -56,8 +62,18 @@ def scaled_subset_sums(a):
     return w, F[R, n - 1]
 
 
+def count_assignments(pattern):
+    """pattern: (R, C) bool.  The number of ways to give every column a row of its own among its True entries, as a float."""
+    layer = np.zeros(1 << pattern.shape[1])
+    layer[0] = 1.0
+    for row in pattern:
+        layer = _step(layer, row.astype(np.float64))
+    return layer[-1]
+
+
 def big_cluster(block, nLk, m):
-    """One sub-block (flat column-major (nLk + m) x m).  Returns (probs [m, nLk + 1], logZ in the units a = exp(-x), info)."""
+    """One sub-block (flat column-major (nLk + m) x m).  Returns (probs [m, nLk + 1], logZ in the units a = exp(-x), info); declined
+    (info OUT_OF_RANGE): (None, None, info)."""
     X = np.asarray(block, dtype=np.float64).reshape(m, nLk + m).T
     fin = np.isfinite(X)
     colmin = np.where(fin, X, np.inf).min(axis=0)
@@ -68,7 +84,9 @@ def big_cluster(block, nLk, m):
     with np.errstate(invalid="ignore"):
         A = np.where(fin[rows], np.exp(colmin - X[rows]), 0.0)
     w, Z = scaled_subset_sums(A)
-    if not Z > 0.0:
+    if not Z >= RANGE_MIN:
+        if count_assignments(A > 0.0) > 0.0 or (fin[rows] & (A == 0.0)).any():
+            return None, None, OUT_OF_RANGE
         return probs, float("-inf"), 0
     for i, r in enumerate(rows):
         probs[:, min(int(r), nLk)] += w[i] / Z
@@ -108,12 +126,16 @@ def hybrid_exact_probs(cost, nL, nM, k=0, condition=False, max_exact=cc.MAX_SIZE
         logperm = logperm + float(np.log(Z))
         for i, r in enumerate(rows):
             probs[cols, min(int(r), nL)] += w[i] / Z
+    for o in opens:
+        if o["big"]:
+            o["probs"], o["logZ"], o["info"] = big_cluster(o["block"], o["nL"], o["m"])
+            o["big"] = o["info"] >= 0  # (declined: on to the enumeration)
     if k < 1 and any(not o["big"] for o in opens):
         return zeros, -1, opens, 0, maxc, nan
     method, nbig = 0, 0
     for o in opens:
         if o["big"]:
-            p, o["logZ"], info = big_cluster(o["block"], o["nL"], o["m"])
+            p, info = o["probs"], o["info"]
             if info <= 0:
                 method = -2
             else:

@@ -12,7 +12,8 @@ tests.
     row, a state that lacks a column whose last row this was is dropped.  Z' = F_R[all columns];
     w[r][c] = a'[r][c] sum_{S in F_i, c not in S} F_i[S] G_{i+1}[S | c]
     probs[c][min(r, nL_k)] += w[r][c] / Z';  log Z_k = log Z' - sum_c colMin_c
-    info: 1 answered, 0 Z' = 0, -4 W > max_width, -3 layers beyond slot_bytes (refusals: nothing written)
+    info: 1 answered (Z' >= bigcluster_check.RANGE_MIN), 0 no complete assignment, -5 Z' below the range although the pattern has
+    one (the same sweep on ones counts them), -4 W > max_width, -3 layers beyond slot_bytes (refusals: nothing written)
     the frame (hybrid_frontier_probs): bigcluster_check.hybrid_exact_probs with this tier first among the open clusters
 
 Cost blocks are column-major (nL+nM) x nM, as everywhere in this project."""
@@ -78,10 +79,11 @@ def layers_bytes(masks, m):
     return greedy_plan(masks, m)[2] * 8
 
 
-def frontier_sums(a, order=None):
+def frontier_sums(a, order=None, dtype=np.float64):
     """a: (R, C) non-negative.  Returns (w (R, C), Z) as permanent_check.subset_sums; the rows are taken in `order` (the greedy
-    order when None)."""
-    a = np.asarray(a, dtype=np.float64)
+    order when None).  dtype: the arithmetic (np.longdouble for the tests' truth; float64 is the kernels')."""
+    a = np.asarray(a, dtype=dtype)
+    one, zero = a.dtype.type(1), a.dtype.type(0)
     R, C = a.shape
     masks = row_masks(a)
     if order is None:
@@ -92,31 +94,31 @@ def frontier_sums(a, order=None):
         for c in range(C):
             if (masks[r] >> c) & 1:
                 last_row[c] = i
-    F = [{0: 1.0}]
+    F = [{0: one}]
     for i, r in enumerate(order):
         cols = [c for c in range(C) if (masks[r] >> c) & 1]
         must = sum(1 << c for c in cols if last_row[c] == i)
         nxt = {}
         for S, v in F[i].items():  # (a row may stay unassigned)
-            nxt[S] = nxt.get(S, 0.0) + v
+            nxt[S] = nxt.get(S, zero) + v
         for c in cols:
             for S, v in F[i].items():
                 if not (S >> c) & 1:
                     T = S | (1 << c)
-                    nxt[T] = nxt.get(T, 0.0) + a[r, c] * v
+                    nxt[T] = nxt.get(T, zero) + a[r, c] * v
         F.append({S: v for S, v in nxt.items() if S & must == must})
-    Z = F[len(order)].get(full, 0.0)
-    w = np.zeros((R, C))
-    G = {full: 1.0}
+    Z = F[len(order)].get(full, zero)
+    w = np.zeros((R, C), dtype=a.dtype)
+    G = {full: one}
     for i in range(len(order) - 1, -1, -1):
         r = order[i]
         cols = [c for c in range(C) if (masks[r] >> c) & 1]
         prev = {}
         for S, v in F[i].items():
-            g = G.get(S, 0.0)
+            g = G.get(S, zero)
             for c in cols:
                 if not (S >> c) & 1:
-                    t = G.get(S | (1 << c), 0.0)
+                    t = G.get(S | (1 << c), zero)
                     w[r, c] += v * t
                     g += a[r, c] * t
             prev[S] = g
@@ -148,8 +150,12 @@ def frontier_cluster(block, nLk, m, slot_bytes=SLOT, max_width=MAX_WIDTH):
     probs = np.zeros((m, nLk + 1))
     if not np.isfinite(colmin).all():
         return probs, float("-inf"), 0, W
-    w, Z = frontier_sums(A, [s["row"] for s in steps])
-    if not Z > 0.0:
+    order = [s["row"] for s in steps]
+    w, Z = frontier_sums(A, order)
+    if not Z >= bc.RANGE_MIN:
+        fin = np.isfinite(np.asarray(block, dtype=np.float64).reshape(m, nLk + m).T[rows])
+        if frontier_sums((A > 0.0).astype(np.float64), order)[1] > 0.0 or (fin & (A == 0.0)).any():
+            return None, None, bc.OUT_OF_RANGE, W
         return probs, float("-inf"), 0, W
     for i, r in enumerate(rows):
         probs[:, min(int(r), nLk)] += w[i] / Z
@@ -197,13 +203,13 @@ def hybrid_frontier_probs(cost, nL, nM, k=0, condition=False, max_exact=cc.MAX_S
                 o["tier"], o["probs"], o["logZ"], o["info"] = "frontier", p, lz, info
                 continue
         if 0 < o["m"] <= max_big and bc.layers_bytes(o["m"], o["nL"]) <= work_cap:
-            o["tier"] = "big"
+            p, lz, info = bc.big_cluster(o["block"], o["nL"], o["m"])
+            if info >= 0:  # (declined: on to the enumeration)
+                o["tier"], o["probs"], o["logZ"], o["info"] = "big", p, lz, info
     if k < 1 and any(o["tier"] == "kbest" for o in opens):
         return zeros, -1, opens, 0, 0, maxc, nan
     method, nfr, nbig = 0, 0, 0
     for o in opens:
-        if o["tier"] == "big":
-            o["probs"], o["logZ"], o["info"] = bc.big_cluster(o["block"], o["nL"], o["m"])
         if o["tier"] in ("frontier", "big"):
             if o["info"] <= 0:
                 infeasible = True

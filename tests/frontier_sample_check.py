@@ -5,7 +5,8 @@ kbest_hybrid_frontier_sample_assoc_batch_f64) for the test
     closing of every step); the forward layers as arrays over the subsets of Phi_i (state bit j = the j-th column of Phi_i in
     ascending order), with the kernel's order of additions:
         F_{i+1}[S] = [T & new = 0] F_i[T] + sum_{c in T & N_r, (T \\ c) & new = 0, c ascending} a'[r][c] F_i[T \\ c],  T = S | closing_i
-    Z' = F_R[empty]
+    Z' = F_R[empty]; below bigcluster_check.RANGE_MIN the cluster is declined (-5) or has no complete assignment (0), as
+    frontier_check.frontier_cluster decides
     the walk, vectorised over the draws: S = empty; for i = R-1 .. 0: tot = F_{i+1}[S], Tt = u tot; T & new == 0: acc = F_i[T],
     Tt < acc: nothing; else for c ascending as above: acc = acc + a'[r][c] F_i[T \\ c], the first c with Tt < acc (else the last
     with a term > 0)
@@ -26,6 +27,7 @@ import functools
 
 import numpy as np
 
+import bigcluster_check as bc
 import cluster_check as cc
 import cluster_sample_check as csc
 import frontier_check as fc
@@ -93,8 +95,12 @@ def cluster_layers(block, nLk, m, slot_bytes=fc.SLOT, max_width=fc.MAX_WIDTH):
             val = np.where(on, val + A[r, c] * Fi[pack(Tc & phi, phi_cols)], val)
         F.append(val)
     Z = float(F[-1][0])
-    ok = Z > 0.0 and np.isfinite(colmin).all() and all(any((n >> c) & 1 for n in masks) for c in range(m))
-    return Layers(A, rows, colmin, X, masks, steps, W, F, Z, 1 if ok else 0)
+    some = np.isfinite(colmin).all() and all(any((n >> c) & 1 for n in masks) for c in range(m))
+    if some and not Z >= bc.RANGE_MIN:  # below the range: declined if the pattern has a complete assignment (or lost an entry)
+        count = fc.frontier_sums((A > 0.0).astype(np.float64), [st["row"] for st in steps])[1]
+        if count > 0.0 or (np.isfinite(X[rows]) & (A == 0.0)).any():
+            return Layers(A, rows, colmin, X, masks, steps, W, None, None, bc.OUT_OF_RANGE)
+    return Layers(A, rows, colmin, X, masks, steps, W, F, Z, 1 if some and Z >= bc.RANGE_MIN else 0)
 
 
 def walk(L, row_key, n_sample, seed=0, frame_key=0, sample_base=0):

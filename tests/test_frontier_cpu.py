@@ -16,6 +16,7 @@ import frontier_check as fc
 import hybrid_check as hc
 import permanent_check as pc
 import probabilisticsemslam_amd as pk
+import range_lib as rl
 from probabilisticsemslam_amd import workloads as wl
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -183,7 +184,13 @@ def test_kernel_source_on_the_host_under_sanitizers(tmp_path):
         blk[:58] = -np.log(A)
     blocks.append((np.ascontiguousarray(blk.T).reshape(-1), 58, 25))
     want.append(fc.frontier_cluster(*blocks[-1]))
-    assert [w[2] for w in want] == [1, 1, 1, 1, 1, 0, fc.REFUSED_WIDTH, 1]
+    # beyond the range (tests/range_lib.py): a deep pair chain of 64 columns is declined, a cluster without a matching stays 0
+    for c in (rl.pair_chain(32, 25), rl.no_matching()["three_columns_two_rows"]):
+        blocks.append((c.block, c.nLk, c.m))
+        want.append(fc.frontier_cluster(*blocks[-1]))
+        names.append(c.name)
+    names.insert(7, "25 x 58")
+    assert [w[2] for w in want] == [1, 1, 1, 1, 1, 0, fc.REFUSED_WIDTH, 1, bc.OUT_OF_RANGE, 0]
     src = tmp_path / "in.bin"
     with open(src, "wb") as f:
         f.write(struct.pack("i", len(blocks)))
@@ -194,7 +201,7 @@ def test_kernel_source_on_the_host_under_sanitizers(tmp_path):
         out = tmp_path / "out.bin"
         subprocess.check_call([exe, str(src), str(out)] + args)
         buf, at = out.read_bytes(), 0
-        for (b, l, m), (wp, wlz, winfo, wW), name in zip(blocks, want, names + ["25 x 58"]):
+        for (b, l, m), (wp, wlz, winfo, wW), name in zip(blocks, want, names):
             info, width, lz = struct.unpack_from("iid", buf, at)
             p = np.frombuffer(buf, dtype=np.float64, count=m * (l + 1), offset=at + 16).reshape(m, l + 1)
             at += 16 + 8 * m * (l + 1)
