@@ -33,6 +33,7 @@
 
 #include "kbest_engine.h"
 #include "kbest_wave.h"
+#include "kbest_wave_sum.h"
 
 namespace kb {
 
@@ -41,18 +42,6 @@ namespace {
 constexpr int BC_MAX = 20;        // KBEST_BIGCLUSTER_MAX_SIZE
 constexpr int BC_THREADS = 256;   // every kernel but bc_rows / bc_finish
 constexpr int BC_SPT = 4;         // subsets per thread of the backward sweep: BC_THREADS * BC_SPT subsets per workgroup
-
-// fp64 sum over the 64 lanes in ONE fixed order; valid in lane 63 only.  All lanes must be active.  (kbest_perm.hip)
-__device__ __forceinline__ double wave_sum63_f64(double x)
-{
-    x = x + dpp_f64<0xB1, 0xF>(x);   // quad_perm [1,0,3,2]
-    x = x + dpp_f64<0x4E, 0xF>(x);   // quad_perm [2,3,0,1]
-    x = x + dpp_f64<0x141, 0xF>(x);  // row_half_mirror
-    x = x + dpp_f64<0x140, 0xF>(x);  // row_mirror
-    x = x + dpp_f64<0x142, 0xA>(x);  // row_bcast:15 -> rows 1,3
-    x = x + dpp_f64<0x143, 0xC>(x);  // row_bcast:31 -> rows 2,3
-    return x;
-}
 
 struct BcView {  // one cluster's part of the work space
     double *a, *colMin, *sumCol, *miss, *part, *F, *G;

@@ -33,6 +33,7 @@
 
 #include "kbest_engine.h"
 #include "kbest_wave.h"
+#include "kbest_wave_sum.h"
 
 namespace kb {
 
@@ -55,18 +56,6 @@ __host__ __device__ inline int cl_threads(int m)
 
 // the tier of a cluster: a function of its own columns and rows only
 __host__ __device__ inline bool cl_small(int m, int R) { return m <= 6 && (R * (1 << m) + R * m) * 8 <= CL_WAVE_BYTES; }
-
-// fp64 sum over the 64 lanes in ONE fixed order; valid in lane 63 only.  All lanes must be active.  (kbest_perm.hip)
-__device__ __forceinline__ double wave_sum63_f64(double x)
-{
-    x = x + dpp_f64<0xB1, 0xF>(x);   // quad_perm [1,0,3,2]
-    x = x + dpp_f64<0x4E, 0xF>(x);   // quad_perm [2,3,0,1]
-    x = x + dpp_f64<0x141, 0xF>(x);  // row_half_mirror
-    x = x + dpp_f64<0x140, 0xF>(x);  // row_mirror
-    x = x + dpp_f64<0x142, 0xA>(x);  // row_bcast:15 -> rows 1,3
-    x = x + dpp_f64<0x143, 0xC>(x);  // row_bcast:31 -> rows 2,3
-    return x;
-}
 
 // the j-th set bit (ascending) of a 128-bit mask that has more than j bits
 __device__ __forceinline__ int nth_bit128(u64 lo, u64 hi, int j)

@@ -14,116 +14,7 @@
 //        the (nL_k + m) * m doubles of its sub-block.
 //   OUT: int count; per cluster of the list: int b, root, m, nL, idx, sent; long long subOff, probOff, rowAt; per frame: int method,
 //        nFrontier, nOpen, first; double logPerm; its slice.
-#include <barrier>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <thread>
-#include <vector>
-#define KBEST_WAVE_H
-#define __global__
-#define __device__
-#define __host__
-#define __forceinline__ inline
-#define __shared__ static
-#define __launch_bounds__(x)
-typedef unsigned long long u64;
-typedef unsigned u32;
-struct dim3 { int x = 1, y = 1, z = 1; dim3(int a = 1, int b = 1, int c = 1) : x(a), y(b), z(c) {} };
-thread_local dim3 threadIdx, blockIdx, gridDim;
-typedef int hipError_t;
-typedef void *hipStream_t;
-const int hipSuccess = 0;
-inline int hipGetLastError() { return 0; }
-static std::barrier<> *wgBar;
-static std::barrier<> *waveBar[4];
-static double xbuf[4][64];
-static u32 ubuf[4][64];
-inline void __syncthreads() { wgBar->arrive_and_wait(); }
-inline int __popcll(u64 x) { return __builtin_popcountll(x); }
-inline int __ffs(unsigned x) { return __builtin_ffs((int)x); }
-inline u64 __ballot(bool p)
-{
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-    ubuf[w][l] = p;
-    waveBar[w]->arrive_and_wait();
-    u64 r = 0;
-    for (int i = 0; i < 64; i++) r |= (u64)(ubuf[w][i] & 1) << i;
-    waveBar[w]->arrive_and_wait();
-    return r;
-}
-inline double __longlong_as_double(long long v)
-{
-    double d;
-    memcpy(&d, &v, 8);
-    return d;
-}
-namespace kb {
-inline double d_inf() { return INFINITY; }
-inline double min_keep(double a, double b) { return b < a ? b : a; }
-inline u32 wave_min_u32(u32 x)
-{
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-    ubuf[w][l] = x;
-    waveBar[w]->arrive_and_wait();
-    u32 r = ubuf[w][0];
-    for (int i = 1; i < 64; i++) r = ubuf[w][i] < r ? ubuf[w][i] : r;
-    waveBar[w]->arrive_and_wait();
-    return r;
-}
-template <int CTRL, int ROWMASK>
-inline double dpp_f64(double x)  // the lane semantics of gfx950, as tests/cpp/frontier_host.cpp has them
-{
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63, row = l >> 4;
-    xbuf[w][l] = x;
-    waveBar[w]->arrive_and_wait();
-    double r = x;
-    if ((ROWMASK >> row) & 1) {
-        int src = l;
-        if (CTRL == 0xB1) src = l ^ 1;
-        else if (CTRL == 0x4E) src = l ^ 2;
-        else if (CTRL == 0x141) src = (l & ~7) | (7 - (l & 7));
-        else if (CTRL == 0x140) src = (l & ~15) | (15 - (l & 15));
-        else if (CTRL == 0x142) src = row * 16 - 1;
-        else if (CTRL == 0x143) src = 31;
-        else abort();
-        r = xbuf[w][src];
-    }
-    waveBar[w]->arrive_and_wait();
-    return r;
-}
-inline double wave_min_f64(double x)  // wave-uniform, as the device's
-{
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-    xbuf[w][l] = x;
-    waveBar[w]->arrive_and_wait();
-    double r = xbuf[w][0];
-    for (int i = 1; i < 64; i++) r = min_keep(r, xbuf[w][i]);
-    waveBar[w]->arrive_and_wait();
-    return r;
-}
-}
-// the workgroups of a launch one after another, on the same 256 threads (the last barrier: a workgroup's static LDS is the next one's)
-template <class K, class... A>
-void emu_launch(K kernel, dim3 grid, dim3 block, A... args)
-{
-    std::barrier<> wg(block.x), w0(64), w1(64), w2(64), w3(64);
-    wgBar = &wg; waveBar[0] = &w0; waveBar[1] = &w1; waveBar[2] = &w2; waveBar[3] = &w3;
-    std::vector<std::thread> th;
-    for (int t = 0; t < block.x; t++)
-        th.emplace_back([=]() {
-            threadIdx = dim3(t);
-            gridDim = grid;
-            for (int b = 0; b < grid.x; b++) {
-                blockIdx = dim3(b);
-                kernel(args...);
-                wgBar->arrive_and_wait();
-            }
-        });
-    for (auto &t : th) t.join();
-}
-#define hipLaunchKernelGGL(kernel, grid, block, lds, stream, ...) emu_launch(kernel, grid, block, __VA_ARGS__)
+#include "hip_on_host.h"
 #include "kbest_frontier.hip"
 #include "kbest_hybrid.hip"
 

@@ -6,82 +6,7 @@
 // usage: sample_host IN OUT
 //   IN: int n, mode, nSample, condition, grid; u32 sampleBase; u64 seed; per frame int nL, nM; u64 key; the (nL + nM) * nM doubles
 //   OUT: per frame double perm; int assign[nSample][nM]; double logProb[nSample]   (prefilled: -7 / -7.0)
-#include <barrier>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <thread>
-#include <vector>
-#define KBEST_WAVE_H
-#define __global__
-#define __device__
-#define __host__
-#define __forceinline__ inline
-#define __launch_bounds__(x)
-typedef unsigned long long u64;
-typedef unsigned u32;
-struct dim3 { int x = 1, y = 1, z = 1; dim3(int a = 1, int b = 1, int c = 1) : x(a), y(b), z(c) {} };
-thread_local dim3 threadIdx, blockIdx, gridDim, blockDim;
-typedef int hipError_t;
-typedef void *hipStream_t;
-const int hipSuccess = 0, hipFuncAttributeMaxDynamicSharedMemorySize = 0;
-inline int hipGetLastError() { return 0; }
-inline int hipGetDevice(int *d) { *d = 0; return 0; }
-inline int hipFuncSetAttribute(const void *, int, int) { return 0; }
-static std::barrier<> *wgBar;
-static std::barrier<> *waveBar[16];
-static double xbuf[16][64];
-static u32 ubuf[16][64];
-static unsigned char *hostLds;  // the workgroup's LDS: a heap block of exactly the planned size
-#define KB_DYNAMIC_LDS(name) unsigned char *name = hostLds
-inline void __syncthreads() { wgBar->arrive_and_wait(); }
-inline int __popcll(u64 x) { return __builtin_popcountll(x); }
-inline int __popc(unsigned x) { return __builtin_popcount(x); }
-inline int __ffs(unsigned x) { return __builtin_ffs((int)x); }
-inline double __longlong_as_double(long long v) { double d; memcpy(&d, &v, 8); return d; }
-inline u64 __ballot(bool p)
-{
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-    ubuf[w][l] = p;
-    waveBar[w]->arrive_and_wait();
-    u64 r = 0;
-    for (int i = 0; i < 64; i++) r |= (u64)(ubuf[w][i] & 1) << i;
-    waveBar[w]->arrive_and_wait();
-    return r;
-}
-namespace kb {
-inline double d_inf() { return INFINITY; }
-inline double min_keep(double a, double b) { return b < a ? b : a; }
-inline double wave_min_f64(double x)
-{
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-    xbuf[w][l] = x;
-    waveBar[w]->arrive_and_wait();
-    double r = xbuf[w][0];
-    for (int i = 1; i < 64; i++) r = min_keep(r, xbuf[w][i]);
-    waveBar[w]->arrive_and_wait();
-    return r;
-}
-}
-template <class K, class P>
-void emu_launch(K kernel, dim3 grid, dim3 block, int lds, P p)
-{
-    for (int b = 0; b < grid.x; b++) {
-        hostLds = new unsigned char[lds];
-        std::barrier<> wg(block.x);
-        std::vector<std::barrier<>*> wv;
-        for (int w = 0; w < block.x / 64; w++) { wv.push_back(new std::barrier<>(64)); waveBar[w] = wv.back(); }
-        wgBar = &wg;
-        std::vector<std::thread> th;
-        for (int t = 0; t < block.x; t++)
-            th.emplace_back([=]() { threadIdx = dim3(t); blockIdx = dim3(b); gridDim = grid; blockDim = block; kernel(p); });
-        for (auto &t : th) t.join();
-        for (auto *w : wv) delete w;
-        delete[] hostLds;
-    }
-}
-#define hipLaunchKernelGGL(kernel, grid, block, lds, stream, p) emu_launch(kernel, grid, block, lds, p)
+#include "hip_on_host.h"
 #include "kbest_sample.hip"
 
 int main(int argc, char **argv)

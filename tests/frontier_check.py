@@ -28,6 +28,7 @@ import cluster_check as cc
 import hybrid_check as hc
 import oracle_lib as ol
 import permanent_check as pc
+from probabilisticsemslam_amd import workloads as wl
 
 MAX_COLS = 64          # KBEST_FRONTIER_MAX_COLS
 MAX_WIDTH = 16         # KBEST_FRONTIER_MAX_WIDTH
@@ -279,3 +280,32 @@ def edge_clusters():
     out["width_17"] = two_rows_over(17)
     out["same_only_row"] = (flat([[1.0, 2.0], [np.inf, np.inf], [np.inf, np.inf], [np.inf, np.inf]]), 2, 2)
     return out
+
+
+# ---- the oversized clusters of the three scene families (tests/test_frontier_cpu.py, tests/test_frontier_sample_cpu.py) ------------
+FAMILIES = ((200, 40, 24, 24), (200, 60, 40, 30), (64, 200, 128, 60))  # README.md: F, nL, nM, side
+
+
+@functools.lru_cache(maxsize=None)
+def scene(F, nL, nM, side):
+    return wl.scene_frames(F, nL, nM, side)
+
+
+@functools.lru_cache(maxsize=None)
+def oversized(shape, condition):
+    """[(frame, a' of the cluster (R, m))] of every cluster of more than 16 columns of the family.  Computed once."""
+    _, nL, nM, _ = shape
+    out = []
+    for b, f in enumerate(scene(*shape)):
+        _, A = hc.gated_block(f, nL, nM, condition)
+        for cols, rows in cc.clusters_of(A)[0]:
+            if len(cols) > cc.MAX_SIZE:
+                out.append((b, A[np.ix_(rows, cols)]))
+    return out
+
+
+def raw_cluster(shape, frame, size):
+    """The one oversized cluster of that frame with a = permanent_check.to_probs(frame), column-scaled as the tier does."""
+    (A,) = [A for b, A in oversized(shape, False) if b == frame]
+    assert A.shape == size
+    return A / A.max(axis=0)

@@ -2,7 +2,6 @@
 sums where they are affordable, the column-scaled sums of the big-cluster tier on the scene clusters of 17, 18 and 20 measurements
 -- its invariances, the clusters of 22, 23 and 25 measurements that have no other exact answer, and the widths of every oversized
 cluster of the three scene families; the kernel source itself on the host under sanitizers; the library exports hybridFrontierProb and its C entries; without a GPU they fail loudly."""
-import functools
 import os
 import struct
 import subprocess
@@ -11,16 +10,13 @@ import numpy as np
 import pytest
 
 import bigcluster_check as bc
-import cluster_check as cc
 import frontier_check as fc
-import hybrid_check as hc
 import permanent_check as pc
 import probabilisticsemslam_amd as pk
 import range_lib as rl
-from probabilisticsemslam_amd import workloads as wl
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FAMILIES = ((200, 40, 24, 24), (200, 60, 40, 30), (64, 200, 128, 60))  # README.md: F, nL, nM, side
+FAMILIES, scene, oversized, raw_cluster = fc.FAMILIES, fc.scene, fc.oversized, fc.raw_cluster
 
 
 @pytest.fixture(scope="module")
@@ -28,31 +24,6 @@ def lib():
     if not os.path.exists(pk.lib_path()):
         subprocess.check_call(["make", "-C", os.path.join(ROOT, "probabilisticsemslam_amd", "csrc")])
     return pk.load_library()
-
-
-@functools.lru_cache(maxsize=None)
-def scene(F, nL, nM, side):
-    return wl.scene_frames(F, nL, nM, side)
-
-
-@functools.lru_cache(maxsize=None)
-def oversized(shape, condition):
-    """[(frame, a' of the cluster (R, m))] of every cluster of more than 16 columns of the family.  Computed once."""
-    _, nL, nM, _ = shape
-    out = []
-    for b, f in enumerate(scene(*shape)):
-        _, A = hc.gated_block(f, nL, nM, condition)
-        for cols, rows in cc.clusters_of(A)[0]:
-            if len(cols) > cc.MAX_SIZE:
-                out.append((b, A[np.ix_(rows, cols)]))
-    return out
-
-
-def raw_cluster(shape, frame, size):
-    """The one oversized cluster of that frame with a = permanent_check.to_probs(frame), column-scaled as the tier does."""
-    (A,) = [A for b, A in oversized(shape, False) if b == frame]
-    assert A.shape == size
-    return A / A.max(axis=0)
 
 
 def sparse_block(rng, R, C, density):

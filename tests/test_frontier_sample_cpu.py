@@ -152,19 +152,26 @@ def host_cases():
     return pick
 
 
-def test_kernel_source_on_the_host_under_sanitizers(tmp_path):
-    """tests/cpp/frontier_sample_host.cpp: the kernel's own source as 256 host threads per workgroup, AddressSanitizer and UBSan on,
-    heap blocks of exactly the planned sizes; 256 draws of three clusters equal the restatement (margin >= 1e-10 asserted first),
-    logTerm within 1e-12, log Z equal to the frontier tier's host program."""
+@pytest.fixture(scope="module")
+def exes(tmp_path_factory):
+    """The two host programs under AddressSanitizer and UBSan, built once for the module."""
+    tmp_path = tmp_path_factory.mktemp("host")
     (tmp_path / "hip").mkdir()
     (tmp_path / "hip" / "hip_runtime.h").write_text("")
     csrc = os.path.join(ROOT, "probabilisticsemslam_amd", "csrc")
-    exes = {}
+    out = {}
     for name in ("frontier_sample_host", "frontier_host"):
-        exes[name] = str(tmp_path / name)
+        out[name] = str(tmp_path / name)
         subprocess.check_call(["g++", "-std=c++20", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
                                "-I", str(tmp_path), "-I", os.path.join(ROOT, "include"), "-I", csrc, "-x", "c++",
-                               os.path.join(ROOT, "tests", "cpp", name + ".cpp"), "-o", exes[name], "-lpthread"])
+                               os.path.join(ROOT, "tests", "cpp", name + ".cpp"), "-o", out[name], "-lpthread"])
+    return out
+
+
+def test_kernel_source_on_the_host_under_sanitizers(tmp_path, exes):
+    """tests/cpp/frontier_sample_host.cpp: the kernel's own source as 256 host threads per workgroup, AddressSanitizer and UBSan on,
+    heap blocks of exactly the planned sizes; 256 draws of three clusters equal the restatement (margin >= 1e-10 asserted first),
+    logTerm within 1e-12, log Z equal to the frontier tier's host program."""
     cases, n_sample, seed, base = host_cases(), 256, fsc.SEED, 7
     want = [fsc.sample_cluster(o["block"], o["nL"], o["m"], o["keys"], n_sample, seed, b, base) for b, o in cases]
     assert all(w[3] == 1 and w[5] >= 1e-10 for w in want), [w[5] for w in want]
@@ -198,6 +205,52 @@ def test_kernel_source_on_the_host_under_sanitizers(tmp_path):
             assert np.array_equal(asg, w[0]), (b, o["m"])
             assert np.abs(lt - w[1]).max() <= 1e-12, (b, o["m"])
         assert at == len(buf)
+
+
+def shared_forward_cases():
+    """[(name, block, nL, m)]: the inputs of the two host tests, the smallest shapes of frontier_check (widths 16 and 17 among
+    them), and the shapes of tests/range_lib.py: hubs, two hubs, pair chains down to a declined one, clusters without a matching."""
+    import range_lib as rl
+    out = [(f"frame {b}, {o['m']} columns", o["block"], o["nL"], o["m"]) for b, o in host_cases()]
+    out += [(n, *fc.edge_clusters()[n]) for n in ("one_by_one", "two_by_one", "fewer_states_than_a_wave", "opens_and_closes_in_one_row",
+                                                  "band_of_24", "same_only_row", "width_16", "width_17")]
+    A = fc.raw_cluster(fc.FAMILIES[1], 89, (58, 25))
+    with np.errstate(divide="ignore"):
+        blk = np.full((58 + 25, 25), np.inf)
+        blk[:58] = -np.log(A)
+    out.append(("25 x 58", np.ascontiguousarray(blk.T).reshape(-1), 58, 25))
+    cases = [rl.hub(17, 36), rl.two_hubs(16, 41), rl.pair_chain(9, 41), rl.pair_chain(32, 20), rl.pair_chain(32, 25)]
+    cases += list(rl.no_matching().values())
+    return out + [(c.name, c.block, c.nLk, c.m) for c in cases]
+
+
+def test_tier_and_sampler_write_the_same_info_width_and_log_z(tmp_path, exes):
+    """The sampler restates the tier's plan and forward sweep: on the same clusters frontier_host and frontier_sample_host
+    write the same (info, width, logZ), byte for byte -- answered, without a matching, refused for its width,
+    declined below the range, and, the width-16 cluster alone in a slot one double below its need, refused for the slot."""
+    every, n_sample = shared_forward_cases(), 2
+    (wide,) = [c for c in every if c[0] == "width_16"]
+    need = fc.layers_bytes(fc.row_masks(fc.scaled_block(*wide[1:])[0]), wide[3]) // 8
+    seen = set()
+    for cases, args in ((every, []), ([wide], [str(need - 1), "1"])):
+        src, plain, tier, draw = (tmp_path / n for n in ("in.bin", "plain.bin", "tier.bin", "draw.bin"))
+        with open(src, "wb") as f, open(plain, "wb") as g:
+            f.write(struct.pack("iiQII", len(cases), n_sample, fsc.SEED, 0, 0))
+            g.write(struct.pack("i", len(cases)))
+            for k, (_, block, nL, m) in enumerate(cases):
+                blk = np.asarray(block, dtype=np.float64).tobytes()
+                f.write(struct.pack("iiQ", m, nL, k) + blk + np.arange(nL + m, dtype=np.int32).tobytes())
+                g.write(struct.pack("ii", m, nL) + blk)
+        subprocess.check_call([exes["frontier_host"], str(plain), str(tier)] + args)
+        subprocess.check_call([exes["frontier_sample_host"], str(src), str(draw)] + args)
+        tbuf, dbuf, tat, dat = tier.read_bytes(), draw.read_bytes(), 0, 0
+        for name, _, nL, m in cases:
+            assert tbuf[tat:tat + 16] == dbuf[dat:dat + 16], (name, struct.unpack_from("iid", tbuf, tat), struct.unpack_from("iid", dbuf, dat))
+            seen.add(struct.unpack_from("i", tbuf, tat)[0])
+            tat += 16 + 8 * m * (nL + 1)
+            dat += 16 + 4 * n_sample * m + 8 * n_sample
+        assert tat == len(tbuf) and dat == len(dbuf)
+    assert seen == {1, 0, fc.REFUSED_SLOT, fc.REFUSED_WIDTH, -5}, seen
 
 
 def test_frontier_sample_without_gpu_fails_loudly(lib):
