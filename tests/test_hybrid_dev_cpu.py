@@ -199,6 +199,19 @@ def test_more_frames_than_one_workgroup_of_the_gather(exe, tmp_path):
     check(index, items, res, 16, maxRawRow=NL + NM + 3, maxCol=NM + 5)
 
 
+def test_more_frames_than_the_grid_of_the_scatter(exe, tmp_path):
+    """4 100 frames (the sixteen in an order that does not repeat every 256 frames): the scatter's launcher caps its grid at 4 096
+    workgroups, so frames 4 096 .. 4 099 are the second pass of its frame loop, on the ctl, colOf and waveMin the first pass left;
+    the gather runs seventeen workgroups.  Raw costs at max_width = 5: workgroups 2 and 3 take a refused frame (10, 15: zeros, no
+    barrier between reading ctl and the end of the pass) and then an answered one (1, 6: colOf, and the block minimum through
+    waveMin) -- the pair of passes that the barrier at the end of the loop keeps apart."""
+    index = [(5 * j + j // 16 + 3 * (j // 256) + 7 * (j // 4096)) % 16 for j in range(4100)]
+    assert index[:240] != index[256:496] and index[:4] == [0, 5, 10, 15] and index[4096:] == [7, 12, 1, 6]
+    assert [restated(b, 5, False)[1] for b in (10, 15, 1, 6)] == [-1, -1, 0, 0]
+    items, res = run_host(exe, tmp_path, index, 5, condition=False)
+    check(index, items, res, 5, condition=False)
+
+
 @pytest.fixture(scope="module")
 def lib():
     if not os.path.exists(pk.lib_path()):
