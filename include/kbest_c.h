@@ -34,6 +34,8 @@
  *   kbest_hybrid_frontier_probs_batch_f64 / kbest_frontier_probs_f64_dev
  *   kbest_hybrid_frontier_probs_batch_f64_dev / kbest_reserve_hybrid_dev
  *        the exact association probabilities by gated clusters, for frames of up to 128 measurements (not in the reference)
+ *   kbest_quadric_map_probs_batch_f64 / kbest_quadric_map_probs_batch_f64_dev / kbest_reserve_quadric_map_dev
+ *        getAssignmentProbs (assignment.cpp:38-74, usePerm) from quadrics against a map of any size: the exact probabilities
  *   kbest_clustered_sample_assoc_batch_f64 / kbest_clustered_sample_assoc_batch_f64_dev
  *   kbest_hybrid_frontier_sample_assoc_batch_f64 / kbest_hybrid_frontier_sample_assoc_batch_f64_dev
  *        joint associations drawn from the exact posterior of such frames, one walk per cluster (not in the reference)
@@ -936,6 +938,76 @@ int kbest_hybrid_frontier_sample_assoc_batch_f64_dev(kbest_ctx *ctx, int B, int 
                                                      int32_t *d_assign, const int64_t *d_asgOff, double *d_logProb,
                                                      const int64_t *d_lpOff, double *d_logPerm, int32_t *d_method, int32_t *d_nOpen,
                                                      int32_t *d_nFrontier, int32_t *d_maxCluster, void *stream);
+/*
+ * Exact getAssignmentProbs from quadrics against a map of any size, on ONE stream (kbest_quadric_map.hip; the usePerm branch of
+ * getAssignmentProbs, assignment.cpp:38-74, from (mean, covariance) pairs).  The cost builder conditions while it builds: the raw
+ * (nL + nM) x nM block is never written.  conditionCosts (:450-494) keeps a landmark row only if some column has
+ * cost <= colMin[c] + 42, and colMin[c] <= gate, so of thousands of landmarks a few dozen remain.  Three passes recompute the
+ * costs (bits of kbest_quadric_costs_f64) rather than store them: per-tile column minima, the kept rows (ballots and counts, a
+ * prefix sum over the tile counts), the compact block.  No floating-point atomics, no workgroup waits for another, no host read,
+ * synchronise or allocation; stream order between the launches is the only synchronisation.  A frame's outputs are a function of
+ * the frame alone: not of the batch, the tile size, or the bounds of the launch.
+ *
+ * One map for the call: d_mapMean [nMap][3], d_mapCov [nMap][9] (row-major 3 x 3).  Frame b sees landmarks d_landOff[b] ..
+ * d_landOff[b] + d_nL[b] - 1 of it -- the caller keeps these windows inside the map, the entry cannot know nMap -- and has
+ * d_nM[b] measurements from d_measOff[b] in d_measMean / d_measCov.  Offsets are int64, counts int32.
+ *   d_nKeep[b]:   the landmark rows conditionCosts keeps -- the TRUE count, also where it exceeds maxKeep.
+ *   d_rowIdx:     [B][maxKeep] int32, frame-local landmark numbers, ascending: conditionCosts' rowIdx restricted to landmarks.
+ *   d_ccost:      (may be NULL: the context's) frame b's (nKeep + nM) x nM column-major compact block at
+ *                 b * (maxKeep + maxCol) * maxCol: the kept landmark rows in order, then ALL nM dummy rows, whether conditionCosts
+ *                 keeps them or not; each entry x <= colMin[c] + 42 ? x - colMin[c] : +inf, colMin over all nL + nM raw rows.
+ *   d_cprobs:     frame b's [nM][nKeep + 1] probabilities at b * maxCol * (maxKeep + 1).
+ *   d_probs:      (may be NULL) the dense [nM][nL + 1] slice at d_probOff[b]: EVERY element written, probs[m][rowIdx[l]] =
+ *                 cprobs[m][l], probs[m][nL] = cprobs[m][nKeep], every other element exactly 0.0.
+ *   d_logPerm, d_method (required), d_nOpen, d_nFrontier, d_maxCluster: what kbest_hybrid_frontier_probs_batch_f64_dev writes, which
+ *                 the entry calls on the compact blocks with condition = 0, maxRawRow = maxKeep + maxCol, on the same stream -- the
+ *                 bits of condition = 1 on the raw block, where that can be formed (the clustered kernel leaves all-zero rows out
+ *                 after the gate, x - colMin is the subtraction it does itself, the block minimum is 0 either way).
+ * Per-frame outcomes.  nKeep > maxKeep: method -1, d_nKeep[b] the true count (reserve again and call again), nothing of the frame
+ * written beyond its slices, its dense slice zeros.  nM < 1, nM > maxCol, nL < 0, nL > maxMap or a negative offset: method -1,
+ * and as for every frame that entry refuses nOpen and nFrontier 0, logPerm NaN; nKeep, rowIdx, maxCluster and every slice of the
+ * frame are not touched.  nL = 0 is no special case: every measurement gets 1.0 in slot 0.
+ * Limits: 1 <= maxCol <= 128, maxKeep >= 1, maxKeep + maxCol <= 1 024, 1 <= maxMap <= KBEST_QUADRIC_MAP_MAX, maxExact 0 .. 16
+ * (0 = 16), maxWidth 1 .. 16, gate not NaN -- else KBEST_ERR_BAD_ARG.  KBEST_QUADRIC_MAP_MAX is 2^22 landmarks a frame: row numbers
+ * are int32, every index into the map and the buffers is 64-bit, and the workgroup number b * ceil(maxMap / 256) + tile of a pass is
+ * an int32, which with 2^22 leaves room for 2^17 frames a call (more: KBEST_ERR_BAD_ARG).
+ * kbest_reserve_quadric_map_dev(ctx, B, maxMap, maxKeep, maxCol) sizes the tile minima, ballots, counts and offsets, the compact
+ * blocks, the d_sub work buffer of the hybrid entry, and calls kbest_reserve_hybrid_dev(B, maxKeep + maxCol, maxCol).  A
+ * reservation never shrinks: it holds the largest of each of the four numbers so far.  Without it, or with a call beyond it in any
+ * of the four: KBEST_ERR_NOT_RESERVED, nothing launched.  B = 0: KBEST_OK, nothing launched.  Asynchronous on `stream` (NULL: the
+ * context's); two calls on one stream need no synchronise between them.
+ */
+/* (a work space a captured launch holds does not grow: "WORK SPACES UNDER A CAPTURED LAUNCH" at kbest_reserve) */
+#define KBEST_QUADRIC_MAP_MAX (1 << 22)
+#define KBEST_QUADRIC_MAP_TILE 256 /* landmark rows per workgroup of the passes over the map (for tests of the tile edges) */
+int kbest_reserve_quadric_map_dev(kbest_ctx *ctx, int B, int maxMap, int maxKeep, int maxCol);
+int kbest_quadric_map_probs_batch_f64_dev(kbest_ctx *ctx, int B, int maxMap, int maxKeep, int maxCol, const double *d_mapMean,
+                                          const double *d_mapCov, const int64_t *d_landOff, const int32_t *d_nL,
+                                          const double *d_measMean, const double *d_measCov, const int64_t *d_measOff,
+                                          const int32_t *d_nM, double gate, int maxExact, int maxWidth, int32_t *d_nKeep,
+                                          int32_t *d_rowIdx, double *d_ccost, double *d_cprobs, double *d_probs,
+                                          const int64_t *d_probOff, double *d_logPerm, int32_t *d_method, int32_t *d_nOpen,
+                                          int32_t *d_nFrontier, int32_t *d_maxCluster, void *stream);
+/*
+ * The same from host buffers, synchronous, with the tiers the one-stream path lacks.  The map (mapMean [nMap][3], mapCov [nMap][9])
+ * is staged once; frame b sees landmarks landOff[b] .. + nL[b] of it (inside the map, else KBEST_ERR_BAD_ARG) and has nM[b]
+ * measurements, packed frame after frame in measMean / measCov.  The gate passes run first, nKeep is read back and the rest is
+ * sized from it.  A frame the one-stream path refuses (an open cluster the frontier tier does not take) goes on, when maxBig > 0
+ * or k >= 1, as its compact block -- one device-to-host copy -- through kbest_hybrid_frontier_probs_batch_f64(k, maxBig,
+ * condition = 0), so k >= 1 answers every gated frame and method 1 / 2 says so.  probs: the dense [nM][nL + 1] slices at
+ * probOff[b], zeros where nothing is assigned; logPerm, nOpen, nBig, nFrontier, maxCluster (each may be NULL), method and nKeep
+ * (required) as that entry's.  More than 1 024 - nM kept landmarks: method -1 for that frame (zeros, logPerm NaN, nKeep the true
+ * count), the call succeeds.  k >= 0, maxExact 0 .. 16, maxBig 0 .. 20, maxWidth 1 .. 16; nM > 128 or nL > KBEST_QUADRIC_MAP_MAX:
+ * KBEST_ERR_UNSUPPORTED.
+ */
+int kbest_quadric_map_probs_batch_f64(kbest_ctx *ctx, int B, int nMap, const double *mapMean, const double *mapCov, const int64_t *landOff,
+                                      const int32_t *nL, const int32_t *nM, const double *measMean, const double *measCov, double gate,
+                                      int k, int maxExact, int maxBig, int maxWidth, double *probs, const int64_t *probOff,
+                                      double *logPerm, int32_t *method, int32_t *nKeep, int32_t *nOpen, int32_t *nBig,
+                                      int32_t *nFrontier, int32_t *maxCluster);
+/* Diagnostic: registers, scratch bytes and static LDS bytes of the passes that compute costs (which = 0: minima, 1: kept rows,
+ * 2: compact block), for tools/bench_quadric_map.py. */
+int kbest_quadric_map_kernel_usage(int which, int32_t *vgprs, int32_t *scratchBytes, int32_t *ldsBytes);
 /* on = 1: the HOST-buffer association entries of this context (kbest_weights / assoc_probs / bruteforce / quadric_assoc) enumerate
  * their k best in the REFERENCE's own order of operations (the reference-order kernel, as KBEST_FLAG_REFERENCE_ORDER does for
  * kbest_batch_f64): where exactly equal gains straddle slot k the assignments that are weighed are the ones the reference's

@@ -21,6 +21,7 @@
 #include "kbest_c.h"
 #include "kbest_engine.h"
 #include "kbest_table_sample.h"
+#include "kbest_quadric_map.h"
 
 namespace kb {
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -231,6 +232,9 @@ struct kbest_ctx {
     std::vector<Block> cache;
     size_t cacheBytes = 0;  // all blocks, idle or in use
     std::mutex cacheMu;
+    DevBufRaw qmapBuf{"quadric map"};  // kbest_quadric_map_probs_batch_f64_dev: tile minima, column minima, ballots, counts, offsets, the
+                              // hybrid entry's d_sub and the compact blocks (kbest_reserve_quadric_map_dev; QmapLayout)
+    int qmapB = 0, qmapMap = 0, qmapKeep = 0, qmapCol = 0;  // ... the largest of each number reserved so far: what it is sized for
 };
 
 namespace {
@@ -852,6 +856,7 @@ int kbest_destroy(kbest_ctx *ctx)
     if (ctx->frLayers.p) (void)hipFree(ctx->frLayers.p);
     if (ctx->frPlan.p) (void)hipFree(ctx->frPlan.p);
     if (ctx->hybBuf.p) (void)hipFree(ctx->hybBuf.p);
+    if (ctx->qmapBuf.p) (void)hipFree(ctx->qmapBuf.p);
     if (ctx->hybSampBuf.p) (void)hipFree(ctx->hybSampBuf.p);
     if (ctx->relayFlags.p) (void)hipFree(ctx->relayFlags.p);
     if (ctx->lastEvent) (void)hipEventDestroy(ctx->lastEvent);
@@ -4667,6 +4672,364 @@ int kbest_hybrid_frontier_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *
     if (B == 0) return KBEST_OK;
     return hybrid_impl(ctx, "kbest_hybrid_frontier_probs_batch_f64", B, nL, nM, cost, costOff, condition, k, maxExact, maxBig, maxWidth,
                        probs, probOff, logPerm, method, nOpen, nBig, nFrontier, maxCluster);
+}
+
+// ---- exact getAssignmentProbs from quadrics against a map of any size (kbest_quadric_map.hip), then the one-stream hybrid path ----
+// Where everything lies in ctx->qmapBuf for a call of (B, maxMap, maxKeep, maxCol), in bytes; every part is 16-byte aligned.  Each
+// size grows with each of the four, so a call within the largest of each reserved so far fits.
+struct QmapLayout {
+    size_t tileMin, colMin, keep, tileCnt, tileOff, nLh, costOff, cprobOff, sub, ccost, total;
+    int nTiles, nKeepTiles;
+    long long costStride, cprobStride;  // doubles of a frame's compact block / compact probabilities
+};
+static QmapLayout qmap_layout(int B, int maxMap, int maxKeep, int maxCol)
+{
+    QmapLayout L;
+    size_t at = 0;
+    auto take = [&at](size_t bytes) { const size_t here = at; at += (bytes + 15) & ~(size_t)15; return here; };
+    const size_t b = (size_t)B;
+    L.nTiles = (maxMap + kb::QMAP_TILE - 1) / kb::QMAP_TILE;
+    L.nKeepTiles = (maxKeep + kb::QMAP_TILE - 1) / kb::QMAP_TILE;
+    L.costStride = (long long)(maxKeep + maxCol) * maxCol;
+    L.cprobStride = (long long)maxCol * (maxKeep + 1);
+    L.tileMin = take(b * (size_t)L.nTiles * (size_t)maxCol * 8);
+    L.colMin = take(b * (size_t)maxCol * 8);
+    L.keep = take(b * (size_t)L.nTiles * (kb::QMAP_TILE / 64) * 8);
+    L.tileCnt = take(b * (size_t)L.nTiles * 4);
+    L.tileOff = take(b * (size_t)L.nTiles * 4);
+    L.nLh = take(b * 4);
+    L.costOff = take(b * 8);
+    L.cprobOff = take(b * 8);
+    L.sub = take(b * (size_t)L.costStride * 8);
+    L.ccost = take(b * (size_t)L.costStride * 8);
+    L.total = at;
+    return L;
+}
+
+static const char QMAP_ARGS_TEXT[] = ": bad argument (B >= 0, 1 <= maxCol <= 128, maxKeep >= 1, maxKeep + maxCol <= 1024, "
+                                     "1 <= maxMap <= KBEST_QUADRIC_MAP_MAX, B * ceil(maxMap / 256) < 2^31)";
+static int qmap_check(kbest_ctx *ctx, const char *who, int B, int maxMap, int maxKeep, int maxCol)
+{
+    if (B < 0 || maxCol < 1 || maxCol > kb::QMAP_MAX_COLS || maxKeep < 1 || maxKeep + maxCol > KBEST_MAX_DIM_WIDE || maxMap < 1 ||
+        maxMap > KBEST_QUADRIC_MAP_MAX || (long long)B * ((maxMap + kb::QMAP_TILE - 1) / kb::QMAP_TILE) > 0x7fffffffLL)
+        return fail(ctx, KBEST_ERR_BAD_ARG, (std::string(who) + QMAP_ARGS_TEXT).c_str());
+    return KBEST_OK;
+}
+
+// workgroups per frame of the expansion: a grid-stride loop over the dense slice, at most 1 024 of them a frame
+static int qmap_expand_tiles(int B, int maxMap, int maxCol)
+{
+    long long t = ((long long)maxCol * ((long long)maxMap + 1) + kb::QMAP_TILE - 1) / kb::QMAP_TILE;
+    if (t > 1024) t = 1024;
+    while (t > 1 && t * B > 0x7fffffffLL) t >>= 1;
+    return (int)t;
+}
+
+static void qmap_params(kb::QuadricMapParams &p, kbest_ctx *ctx, const QmapLayout &L, int B, int maxMap, int maxKeep, int maxCol,
+                        const double *d_mapMean, const double *d_mapCov, const int64_t *d_landOff, const int32_t *d_nL,
+                        const double *d_measMean, const double *d_measCov, const int64_t *d_measOff, const int32_t *d_nM, double gate,
+                        int32_t *d_nKeep, int32_t *d_rowIdx, double *d_ccost)
+{
+    unsigned char *h8 = static_cast<unsigned char *>(ctx->qmapBuf.p);
+    p.mapMean = d_mapMean;
+    p.mapCov = d_mapCov;
+    p.measMean = d_measMean;
+    p.measCov = d_measCov;
+    p.landOff = reinterpret_cast<const long long *>(d_landOff);
+    p.measOff = reinterpret_cast<const long long *>(d_measOff);
+    p.nL = d_nL;
+    p.nM = d_nM;
+    p.gate = gate;
+    p.B = B;
+    p.maxMap = maxMap;
+    p.maxKeep = maxKeep;
+    p.maxCol = maxCol;
+    p.nTiles = L.nTiles;
+    p.nKeepTiles = L.nKeepTiles;
+    p.nExpandTiles = qmap_expand_tiles(B, maxMap, maxCol);
+    p.tileMin = reinterpret_cast<double *>(h8 + L.tileMin);
+    p.colMin = reinterpret_cast<double *>(h8 + L.colMin);
+    p.keep = reinterpret_cast<kb::u64 *>(h8 + L.keep);
+    p.tileCnt = reinterpret_cast<int *>(h8 + L.tileCnt);
+    p.tileOff = reinterpret_cast<int *>(h8 + L.tileOff);
+    p.nKeep = d_nKeep;
+    p.nLh = reinterpret_cast<int *>(h8 + L.nLh);
+    p.costOff = reinterpret_cast<long long *>(h8 + L.costOff);
+    p.cprobOff = reinterpret_cast<long long *>(h8 + L.cprobOff);
+    p.rowIdx = d_rowIdx;
+    p.ccost = d_ccost ? d_ccost : reinterpret_cast<double *>(h8 + L.ccost);
+    p.cprobs = nullptr;
+    p.probs = nullptr;
+    p.probOff = nullptr;
+}
+
+static bool qmap_reserved(const kbest_ctx *ctx, int B, int maxMap, int maxKeep, int maxCol)
+{
+    return ctx->qmapBuf.p && B <= ctx->qmapB && maxMap <= ctx->qmapMap && maxKeep <= ctx->qmapKeep && maxCol <= ctx->qmapCol;
+}
+
+int kbest_reserve_quadric_map_dev(kbest_ctx *ctx, int B, int maxMap, int maxKeep, int maxCol)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    KB_TRY(qmap_check(ctx, "kbest_reserve_quadric_map_dev", B, maxMap, maxKeep, maxCol));
+    if (B == 0) return KBEST_OK;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // sized for the largest of each of the four numbers so far: a reservation never shrinks (the four together need not be a legal
+    // call; every legal call within them fits)
+    const int nb = std::max(B, ctx->qmapB), nm = std::max(maxMap, ctx->qmapMap), nk = std::max(maxKeep, ctx->qmapKeep),
+              nc = std::max(maxCol, ctx->qmapCol);
+    KB_TRY(kbest_reserve_hybrid_dev(ctx, nb, std::min(nk + nc, (int)KBEST_MAX_DIM_WIDE), nc));
+    KB_TRY(raw_reserve(ctx, ctx->qmapBuf, qmap_layout(nb, nm, nk, nc).total));
+    ctx->qmapB = nb;
+    ctx->qmapMap = nm;
+    ctx->qmapKeep = nk;
+    ctx->qmapCol = nc;
+    return KBEST_OK;
+}
+
+int kbest_quadric_map_probs_batch_f64_dev(kbest_ctx *ctx, int B, int maxMap, int maxKeep, int maxCol, const double *d_mapMean,
+                                          const double *d_mapCov, const int64_t *d_landOff, const int32_t *d_nL,
+                                          const double *d_measMean, const double *d_measCov, const int64_t *d_measOff,
+                                          const int32_t *d_nM, double gate, int maxExact, int maxWidth, int32_t *d_nKeep,
+                                          int32_t *d_rowIdx, double *d_ccost, double *d_cprobs, double *d_probs,
+                                          const int64_t *d_probOff, double *d_logPerm, int32_t *d_method, int32_t *d_nOpen,
+                                          int32_t *d_nFrontier, int32_t *d_maxCluster, void *stream)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    const char *who = "kbest_quadric_map_probs_batch_f64_dev";
+    KB_TRY(qmap_check(ctx, who, B, maxMap, maxKeep, maxCol));
+    if (maxExact < 0 || maxExact > KBEST_CLUSTER_MAX_SIZE || maxWidth < 1 || maxWidth > KBEST_FRONTIER_MAX_WIDTH || gate != gate)
+        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_quadric_map_probs_batch_f64_dev: bad argument (maxExact 0 .. 16, maxWidth 1 .. 16, gate not NaN)");
+    if (B == 0) return KBEST_OK;
+    if (!d_mapMean || !d_mapCov || !d_landOff || !d_nL || !d_measMean || !d_measCov || !d_measOff || !d_nM || !d_nKeep || !d_rowIdx ||
+        !d_cprobs || !d_method || (d_probs && !d_probOff))
+        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_quadric_map_probs_batch_f64_dev: bad argument (a required pointer is NULL)");
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // everything is checked before anything is launched: this entry's work space, and what the hybrid entry will ask for
+    HybridDevPlan d;
+    KB_TRY(hybrid_dev_plan(ctx, who, B, maxKeep + maxCol, maxCol, d));
+    if (!qmap_reserved(ctx, B, maxMap, maxKeep, maxCol) || !d.reserved)
+        return fail(ctx, KBEST_ERR_NOT_RESERVED, "kbest_quadric_map_probs_batch_f64_dev: call kbest_reserve_quadric_map_dev first");
+    const QmapLayout L = qmap_layout(B, maxMap, maxKeep, maxCol);
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    KB_TRY(order_behind_last(ctx, s));
+    const Launched mark{ctx, s};
+    hold_if_capturing(s, {&ctx->qmapBuf});
+    kb::QuadricMapParams p;
+    qmap_params(p, ctx, L, B, maxMap, maxKeep, maxCol, d_mapMean, d_mapCov, d_landOff, d_nL, d_measMean, d_measCov, d_measOff, d_nM, gate,
+                d_nKeep, d_rowIdx, d_ccost);
+    hipError_t e = kb::launch_quadric_map_gate(p, s);
+    if (e == hipSuccess) e = kb::launch_quadric_map_fill(p, s);
+    if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "quadric map kernel launch", e);
+    // the compact blocks are conditioned already: condition = 0, nL = the kept rows (-1: the frame is refused and not touched)
+    unsigned char *h8 = static_cast<unsigned char *>(ctx->qmapBuf.p);
+    KB_TRY(kbest_hybrid_frontier_probs_batch_f64_dev(ctx, B, maxKeep + maxCol, maxCol, p.nLh, d_nM, p.ccost,
+                                                     reinterpret_cast<const int64_t *>(p.costOff), 0, maxExact, maxWidth,
+                                                     reinterpret_cast<double *>(h8 + L.sub), d_cprobs,
+                                                     reinterpret_cast<const int64_t *>(p.cprobOff), d_logPerm, d_method, d_nOpen,
+                                                     d_nFrontier, d_maxCluster, stream));
+    if (d_probs) {
+        p.cprobs = d_cprobs;
+        p.probs = d_probs;
+        p.probOff = reinterpret_cast<const long long *>(d_probOff);
+        e = kb::launch_quadric_map_expand(p, s);
+        if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "quadric map expansion launch", e);
+    }
+    return KBEST_OK;
+}
+
+int kbest_quadric_map_kernel_usage(int which, int32_t *vgprs, int32_t *scratchBytes, int32_t *ldsBytes)
+{
+    int v = 0, sc = 0, l = 0;
+    if (which < 0 || which > 2 || !vgprs || !scratchBytes || !ldsBytes) return KBEST_ERR_BAD_ARG;
+    if (kb::quadric_map_kernel_usage(which, &v, &sc, &l) != hipSuccess) return KBEST_ERR_HIP;
+    *vgprs = v;
+    *scratchBytes = sc;
+    *ldsBytes = l;
+    return KBEST_OK;
+}
+
+// The synchronous entry: the map staged once, the gate passes, nKeep read back, the rest sized from that; the frames the one-stream
+// path refuses go on as their compact blocks through kbest_hybrid_frontier_probs_batch_f64(k, maxBig, condition = 0).  Frames run
+// in rounds so that every frame with nKeep <= 1 024 - nM is taken whatever else the batch holds: a round's bounds are the largest
+// nM of the frames still waiting and the largest nKeep that fits beside it (the frame with that nM always fits: one round, almost
+// always).
+int kbest_quadric_map_probs_batch_f64(kbest_ctx *ctx, int B, int nMap, const double *mapMean, const double *mapCov, const int64_t *landOff,
+                                      const int32_t *nL, const int32_t *nM, const double *measMean, const double *measCov, double gate,
+                                      int k, int maxExact, int maxBig, int maxWidth, double *probs, const int64_t *probOff,
+                                      double *logPerm, int32_t *method, int32_t *nKeep, int32_t *nOpen, int32_t *nBig,
+                                      int32_t *nFrontier, int32_t *maxCluster)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    const char *who = "kbest_quadric_map_probs_batch_f64";
+    if (B < 0 || nMap < 0 || k < 0 || maxExact < 0 || maxExact > KBEST_CLUSTER_MAX_SIZE || maxBig < 0 || maxBig > KBEST_BIGCLUSTER_MAX_SIZE ||
+        maxWidth < 1 || maxWidth > KBEST_FRONTIER_MAX_WIDTH || gate != gate ||
+        (B > 0 && (!landOff || !nL || !nM || !measMean || !measCov || !probs || !probOff || !method || !nKeep)) ||
+        (nMap > 0 && (!mapMean || !mapCov)))
+        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_quadric_map_probs_batch_f64: bad argument (k >= 0, maxExact 0 .. 16, maxBig 0 .. 20, "
+                                            "maxWidth 1 .. 16, gate not NaN)");
+    if (B == 0) return KBEST_OK;
+    int maxMap = 1, maxColAll = 1;
+    std::vector<int64_t> measOff(B);
+    int64_t nMeas = 0;
+    for (int b = 0; b < B; b++) {
+        if (nM[b] < 1 || nL[b] < 0 || landOff[b] < 0 || landOff[b] + nL[b] > nMap || probOff[b] < 0)
+            return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_quadric_map_probs_batch_f64: a frame with nM < 1, nL < 0, a window beyond the map or a negative offset");
+        if (nM[b] > kb::QMAP_MAX_COLS) return fail(ctx, KBEST_ERR_UNSUPPORTED, (std::string(who) + CLUSTER_COLS_TEXT).c_str());
+        if (nL[b] > KBEST_QUADRIC_MAP_MAX) return fail(ctx, KBEST_ERR_UNSUPPORTED, "kbest_quadric_map_probs_batch_f64: more than KBEST_QUADRIC_MAP_MAX landmarks in a frame");
+        maxMap = std::max(maxMap, nL[b]);
+        maxColAll = std::max(maxColAll, nM[b]);
+        measOff[b] = nMeas;
+        nMeas += nM[b];
+    }
+    KB_TRY(qmap_check(ctx, who, B, maxMap, 1, maxColAll));
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    // meta: landOff[B] | measOff[B] (int64) | nL[B] | nM[B] | nKeep[B] | method | nOpen | nFrontier | maxCluster (int32) | logPerm[B]
+    DevBuf dMap, dMeas, dMeta;
+    hipError_t e;
+    const size_t mapN = (size_t)std::max(nMap, 1);
+    if ((e = dMap.alloc(ctx, mapN * 12 * 8)) != hipSuccess || (e = dMeas.alloc(ctx, (size_t)nMeas * 12 * 8)) != hipSuccess ||
+        (e = dMeta.alloc(ctx, (size_t)B * 64)) != hipSuccess)
+        return fail(ctx, KBEST_ERR_NOMEM, "kbest_quadric_map_probs_batch_f64: device buffers", e);
+    double *d_mapMean = dMap.as<double>(), *d_mapCov = d_mapMean + mapN * 3;
+    double *d_measMean = dMeas.as<double>(), *d_measCov = d_measMean + (size_t)nMeas * 3;
+    if (nMap > 0) {  // the map goes up once, whatever the number of frames
+        HIP_TRY(ctx, hipMemcpy(d_mapMean, mapMean, (size_t)nMap * 3 * 8, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(d_mapCov, mapCov, (size_t)nMap * 9 * 8, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(ctx, hipMemcpy(d_measMean, measMean, (size_t)nMeas * 3 * 8, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(d_measCov, measCov, (size_t)nMeas * 9 * 8, hipMemcpyHostToDevice));
+    int64_t *d_landOff = dMeta.as<int64_t>(), *d_measOff = d_landOff + B;
+    int32_t *d_i = reinterpret_cast<int32_t *>(d_measOff + B);
+    int32_t *d_nL = d_i, *d_nM = d_i + B, *d_nKeep = d_i + 2 * (size_t)B, *d_method = d_i + 3 * (size_t)B, *d_nOpen = d_i + 4 * (size_t)B,
+            *d_nFrontier = d_i + 5 * (size_t)B, *d_maxCluster = d_i + 6 * (size_t)B;
+    double *d_logPerm = reinterpret_cast<double *>(d_i + 8 * (size_t)B);
+    auto put_frames = [&](const std::vector<int> &idx) -> int {
+        const size_t n = idx.size();
+        std::vector<int64_t> o(2 * n);
+        std::vector<int32_t> c(2 * n);
+        for (size_t j = 0; j < n; j++) { o[j] = landOff[idx[j]]; o[n + j] = measOff[idx[j]]; c[j] = nL[idx[j]]; c[n + j] = nM[idx[j]]; }
+        HIP_TRY(ctx, hipMemcpy(d_landOff, o.data(), n * 8, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(d_measOff, o.data() + n, n * 8, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(d_nL, c.data(), n * 4, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(d_nM, c.data() + n, n * 4, hipMemcpyHostToDevice));
+        return KBEST_OK;
+    };
+    // 1. the gate passes on the whole batch: nKeep
+    std::vector<int> all(B);
+    for (int b = 0; b < B; b++) all[b] = b;
+    KB_TRY(put_frames(all));
+    KB_TRY(kbest_reserve_quadric_map_dev(ctx, B, maxMap, 1, maxColAll));
+    {
+        const QmapLayout L = qmap_layout(B, maxMap, 1, maxColAll);
+        kb::QuadricMapParams p;
+        qmap_params(p, ctx, L, B, maxMap, 1, maxColAll, d_mapMean, d_mapCov, d_landOff, d_nL, d_measMean, d_measCov, d_measOff, d_nM, gate,
+                    d_nKeep, nullptr, nullptr);
+        KB_TRY(order_behind_last(ctx, s));
+        if ((e = kb::launch_quadric_map_gate(p, s)) != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "quadric map kernel launch", e);
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+        HIP_TRY(ctx, hipMemcpy(nKeep, d_nKeep, (size_t)B * 4, hipMemcpyDeviceToHost));
+    }
+    // 2. every output as a refused frame has it; the frames that fit wait for a round
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    std::vector<int> waiting;
+    for (int b = 0; b < B; b++) {
+        memset(probs + probOff[b], 0, (size_t)nM[b] * ((size_t)nL[b] + 1) * 8);
+        method[b] = -1;
+        if (logPerm) logPerm[b] = nan;
+        if (nOpen) nOpen[b] = 0;
+        if (nBig) nBig[b] = 0;
+        if (nFrontier) nFrontier[b] = 0;
+        if (maxCluster) maxCluster[b] = 0;
+        if (nKeep[b] <= KBEST_MAX_DIM_WIDE - nM[b]) waiting.push_back(b);
+    }
+    while (!waiting.empty()) {
+        int maxCol = 1, maxKeep = 1;
+        for (int b : waiting) maxCol = std::max(maxCol, nM[b]);
+        for (int b : waiting) if (nKeep[b] + maxCol <= KBEST_MAX_DIM_WIDE) maxKeep = std::max(maxKeep, nKeep[b]);
+        std::vector<int> idx, rest;
+        for (int b : waiting) (nKeep[b] <= maxKeep ? idx : rest).push_back(b);
+        waiting.swap(rest);
+        const int n = (int)idx.size();
+        KB_TRY(put_frames(idx));
+        KB_TRY(kbest_reserve_quadric_map_dev(ctx, n, maxMap, maxKeep, maxCol));
+        const QmapLayout L = qmap_layout(n, maxMap, maxKeep, maxCol);
+        DevBuf dRows, dCost, dCp;
+        if ((e = dRows.alloc(ctx, (size_t)n * maxKeep * 4)) != hipSuccess || (e = dCost.alloc(ctx, (size_t)n * L.costStride * 8)) != hipSuccess ||
+            (e = dCp.alloc(ctx, (size_t)n * L.cprobStride * 8)) != hipSuccess)
+            return fail(ctx, KBEST_ERR_NOMEM, "kbest_quadric_map_probs_batch_f64: device buffers", e);
+        KB_TRY(kbest_quadric_map_probs_batch_f64_dev(ctx, n, maxMap, maxKeep, maxCol, d_mapMean, d_mapCov, d_landOff, d_nL, d_measMean,
+                                                     d_measCov, d_measOff, d_nM, gate, maxExact, maxWidth, d_nKeep, dRows.as<int32_t>(),
+                                                     dCost.as<double>(), dCp.as<double>(), nullptr, nullptr, d_logPerm, d_method, d_nOpen,
+                                                     d_nFrontier, d_maxCluster, nullptr));
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+        std::vector<int32_t> rows((size_t)n * maxKeep), ints((size_t)n * 4);
+        std::vector<double> cp((size_t)n * L.cprobStride), lp(n);
+        HIP_TRY(ctx, hipMemcpy(rows.data(), dRows.p, rows.size() * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(cp.data(), dCp.p, cp.size() * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(lp.data(), d_logPerm, (size_t)n * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(ints.data(), d_method, (size_t)n * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(ints.data() + n, d_nOpen, (size_t)n * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(ints.data() + 2 * (size_t)n, d_nFrontier, (size_t)n * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(ints.data() + 3 * (size_t)n, d_maxCluster, (size_t)n * 4, hipMemcpyDeviceToHost));
+        std::vector<int32_t> big(n, 0);
+        // the frames with an open cluster the frontier tier did not take, where another tier could: one copy of the compact blocks
+        std::vector<int> fwd;
+        for (int j = 0; j < n; j++)
+            if (ints[j] == -1 && (k >= 1 || maxBig > 0)) fwd.push_back(j);
+        if (!fwd.empty()) {
+            std::vector<double> cc((size_t)n * L.costStride);
+            HIP_TRY(ctx, hipMemcpy(cc.data(), dCost.p, cc.size() * 8, hipMemcpyDeviceToHost));
+            dCost.release();
+            dCp.release();
+            dRows.release();
+            const size_t nf = fwd.size();
+            std::vector<int32_t> fL(nf), fM(nf), fi(5 * nf);
+            std::vector<int64_t> fco(nf), fpo(nf);
+            std::vector<double> flp(nf);
+            for (size_t i = 0; i < nf; i++) {
+                const int j = fwd[i];
+                fL[i] = nKeep[idx[j]];
+                fM[i] = nM[idx[j]];
+                fco[i] = (int64_t)j * L.costStride;
+                fpo[i] = (int64_t)j * L.cprobStride;
+            }
+            KB_TRY(kbest_hybrid_frontier_probs_batch_f64(ctx, (int)nf, fL.data(), fM.data(), cc.data(), fco.data(), 0, k, maxExact, maxBig,
+                                                         maxWidth, cp.data(), fpo.data(), flp.data(), fi.data(), fi.data() + nf,
+                                                         fi.data() + 2 * nf, fi.data() + 3 * nf, fi.data() + 4 * nf));
+            for (size_t i = 0; i < nf; i++) {
+                const int j = fwd[i];
+                ints[j] = fi[i];
+                ints[n + j] = fi[nf + i];
+                big[j] = fi[2 * nf + i];
+                ints[3 * (size_t)n + j] = fi[3 * nf + i];
+                ints[2 * (size_t)n + j] = fi[4 * nf + i];
+                lp[j] = flp[i];
+            }
+        }
+        for (int j = 0; j < n; j++) {
+            const int b = idx[j], nk = nKeep[b];
+            const size_t w = (size_t)nL[b] + 1;
+            double *out = probs + probOff[b];
+            const double *c = cp.data() + (size_t)j * L.cprobStride;
+            const int32_t *r = rows.data() + (size_t)j * maxKeep;
+            for (int m = 0; m < nM[b]; m++) {
+                for (int l = 0; l < nk; l++) out[m * w + r[l]] = c[(size_t)m * (nk + 1) + l];
+                out[m * w + nL[b]] = c[(size_t)m * (nk + 1) + nk];
+            }
+            method[b] = ints[j];
+            if (nOpen) nOpen[b] = ints[n + j];
+            if (nFrontier) nFrontier[b] = ints[2 * (size_t)n + j];
+            if (maxCluster) maxCluster[b] = ints[3 * (size_t)n + j];
+            if (nBig) nBig[b] = big[j];
+            if (logPerm) logPerm[b] = lp[j];
+        }
+    }
+    return KBEST_OK;
 }
 
 // ---- whole hypotheses for the frames of kbest_hybrid_frontier_probs_batch_f64(k = 0, maxBig = 0): the small clusters by the

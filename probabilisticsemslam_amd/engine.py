@@ -37,6 +37,8 @@ KBEST_BIGCLUSTER_MAX_SIZE = 20  # ... and per cluster of the big-cluster tier (o
 KBEST_FRONTIER_MAX_COLS = 64    # ... and per cluster of the frontier tier (one workgroup per cluster)
 KBEST_FRONTIER_MAX_WIDTH = 16   # ... whose rows, in the greedy order, keep at most this many columns open
 KBEST_FRONTIER_SLOT = 4 << 20   # ... and whose layers fit this many bytes
+KBEST_QUADRIC_MAP_MAX = 1 << 22  # landmarks a frame of the quadric-map entries sees at the most
+KBEST_QUADRIC_MAP_TILE = 256     # ... and landmark rows per workgroup of their passes over the map
 
 # every symbol include/kbest_c.h declares
 C_ABI_SYMBOLS = (
@@ -68,6 +70,8 @@ C_ABI_SYMBOLS = (
     "kbest_reserve_hybrid_sample_dev", "kbest_hybrid_frontier_sample_assoc_batch_f64_dev",
     "kbest_table_sample_f64_dev", "kbest_hybrid_sample_assoc_batch_f64",
     "kbest_bb_costs_f64",
+    "kbest_reserve_quadric_map_dev", "kbest_quadric_map_probs_batch_f64_dev", "kbest_quadric_map_probs_batch_f64",
+    "kbest_quadric_map_kernel_usage",
 )
 KBEST_MULTI_STAMPS = 6
 KBEST_MULTI_BATCH, KBEST_MULTI_SUBTREE = 0, 1
@@ -237,6 +241,14 @@ def load_library():
         lib.kbest_hybrid_sample_assoc_batch_f64.argtypes = [vp, C.c_int, i32p, i32p, dp, i64p, C.c_int, C.c_int, C.c_int, C.c_int,
                                                             C.c_int, C.c_uint64, C.c_uint32, i64p, i32p, i64p, dp, i64p, dp, i32p,
                                                             i32p, i32p, i32p, i32p]
+    if hasattr(lib, "kbest_quadric_map_probs_batch_f64_dev"):
+        lib.kbest_reserve_quadric_map_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
+        lib.kbest_quadric_map_probs_batch_f64_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, i64p, i32p, dp, dp, i64p,
+                                                              i32p, C.c_double, C.c_int, C.c_int, i32p, i32p, dp, dp, dp, i64p, dp,
+                                                              i32p, i32p, i32p, i32p, vp]
+        lib.kbest_quadric_map_probs_batch_f64.argtypes = [vp, C.c_int, C.c_int, dp, dp, i64p, i32p, i32p, dp, dp, C.c_double, C.c_int,
+                                                          C.c_int, C.c_int, C.c_int, dp, i64p, dp, i32p, i32p, i32p, i32p, i32p, i32p]
+        lib.kbest_quadric_map_kernel_usage.argtypes = [C.c_int, i32p, i32p, i32p]
     lib.kbest_register_host_buffer.argtypes = [vp, vp, C.c_size_t]
     lib.kbest_unregister_host_buffer.argtypes = [vp, vp]
     _lib = lib
@@ -803,6 +815,59 @@ class KBestEngine:
                                                                  _ptr(mm), _ptr(mc), float(gate), k, _ptr(probs), _ptr(poff),
                                                                  _ptr(nf)))
         return [probs[poff[b]: poff[b] + psizes[b]].reshape(int(nM[b]), int(nL[b]) + 1) for b in range(len(frames))], nf
+
+    def quadric_map_probs(self, map_mean, map_cov, frames, gate, k=0, max_exact=16, max_big=20, max_width=16):
+        """getAssignmentProbs' exact branch from quadrics against one map of any size (kbest_quadric_map_probs_batch_f64).
+        map_mean (nMap, 3), map_cov (nMap, 3, 3); frames: list of (landOff, nL, measMean (nM, 3), measCov (nM, 3, 3)) -- frame b
+        sees landmarks landOff .. landOff + nL of the map.  The cost builder conditions while it builds (the raw block is never
+        formed); the compact blocks go through the one-stream exact path, and what that refuses through
+        hybrid_frontier_probs(k, max_big, condition=False) when k >= 1 or max_big > 0.  Returns (list of dense [nM, nL+1] arrays,
+        method[B], nKeep[B]: landmark rows conditionCosts keeps, nOpen[B], nBig[B], nFrontier[B], maxCluster[B], logPerm[B])."""
+        B = len(frames)
+        mm = np.ascontiguousarray(np.asarray(map_mean, np.float64).reshape(-1, 3))
+        mc = np.ascontiguousarray(np.asarray(map_cov, np.float64).reshape(-1, 9))
+        if len(mm) != len(mc):
+            raise KBestError("quadric_map_probs: map_mean and map_cov differ in length")
+        landOff = np.array([f[0] for f in frames], np.int64)
+        nL = np.array([f[1] for f in frames], np.int32)
+        nM = np.array([len(f[2]) for f in frames], np.int32)
+        cat = lambda i, w: np.ascontiguousarray(np.concatenate([np.zeros((0, w))] + [np.asarray(f[i], np.float64).reshape(-1, w) for f in frames]))  # noqa: E731
+        zm, zc = cat(2, 3), cat(3, 9)
+        psizes = nM.astype(np.int64) * (nL.astype(np.int64) + 1)
+        probOff = np.zeros(B, np.int64)
+        probOff[1:] = np.cumsum(psizes)[:-1]
+        probs = np.zeros(int(psizes.sum()), np.float64)
+        ints = np.zeros((6, max(B, 1)), np.int32)  # method | nKeep | nOpen | nBig | nFrontier | maxCluster
+        logPerm = np.zeros(max(B, 1), np.float64)
+        self._check(self.lib.kbest_quadric_map_probs_batch_f64(
+            self.ctx, B, len(mm), _ptr(mm), _ptr(mc), _ptr(landOff), _ptr(nL), _ptr(nM), _ptr(zm), _ptr(zc), float(gate), int(k),
+            int(max_exact), int(max_big), int(max_width), _ptr(probs), _ptr(probOff), _ptr(logPerm), _ptr(ints[0]), _ptr(ints[1]),
+            _ptr(ints[2]), _ptr(ints[3]), _ptr(ints[4]), _ptr(ints[5])))
+        out = _split_probs(probs, probOff, psizes, nL, nM)
+        return (out,) + tuple(ints[i, :B].copy() for i in range(6)) + (logPerm[:B].copy(),)
+
+    def reserve_quadric_map_dev(self, B, maxMap, maxKeep, maxCol):
+        """kbest_reserve_quadric_map_dev: everything quadric_map_probs_dev needs besides the caller's buffers, sized from the four
+        numbers alone (a reservation never shrinks)."""
+        self._check(self.lib.kbest_reserve_quadric_map_dev(self.ctx, int(B), int(maxMap), int(maxKeep), int(maxCol)))
+
+    def quadric_map_probs_dev(self, B, maxMap, maxKeep, maxCol, d_mapMean, d_mapCov, d_landOff, d_nL, d_measMean, d_measCov, d_measOff,
+                              d_nM, gate, d_nKeep, d_rowIdx, d_cprobs, d_method, d_ccost=None, d_probs=None, d_probOff=None,
+                              d_logPerm=None, d_nOpen=None, d_nFrontier=None, d_maxCluster=None, max_exact=16, max_width=16,
+                              stream=None, reserve=True):
+        """kbest_quadric_map_probs_batch_f64_dev on torch CUDA tensors (or raw addresses), asynchronous on `stream` (a raw
+        hipStream_t integer): from quadrics against one resident map to the exact probabilities without a host read, a synchronise
+        or an allocation.  d_landOff, d_measOff, d_probOff int64 [B]; d_nL, d_nM int32 [B]; d_nKeep int32 [B]; d_rowIdx int32
+        [B][maxKeep]; d_ccost (None: the context's) frame b's compact block at b (maxKeep + maxCol) maxCol; d_cprobs frame b's
+        [nM][nKeep + 1] at b maxCol (maxKeep + 1); d_probs (None: not expanded) the dense [nM][nL + 1] slices at d_probOff.
+        reserve=False: the caller has called reserve_quadric_map_dev (timed loops, graph capture; the C entry never allocates)."""
+        if reserve:
+            self.reserve_quadric_map_dev(B, maxMap, maxKeep, maxCol)
+        self._check(self.lib.kbest_quadric_map_probs_batch_f64_dev(
+            self.ctx, int(B), int(maxMap), int(maxKeep), int(maxCol), _dptr(d_mapMean), _dptr(d_mapCov), _dptr(d_landOff), _dptr(d_nL),
+            _dptr(d_measMean), _dptr(d_measCov), _dptr(d_measOff), _dptr(d_nM), float(gate), int(max_exact), int(max_width),
+            _dptr(d_nKeep), _dptr(d_rowIdx), _dptr(d_ccost), _dptr(d_cprobs), _dptr(d_probs), _dptr(d_probOff), _dptr(d_logPerm),
+            _dptr(d_method), _dptr(d_nOpen), _dptr(d_nFrontier), _dptr(d_maxCluster), _stream(stream)))
 
     @staticmethod
     def _pack_boxes(boxesL, boxesR):
