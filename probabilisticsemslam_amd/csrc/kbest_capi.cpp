@@ -1047,13 +1047,7 @@ static bool lane_fits(const kbest_ctx *ctx, int B, int maxRow, int maxCol, int k
            kb::lane_lds_layout(maxRow, maxCol, k, s.spec, s.nWaves, s.lanes).total <= ctx->ldsLimit;
 }
 
-// bytes of the lane kernel's workspace (saved hypotheses, then the slot -> state table) and where the table starts
-static size_t lane_states_need(int B, int maxRow, int maxCol, int k, int spec, size_t *slotOff)
-{
-    const size_t nStates = (size_t)B * (size_t)kb::lane_states_per_problem(k, spec, maxCol) * (size_t)kb::lane_state_stride(maxRow);
-    if (slotOff) *slotOff = (nStates + 127) & ~(size_t)127;
-    return ((nStates + 127) & ~(size_t)127) + (size_t)B * (size_t)kb::slot_table_stride(k) * 2 + 256;
-}
+using kb::lane_states_need;  // (kbest_engine.h: the lane kernel's work space, one definition for the entry and the kernel's host build)
 
 static int ensure_states(kbest_ctx *ctx, size_t need, bool grow)
 {

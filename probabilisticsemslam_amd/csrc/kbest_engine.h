@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 
 #include "kbest_c.h"
@@ -403,6 +404,14 @@ __host__ __device__ inline int lane_rows(int maxRow) { return maxRow <= 16 ? 16 
 __host__ __device__ inline long long lane_state_stride(int maxRow) { return state_stride(lane_rows(maxRow)); }
 // emitted + pool (<= k together) + the children completed in one round (<= spec * maxCol) + the root
 __host__ __device__ inline int lane_states_per_problem(int k, int spec, int maxCol) { return k + spec * maxCol + 2; }
+// bytes of the lane kernel's work space (saved hypotheses, then the slot -> state table, then 256 spare bytes) and where the table
+// starts: the entry (kbest_capi.cpp) and the kernel's host build (tests/cpp/lane_host.cpp) size from this one definition
+inline size_t lane_states_need(int B, int maxRow, int maxCol, int k, int spec, size_t *slotOff)
+{
+    const size_t nStates = (size_t)B * (size_t)lane_states_per_problem(k, spec, maxCol) * (size_t)lane_state_stride(maxRow);
+    if (slotOff) *slotOff = (nStates + 127) & ~(size_t)127;
+    return ((nStates + 127) & ~(size_t)127) + (size_t)B * (size_t)slot_table_stride(k) * 2 + 256;
+}
 
 struct LaneLds {
     int offC, offNodes, nodeStride, offPoolG, offFreshG, offPoolM, offFreshM, offPoolS, offFreshS, offItems, offComp, offFree, offScr,

@@ -41,6 +41,10 @@
 #include "kbest_wave.h"
 #include "kbest_lap.h"
 
+#ifndef KB_DYNAMIC_LDS  // (tests/cpp/lane_host.cpp runs these lines on the host, on a heap block of exactly the planned size)
+#define KB_DYNAMIC_LDS(name) extern __shared__ __align__(16) unsigned char name[]
+#endif
+
 namespace kb {
 
 namespace {
@@ -88,10 +92,11 @@ template <int R>
 __device__ __forceinline__ void lane_row(double &spc, u32 &pred, double &best, int &arg, double Crc, double vr,
                                          double delta, double ucur, u32 pm, u32 curRep, u64 execAll)
 {
+    const u32 bm = 0xffu << (8 * (R & 3));
+#ifndef HIP_ON_HOST_H
     double t;
     u32 tmp;
     u64 m;
-    const u32 bm = 0xffu << (8 * (R & 3));
     asm volatile(
         "v_and_b32_e32 %[tmp], %[bit], %[pm]\n\t"
         "v_add_f64 %[t], %[delta], %[C]\n\t"
@@ -110,6 +115,19 @@ __device__ __forceinline__ void lane_row(double &spc, u32 &pred, double &best, i
         : [C] "v"(Crc), [v] "v"(vr), [delta] "v"(delta), [u] "v"(ucur), [pm] "v"(pm), [cr] "v"(curRep), [ex] "s"(execAll),
           [bit] "n"(1u << R), [bm] "s"(bm), [r] "n"(R)
         : "vcc");
+#else  // (tests/cpp/lane_host.cpp: the same step in plain C++ -- the same order of operations, strict '<' twice, pred's byte as v_bfi puts it)
+    (void)execAll;
+    const bool in = ((pm >> R) & 1u) != 0u;
+    const double t = ((delta + Crc) - ucur) - vr;
+    if (in && t < spc) {
+        spc = t;
+        pred = (bm & curRep) | (~bm & pred);
+    }
+    if (in && spc < best) {
+        best = spc;
+        arg = R;
+    }
+#endif
 }
 
 }  // namespace
@@ -119,7 +137,7 @@ __device__ __forceinline__ void lane_row(double &spc, u32 &pred, double &best, i
 template <int RL, int G, int NW, int EPT>
 __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4, 8))) kbest_lane_kernel(Params p)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    KB_DYNAMIC_LDS(smem);
     constexpr int NT = NW * 64, DR = RL * G, LOG_RL = (RL == 16 ? 4 : (RL == 8 ? 3 : 2)), CPW = 64 / G;  // CPW: children per wave
     static_assert((RL == 4 || RL == 8 || RL == 16) && (G == 2 || G == 4) && (DR == 16 || DR == 32), "row / lane split");
     // node block / saved state offsets
@@ -553,7 +571,9 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4,
                         bool live = got;
                         if (__builtin_expect(p.rootColStride > 1, 0)) {  // (the stride opaque: its reciprocal must not be kept across the rounds)
                             int st = p.rootColStride;
+#ifndef HIP_ON_HOST_H
                             asm volatile("" : "+s"(st));
+#endif
                             live = got && !(sidP == 0 && ((int)colOf[c] % st) != p.rootColOffset);
                         }
                         const double bnd = *reinterpret_cast<const double *>(smem + nbN + N_BOUND);

@@ -83,6 +83,7 @@ __device__ __forceinline__ int dijkstra(const double *Cs, int LDC, const double 
     // chosen row, s[84:85] rows still to scan, s[86:87] rows scanned against this column, s[88:89] rows at the minimum.
     // Wait states (gfx950): VALU write -> DPP read 2, VALU VGPR write -> readlane 1, VALU SGPR write -> VALU read 2.
     for (;;) {
+#ifndef HIP_ON_HOST_H
         asm volatile(
             "L_step%=:\n\t"
             "s_mul_i32 s94, s82, s91\n\t"
@@ -151,6 +152,31 @@ __device__ __forceinline__ int dijkstra(const double *Cs, int LDC, const double 
               "{s93}"(bndHi), "{s96}"(parkThr)
             : "v28", "v30", "v31", "v32", "v33", "v34", "v35", "v36", "v37", "v39", "s76", "s77", "s94", "s97", "vcc", "scc",
               "memory");
+#else  // (the host builds of tests/cpp: the same loop in plain C++, one step per iteration; it leaves with status 1 exactly where the
+       //  assembly branches to L_slow, or to L_tie and from there into L_slow, with the registers as the assembly leaves them)
+        (void)rowAddr; (void)uBase; (void)ldc8;
+        for (;;) {
+            const double dl = __longlong_as_double((long long)dbits);
+            const double t = ((dl + Cs[rl + cur * LDC]) - u[cur]) - v;
+            const bool on = ((act >> lane) & 1ull) != 0ull;
+            if (on && t < sp) { sp = t; pred = cur; }
+            khi = on ? __double2hiint(sp) : keyInf;
+            const int mn = wave_min_i32(khi);
+            dbits = ((u64)(u32)mn << 32) | (u32)dbits;  // s81
+            eq = __ballot(khi == mn);
+            status = 1;
+            if (mn < 0) break;  // L_slow
+            closest = __builtin_ctzll(eq);
+            dbits = ((u64)(u32)mn << 32) | (u32)__builtin_amdgcn_readlane(__double2loint(sp), closest);  // s80
+            if (__popcll(eq) > 1 && (__ballot((u32)__double2loint(sp) < (u32)dbits) & eq) != 0ull) break;  // L_tie, then L_slow
+            cur = __builtin_amdgcn_readlane(c4r, closest);  // L_tail
+            cand &= ~(1ull << closest);
+            act = cand;
+            status = 0;
+            if ((int)(((u32)mn - (u32)bndHi) & ~(u32)cur & ((u32)cur - (u32)parkThr)) < 0) continue;  // L_step
+            break;
+        }
+#endif
         // (the compiler does not know that outputs bound to physical scalar registers are wave-uniform)
         dbits = uni64(dbits);
         cur = uni32(cur);

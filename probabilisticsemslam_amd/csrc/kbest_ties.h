@@ -177,6 +177,10 @@ __device__ __attribute__((noinline)) int tie_tail(const double *gain, int *row4c
             // in place, by swaps: position q of the run receives the entry of rank q
             for (int q = 0; q < L; q++) {
                 const int en = inv[q], cur = pos[en];
+#ifdef HIP_ON_HOST_H  // (the host builds of tests/cpp: the lanes are threads there -- on the device the whole wave has read pos[en]
+                      //  in one instruction before lane 0 rewrites it below)
+                wave_fence();
+#endif
                 if (cur != q) {
                     const long long a = r4cBase + (long long)(s + q) * ldCol, b = r4cBase + (long long)(s + cur) * ldCol;
                     for (int c = lane; c < M; c += 64) {

@@ -26,7 +26,7 @@ struct dim3 { int x = 1, y = 1, z = 1; dim3(int a = 1, int b = 1, int c = 1) : x
 thread_local dim3 threadIdx, blockIdx, gridDim, blockDim;
 typedef int hipError_t;
 typedef void *hipStream_t;
-const int hipSuccess = 0, hipFuncAttributeMaxDynamicSharedMemorySize = 0;
+const int hipSuccess = 0, hipErrorInvalidValue = 1, hipFuncAttributeMaxDynamicSharedMemorySize = 0;
 inline int hipGetLastError() { return 0; }
 inline int hipGetDevice(int *d) { *d = 0; return 0; }
 inline int hipFuncSetAttribute(const void *, int, int) { return 0; }
@@ -37,6 +37,26 @@ static double xbuf[EMU_MAX_WAVES][64];
 static u32 ubuf[EMU_MAX_WAVES][64];
 static unsigned char *hostLds;  // the workgroup's dynamic LDS
 #define KB_DYNAMIC_LDS(name) unsigned char *name = hostLds
+// What a workgroup finds in its fresh block of dynamic LDS (a device does not clear LDS between workgroups): 0 = nothing is written
+// (the default: the block is as operator new left it), 1 = every byte 0x00, 2 = every byte 0xFF, 3 = bytes of a generator seeded
+// with emuLdsSeed and the workgroup's index.
+static int emuLdsFill = 0;
+static unsigned long long emuLdsSeed = 0;
+inline void emu_fill_bytes(unsigned char *p, size_t n, int fill, unsigned long long seed)
+{
+    if (fill == 1) memset(p, 0x00, n);
+    else if (fill == 2) memset(p, 0xFF, n);
+    else if (fill == 3) {
+        unsigned long long s = seed * 0x9E3779B97F4A7C15ull + 0xD1B54A32D192ED03ull;
+        for (size_t i = 0; i < n; i++) {  // splitmix64, one byte of every draw
+            s += 0x9E3779B97F4A7C15ull;
+            unsigned long long z = s;
+            z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+            z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+            p[i] = (unsigned char)((z ^ (z >> 31)) >> 24);
+        }
+    }
+}
 inline void __syncthreads() { wgBar->arrive_and_wait(); }
 inline int __popcll(u64 x) { return __builtin_popcountll(x); }
 inline int __popc(unsigned x) { return __builtin_popcount(x); }
@@ -57,7 +77,99 @@ inline u64 __ballot(bool p)
     waveBar[w]->arrive_and_wait();
     return r;
 }
+// ---- the lane-level operations of the k-best kernels (tests/cpp/lane_host.cpp).  One exchange: every lane of the wave publishes a
+// value, the wave's barrier, every lane reads the lane it wants.  Two buffers taken in turn: a lane that writes buffer p again has
+// passed the barrier of the exchange in between, which every lane reaches only after its read of p -- one barrier per exchange.
+static u64 xchgBuf[2][EMU_MAX_WAVES][64];
+static thread_local unsigned xchgTurn;
+template <class T>
+inline T emu_xchg(T x, int src)
+{
+    static_assert(sizeof(T) <= 8, "one 64-bit word per lane");
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+    const unsigned p = xchgTurn++ & 1u;
+    u64 bits = 0;
+    memcpy(&bits, &x, sizeof(T));
+    __atomic_store_n(&xchgBuf[p][w][l], bits, __ATOMIC_RELAXED);
+    waveBar[w]->arrive_and_wait();
+    bits = __atomic_load_n(&xchgBuf[p][w][src & 63], __ATOMIC_RELAXED);
+    T r;
+    memcpy(&r, &bits, sizeof(T));
+    return r;
+}
+inline int __shfl(int x, int src) { return emu_xchg(x, src & 63); }
+inline int __shfl_down(int x, int d) { const int l = threadIdx.x & 63; return emu_xchg(x, l + d < 64 ? l + d : l); }
+inline int __shfl_up(int x, int d) { const int l = threadIdx.x & 63; return emu_xchg(x, l - d >= 0 ? l - d : l); }
+inline int __builtin_amdgcn_readlane(int x, int l) { return emu_xchg(x, l & 63); }
+inline int __builtin_amdgcn_readfirstlane(int x) { return emu_xchg(x, 0); }  // (every lane of the wave is active wherever the kernels call it)
+// DPP with a quad_perm control word (below 0x100: two bits per lane of the quad), every row and bank enabled
+inline int __builtin_amdgcn_update_dpp(int, int x, int ctrl, int rowMask, int bankMask, bool)
+{
+    if (ctrl < 0 || ctrl >= 0x100 || rowMask != 0xF || bankMask != 0xF) abort();
+    const int l = threadIdx.x & 63;
+    return emu_xchg(x, (l & ~3) | ((ctrl >> (2 * (l & 3))) & 3));
+}
+inline u32 __builtin_amdgcn_mbcnt_lo(u32 mask, u32 base) { const int l = threadIdx.x & 63; return base + (u32)__builtin_popcount(l >= 32 ? mask : (mask & ((1u << l) - 1u))); }
+inline u32 __builtin_amdgcn_mbcnt_hi(u32 mask, u32 base) { const int l = threadIdx.x & 63; return base + (u32)__builtin_popcount(l <= 32 ? 0u : (mask & ((1u << (l - 32)) - 1u))); }
+inline bool __builtin_amdgcn_inverse_ballot_w64(u64 mask) { return ((mask >> (threadIdx.x & 63)) & 1ull) != 0ull; }
+inline u64 __builtin_amdgcn_read_exec() { return ~0ull; }
+#define __builtin_amdgcn_fence(order, scope) __atomic_thread_fence(order)
+#define __HIP_MEMORY_SCOPE_AGENT 0
+#define __hip_atomic_load(ptr, order, scope) __atomic_load_n(ptr, order)
+#define __hip_atomic_store(ptr, value, order, scope) __atomic_store_n(ptr, value, order)
+inline int atomicAdd(int *p, int v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
+inline int atomicSub(int *p, int v) { return __atomic_fetch_sub(p, v, __ATOMIC_RELAXED); }
+inline int atomicOr(int *p, int v) { return __atomic_fetch_or(p, v, __ATOMIC_RELAXED); }
+inline int atomicMin(int *p, int v)
+{
+    int old = __atomic_load_n(p, __ATOMIC_RELAXED);
+    while (v < old && !__atomic_compare_exchange_n(p, &old, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) { }
+    return old;
+}
+struct alignas(16) double2 { double x, y; };
+struct alignas(16) float4 { float x, y, z, w; };
+struct alignas(16) int4 { int x, y, z, w; };
+struct alignas(16) uint4 { unsigned x, y, z, w; };
+struct alignas(4) char4 { signed char x, y, z, w; };
+inline int4 make_int4(int x, int y, int z, int w) { return int4{x, y, z, w}; }
+inline int __double2hiint(double d) { u64 b; memcpy(&b, &d, 8); return (int)(u32)(b >> 32); }
+inline int __double2loint(double d) { u64 b; memcpy(&b, &d, 8); return (int)(u32)b; }
+inline double __hiloint2double(int hi, int lo) { const u64 b = ((u64)(u32)hi << 32) | (u32)lo; double d; memcpy(&d, &b, 8); return d; }
+inline float __int_as_float(int i) { float f; memcpy(&f, &i, 4); return f; }
 namespace kb {
+constexpr int KEY_INF_HI = 0x7ff00000;  // kbest_wave.h's keys
+inline void to_key(double x, int &khi, u32 &klo)
+{
+    const int hi = __double2hiint(x), lo = __double2loint(x);
+    const int s = hi >> 31;
+    khi = hi ^ (int)((u32)s >> 1);
+    klo = (u32)(lo ^ s);
+}
+inline double from_key(int khi, u32 klo)
+{
+    const int s = khi >> 31;
+    return __hiloint2double(khi ^ (int)((u32)s >> 1), (int)klo ^ s);
+}
+inline int uni32(int x) { return __builtin_amdgcn_readfirstlane(x); }
+inline u64 uni64(u64 x) { return emu_xchg(x, 0); }
+inline int sel32(u64 mask, int ifset, int ifclear) { return ((mask >> (threadIdx.x & 63)) & 1ull) ? ifset : ifclear; }
+inline double readlane_f64(double x, int l) { return emu_xchg(x, l & 63); }
+inline void wave_fence() { waveBar[threadIdx.x >> 6]->arrive_and_wait(); }  // a wave barrier: the lanes are threads here
+inline u64 bit64(int i) { return 1ull << (i & 63); }
+inline void put_index(int *table, long long i, int value, bool i8)
+{
+    if (i8) reinterpret_cast<signed char *>(table)[i] = (signed char)value;
+    else table[i] = value;
+}
+inline int wave_min_i32(int x)
+{
+    int r = x;
+    for (int s = 1; s < 64; s <<= 1) {  // butterfly: every lane ends with the minimum of all 64
+        const int o = emu_xchg(r, (int)(threadIdx.x & 63) ^ s);
+        r = o < r ? o : r;
+    }
+    return r;
+}
 inline double d_inf() { return INFINITY; }
 inline double min_keep(double a, double b) { return b < a ? b : a; }
 inline u32 wave_min_u32(u32 x)
@@ -89,8 +201,7 @@ inline double dpp_f64(double x)
     double r = x;
     if ((ROWMASK >> row) & 1) {
         int src = l;
-        if (CTRL == 0xB1) src = l ^ 1;
-        else if (CTRL == 0x4E) src = l ^ 2;
+        if (CTRL < 0x100) src = (l & ~3) | ((CTRL >> (2 * (l & 3))) & 3);  // quad_perm (0xB1: lane ^ 1, 0x4E: lane ^ 2)
         else if (CTRL == 0x141) src = (l & ~7) | (7 - (l & 7));
         else if (CTRL == 0x140) src = (l & ~15) | (15 - (l & 15));
         else if (CTRL == 0x142) src = row * 16 - 1;
@@ -104,7 +215,7 @@ inline double dpp_f64(double x)
 }
 // block.x threads (whole waves) and block.x / 64 wave barriers, whatever the program launches; the workgroups of the launch one
 // after another on the same threads, each with a fresh block of dynamic LDS (the barriers around a workgroup: its static LDS and
-// hostLds are the next one's).  lds = 0 is the normal case: of the five programs only sample_host launches with dynamic LDS.
+// hostLds are the next one's).  lds = 0 is the normal case: only sample_host and lane_host launch with dynamic LDS.
 template <class K, class... A>
 void emu_launch(K kernel, dim3 grid, dim3 block, int lds, A... args)
 {
@@ -124,7 +235,10 @@ void emu_launch(K kernel, dim3 grid, dim3 block, int lds, A... args)
             blockDim = block;
             for (int b = 0; b < grid.x; b++) {
                 blockIdx = dim3(b);
-                if (t == 0) hostLds = new unsigned char[lds];
+                if (t == 0) {
+                    hostLds = new unsigned char[lds];
+                    emu_fill_bytes(hostLds, (size_t)lds, emuLdsFill, emuLdsSeed + (unsigned long long)b);
+                }
                 wgBar->arrive_and_wait();
                 kernel(args...);
                 wgBar->arrive_and_wait();
