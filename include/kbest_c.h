@@ -39,6 +39,8 @@
  *   kbest_clustered_sample_assoc_batch_f64 / kbest_clustered_sample_assoc_batch_f64_dev
  *   kbest_hybrid_frontier_sample_assoc_batch_f64 / kbest_hybrid_frontier_sample_assoc_batch_f64_dev
  *        joint associations drawn from the exact posterior of such frames, one walk per cluster (not in the reference)
+ *   kbest_quadric_map_sample_assoc_batch_f64 / kbest_quadric_map_sample_assoc_batch_f64_dev / kbest_reserve_quadric_map_sample_dev
+ *        the same draws from quadrics against a map of any size, in the rows of the raw block (not in the reference)
  *
  * Conventions kept from the reference: cost matrices are column-major
  * C[row + col*numRow] with numRow >= numCol (shortestPathCPP.hpp:185-190);
@@ -1008,6 +1010,74 @@ int kbest_quadric_map_probs_batch_f64(kbest_ctx *ctx, int B, int nMap, const dou
 /* Diagnostic: registers, scratch bytes and static LDS bytes of the passes that compute costs (which = 0: minima, 1: kept rows,
  * 2: compact block), for tools/bench_quadric_map.py. */
 int kbest_quadric_map_kernel_usage(int which, int32_t *vgprs, int32_t *scratchBytes, int32_t *ldsBytes);
+/*
+ * Joint associations from quadrics against a map of any size, on ONE stream (kbest_quadric_map_sample.hip; not in the reference):
+ * the drawing twin of kbest_quadric_map_probs_batch_f64_dev.  Four steps on the stream: the gate passes and the fill of
+ * kbest_quadric_map.hip (nKeep, rowIdx, the compact conditioned blocks -- the raw block is never written),
+ * kbest_hybrid_frontier_sample_assoc_batch_f64_dev on the compact blocks (condition = 0, maxRawRow = maxKeep + maxCol, nL = the
+ * kept rows, the context's d_sub, the caller's d_assign, d_logProb and offsets), and one kernel that rewrites d_assign in place
+ * from compact rows to the rows of the notional raw (nL + nM) x nM block, which is what every other sampling entry returns (a miss
+ * is not folded into nL): v < 0 stays -1; v < nKeep becomes rowIdx[b][v]; otherwise v becomes nL + (v - nKeep), the miss row of
+ * measurement v - nKeep.  No host read, no synchronise, no allocation, no atomics, no workgroup waits for another; stream order
+ * between the launches is the only synchronisation.
+ *
+ * kbest_quadric_map_sample_assoc_batch_f64_dev: the map, frames, gate, d_nKeep, d_rowIdx and d_ccost (may be NULL: the context's) as
+ * in kbest_quadric_map_probs_batch_f64_dev; maxExact, maxWidth, nSample, seed, sampleBase, d_frameKey (may be NULL: frame b has key
+ * b), d_assign, d_asgOff, d_logProb, d_lpOff, d_logPerm, d_method (required), d_nOpen, d_nFrontier and d_maxCluster (each may be
+ * NULL) as in kbest_hybrid_frontier_sample_assoc_batch_f64_dev.
+ *   nKeep, rowIdx, ccost, logPerm, method, nOpen, nFrontier, maxCluster: the bits of kbest_quadric_map_probs_batch_f64_dev on the
+ *       same frames.
+ *   assign, logProb: those of kbest_hybrid_frontier_sample_assoc_batch_f64_dev on the compact block with condition = 0, assign
+ *       mapped as above.  A frame's draws are a function of (frame, seed, frame key, draw index) alone.  On a frame without an
+ *       open cluster they are, bit for bit, the draws of the older path -- kbest_quadric_costs_f64, then that entry with
+ *       condition = 1 on the raw block: the uniforms are indexed by active rows, and conditioning does not renumber those.
+ *   NOTE: on a frame with a frontier cluster they are exact draws from the same posterior but NOT the same draws as on the raw
+ *       block: the frontier sampler's key is the row number of the block it is given (the NOTE at
+ *       kbest_hybrid_frontier_sample_assoc_batch_f64), and that is a compact row here.
+ * Per-frame outcomes.  nKeep > maxKeep: method -1, d_nKeep[b] the true count (reserve again and call again), every assign -1,
+ * every logProb NaN, rowIdx and the compact block not written.  nM < 1, nM > maxCol, nL < 0, nL > maxMap or a negative offset:
+ * method -1, nOpen and nFrontier 0, logPerm NaN; nKeep, rowIdx, maxCluster, assign and logProb of the frame are not touched.
+ * nL = 0 is no special case: assign[s][c] = c, the miss row of measurement c.
+ * Limits: those of kbest_quadric_map_probs_batch_f64_dev, but maxWidth 0 .. 16, where 0 refuses every frame with an open cluster, as
+ * the sampler defines it; nSample >= 1; sampleBase + nSample <= 2^32 -- else KBEST_ERR_BAD_ARG.
+ * kbest_reserve_quadric_map_sample_dev(ctx, B, maxMap, maxKeep, maxCol, nSample) calls kbest_reserve_quadric_map_dev(B, maxMap,
+ * maxKeep, maxCol) and kbest_reserve_hybrid_sample_dev(B, min(maxKeep + maxCol, 1 024), maxCol, nSample), the latter with the
+ * largest of each number so far.  A reservation never shrinks.  Without it, or with a call beyond it in any of the five numbers:
+ * KBEST_ERR_NOT_RESERVED, nothing launched.  B = 0: KBEST_OK, nothing launched.  Asynchronous on `stream` (NULL: the context's);
+ * two calls on one stream need no synchronise between them.
+ */
+/* (a work space a captured launch holds does not grow: "WORK SPACES UNDER A CAPTURED LAUNCH" at kbest_reserve) */
+int kbest_reserve_quadric_map_sample_dev(kbest_ctx *ctx, int B, int maxMap, int maxKeep, int maxCol, int nSample);
+int kbest_quadric_map_sample_assoc_batch_f64_dev(kbest_ctx *ctx, int B, int maxMap, int maxKeep, int maxCol, const double *d_mapMean,
+                                                 const double *d_mapCov, const int64_t *d_landOff, const int32_t *d_nL,
+                                                 const double *d_measMean, const double *d_measCov, const int64_t *d_measOff,
+                                                 const int32_t *d_nM, double gate, int maxExact, int maxWidth, int nSample, uint64_t seed,
+                                                 uint32_t sampleBase, const uint64_t *d_frameKey, int32_t *d_nKeep, int32_t *d_rowIdx,
+                                                 double *d_ccost, int32_t *d_assign, const int64_t *d_asgOff, double *d_logProb,
+                                                 const int64_t *d_lpOff, double *d_logPerm, int32_t *d_method, int32_t *d_nOpen,
+                                                 int32_t *d_nFrontier, int32_t *d_maxCluster, void *stream);
+/*
+ * The same from host buffers, synchronous, shaped like kbest_quadric_map_probs_batch_f64 and sharing its staging, gate and round
+ * plumbing: the map staged once, the gate passes, nKeep read back, the rest sized from it, rounds where maxKeep + maxCol would
+ * exceed 1 024.  assign at asgOff[b]: int32 [nSample][nM], raw rows as above; logProb at lpOff[b]: double [nSample]; frameKey (may
+ * be NULL: frame b has key b).  k = 0: the bits of the one-stream entry.  k >= 1 (up to KBEST_TABLE_SAMPLE_MAX_K): a frame that
+ * entry refuses because of an open cluster goes on, as its compact block -- one device-to-host copy --, through
+ * kbest_hybrid_sample_assoc_batch_f64(condition = 0, k) with the frame's own key and the same sampleBase, and its rows are mapped on
+ * the host; so k >= 1 draws every gated frame, and method 1 / 2 and nEnum say which frames were enumerated.  logPerm, nOpen,
+ * nFrontier, nEnum, maxCluster (each may be NULL), method and nKeep (required) as that entry's.  More than 1 024 - nM kept
+ * landmarks: method -1 for that frame (every assign -1, every logProb NaN, logPerm NaN, nKeep the true count), the call succeeds.
+ * nM > 128 or nL > KBEST_QUADRIC_MAP_MAX: KBEST_ERR_UNSUPPORTED.
+ */
+int kbest_quadric_map_sample_assoc_batch_f64(kbest_ctx *ctx, int B, int nMap, const double *mapMean, const double *mapCov,
+                                             const int64_t *landOff, const int32_t *nL, const int32_t *nM, const double *measMean,
+                                             const double *measCov, double gate, int k, int maxExact, int maxWidth, int nSample,
+                                             uint64_t seed, uint32_t sampleBase, const uint64_t *frameKey, int32_t *assign,
+                                             const int64_t *asgOff, double *logProb, const int64_t *lpOff, double *logPerm,
+                                             int32_t *method, int32_t *nKeep, int32_t *nOpen, int32_t *nFrontier, int32_t *nEnum,
+                                             int32_t *maxCluster);
+/* Diagnostic: registers, scratch bytes and static LDS bytes of the kernel that maps compact rows to raw rows, for
+ * tools/bench_quadric_map_sample.py. */
+int kbest_quadric_map_sample_kernel_usage(int32_t *vgprs, int32_t *scratchBytes, int32_t *ldsBytes);
 /* on = 1: the HOST-buffer association entries of this context (kbest_weights / assoc_probs / bruteforce / quadric_assoc) enumerate
  * their k best in the REFERENCE's own order of operations (the reference-order kernel, as KBEST_FLAG_REFERENCE_ORDER does for
  * kbest_batch_f64): where exactly equal gains straddle slot k the assignments that are weighed are the ones the reference's

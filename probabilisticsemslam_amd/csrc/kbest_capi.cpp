@@ -4845,34 +4845,39 @@ int kbest_quadric_map_kernel_usage(int which, int32_t *vgprs, int32_t *scratchBy
     return KBEST_OK;
 }
 
-// The synchronous entry: the map staged once, the gate passes, nKeep read back, the rest sized from that; the frames the one-stream
-// path refuses go on as their compact blocks through kbest_hybrid_frontier_probs_batch_f64(k, maxBig, condition = 0).  Frames run
-// in rounds so that every frame with nKeep <= 1 024 - nM is taken whatever else the batch holds: a round's bounds are the largest
-// nM of the frames still waiting and the largest nKeep that fits beside it (the frame with that nM always fits: one round, almost
-// always).
-int kbest_quadric_map_probs_batch_f64(kbest_ctx *ctx, int B, int nMap, const double *mapMean, const double *mapCov, const int64_t *landOff,
-                                      const int32_t *nL, const int32_t *nM, const double *measMean, const double *measCov, double gate,
-                                      int k, int maxExact, int maxBig, int maxWidth, double *probs, const int64_t *probOff,
-                                      double *logPerm, int32_t *method, int32_t *nKeep, int32_t *nOpen, int32_t *nBig,
-                                      int32_t *nFrontier, int32_t *maxCluster)
+// The two synchronous entries (the probabilities here, the draws of kbest_quadric_map_sample_assoc_batch_f64 further down) share
+// everything up to a round: the map staged once, the gate passes, nKeep read back, the rest sized from that.  Frames run in rounds
+// so that every frame with nKeep <= 1 024 - nM is taken whatever else the batch holds: a round's bounds are the largest nM of the
+// frames still waiting and the largest nKeep that fits beside it (the frame with that nM always fits: one round, almost always).
+// What a round is handed: its n frames (idx: their numbers in the caller's batch) staged at the head of the device arrays, the
+// bounds of the round, and the per-frame outputs of the one-stream entries ([n] each, device).
+struct QmapHostRound {
+    int n, maxMap, maxKeep, maxCol;
+    const std::vector<int> *idx;
+    double *d_mapMean, *d_mapCov, *d_measMean, *d_measCov;
+    int64_t *d_landOff, *d_measOff;
+    int32_t *d_nL, *d_nM, *d_nKeep, *d_method, *d_nOpen, *d_nFrontier, *d_maxCluster;
+    double *d_logPerm;
+    hipStream_t s;
+};
+// offs: the caller's per-frame offset arrays, none of which may hold a negative number; refuse(b): every output of frame b as a
+// refused frame has it, called once for every frame after nKeep[b] is known; round(r): everything from the reservation on.
+extern "C++" {
+template <class Refuse, class Round>
+static int qmap_host_rounds(kbest_ctx *ctx, const char *who, int B, int nMap, const double *mapMean, const double *mapCov,
+                            const int64_t *landOff, const int32_t *nL, const int32_t *nM, const double *measMean, const double *measCov,
+                            double gate, std::initializer_list<const int64_t *> offs, int32_t *nKeep, Refuse refuse, Round round)
 {
-    if (!ctx) return KBEST_ERR_BAD_ARG;
-    const char *who = "kbest_quadric_map_probs_batch_f64";
-    if (B < 0 || nMap < 0 || k < 0 || maxExact < 0 || maxExact > KBEST_CLUSTER_MAX_SIZE || maxBig < 0 || maxBig > KBEST_BIGCLUSTER_MAX_SIZE ||
-        maxWidth < 1 || maxWidth > KBEST_FRONTIER_MAX_WIDTH || gate != gate ||
-        (B > 0 && (!landOff || !nL || !nM || !measMean || !measCov || !probs || !probOff || !method || !nKeep)) ||
-        (nMap > 0 && (!mapMean || !mapCov)))
-        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_quadric_map_probs_batch_f64: bad argument (k >= 0, maxExact 0 .. 16, maxBig 0 .. 20, "
-                                            "maxWidth 1 .. 16, gate not NaN)");
-    if (B == 0) return KBEST_OK;
     int maxMap = 1, maxColAll = 1;
     std::vector<int64_t> measOff(B);
     int64_t nMeas = 0;
     for (int b = 0; b < B; b++) {
-        if (nM[b] < 1 || nL[b] < 0 || landOff[b] < 0 || landOff[b] + nL[b] > nMap || probOff[b] < 0)
-            return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_quadric_map_probs_batch_f64: a frame with nM < 1, nL < 0, a window beyond the map or a negative offset");
+        bool negative = false;
+        for (const int64_t *o : offs) negative = negative || o[b] < 0;
+        if (nM[b] < 1 || nL[b] < 0 || landOff[b] < 0 || landOff[b] + nL[b] > nMap || negative)
+            return fail(ctx, KBEST_ERR_BAD_ARG, (std::string(who) + ": a frame with nM < 1, nL < 0, a window beyond the map or a negative offset").c_str());
         if (nM[b] > kb::QMAP_MAX_COLS) return fail(ctx, KBEST_ERR_UNSUPPORTED, (std::string(who) + CLUSTER_COLS_TEXT).c_str());
-        if (nL[b] > KBEST_QUADRIC_MAP_MAX) return fail(ctx, KBEST_ERR_UNSUPPORTED, "kbest_quadric_map_probs_batch_f64: more than KBEST_QUADRIC_MAP_MAX landmarks in a frame");
+        if (nL[b] > KBEST_QUADRIC_MAP_MAX) return fail(ctx, KBEST_ERR_UNSUPPORTED, (std::string(who) + ": more than KBEST_QUADRIC_MAP_MAX landmarks in a frame").c_str());
         maxMap = std::max(maxMap, nL[b]);
         maxColAll = std::max(maxColAll, nM[b]);
         measOff[b] = nMeas;
@@ -4888,7 +4893,7 @@ int kbest_quadric_map_probs_batch_f64(kbest_ctx *ctx, int B, int nMap, const dou
     const size_t mapN = (size_t)std::max(nMap, 1);
     if ((e = dMap.alloc(ctx, mapN * 12 * 8)) != hipSuccess || (e = dMeas.alloc(ctx, (size_t)nMeas * 12 * 8)) != hipSuccess ||
         (e = dMeta.alloc(ctx, (size_t)B * 64)) != hipSuccess)
-        return fail(ctx, KBEST_ERR_NOMEM, "kbest_quadric_map_probs_batch_f64: device buffers", e);
+        return fail(ctx, KBEST_ERR_NOMEM, (std::string(who) + ": device buffers").c_str(), e);
     double *d_mapMean = dMap.as<double>(), *d_mapCov = d_mapMean + mapN * 3;
     double *d_measMean = dMeas.as<double>(), *d_measCov = d_measMean + (size_t)nMeas * 3;
     if (nMap > 0) {  // the map goes up once, whatever the number of frames
@@ -4929,16 +4934,9 @@ int kbest_quadric_map_probs_batch_f64(kbest_ctx *ctx, int B, int nMap, const dou
         HIP_TRY(ctx, hipMemcpy(nKeep, d_nKeep, (size_t)B * 4, hipMemcpyDeviceToHost));
     }
     // 2. every output as a refused frame has it; the frames that fit wait for a round
-    const double nan = std::numeric_limits<double>::quiet_NaN();
     std::vector<int> waiting;
     for (int b = 0; b < B; b++) {
-        memset(probs + probOff[b], 0, (size_t)nM[b] * ((size_t)nL[b] + 1) * 8);
-        method[b] = -1;
-        if (logPerm) logPerm[b] = nan;
-        if (nOpen) nOpen[b] = 0;
-        if (nBig) nBig[b] = 0;
-        if (nFrontier) nFrontier[b] = 0;
-        if (maxCluster) maxCluster[b] = 0;
+        refuse(b);
         if (nKeep[b] <= KBEST_MAX_DIM_WIDE - nM[b]) waiting.push_back(b);
     }
     while (!waiting.empty()) {
@@ -4948,19 +4946,59 @@ int kbest_quadric_map_probs_batch_f64(kbest_ctx *ctx, int B, int nMap, const dou
         std::vector<int> idx, rest;
         for (int b : waiting) (nKeep[b] <= maxKeep ? idx : rest).push_back(b);
         waiting.swap(rest);
-        const int n = (int)idx.size();
         KB_TRY(put_frames(idx));
+        const QmapHostRound r{(int)idx.size(), maxMap, maxKeep, maxCol, &idx, d_mapMean, d_mapCov, d_measMean, d_measCov, d_landOff,
+                              d_measOff, d_nL, d_nM, d_nKeep, d_method, d_nOpen, d_nFrontier, d_maxCluster, d_logPerm, s};
+        KB_TRY(round(r));
+    }
+    return KBEST_OK;
+}
+}  // extern "C++"
+
+// The synchronous entry: qmap_host_rounds, and in a round the one-stream entry; the frames that path refuses go on as their compact
+// blocks through kbest_hybrid_frontier_probs_batch_f64(k, maxBig, condition = 0).
+int kbest_quadric_map_probs_batch_f64(kbest_ctx *ctx, int B, int nMap, const double *mapMean, const double *mapCov, const int64_t *landOff,
+                                      const int32_t *nL, const int32_t *nM, const double *measMean, const double *measCov, double gate,
+                                      int k, int maxExact, int maxBig, int maxWidth, double *probs, const int64_t *probOff,
+                                      double *logPerm, int32_t *method, int32_t *nKeep, int32_t *nOpen, int32_t *nBig,
+                                      int32_t *nFrontier, int32_t *maxCluster)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    const char *who = "kbest_quadric_map_probs_batch_f64";
+    if (B < 0 || nMap < 0 || k < 0 || maxExact < 0 || maxExact > KBEST_CLUSTER_MAX_SIZE || maxBig < 0 || maxBig > KBEST_BIGCLUSTER_MAX_SIZE ||
+        maxWidth < 1 || maxWidth > KBEST_FRONTIER_MAX_WIDTH || gate != gate ||
+        (B > 0 && (!landOff || !nL || !nM || !measMean || !measCov || !probs || !probOff || !method || !nKeep)) ||
+        (nMap > 0 && (!mapMean || !mapCov)))
+        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_quadric_map_probs_batch_f64: bad argument (k >= 0, maxExact 0 .. 16, maxBig 0 .. 20, "
+                                            "maxWidth 1 .. 16, gate not NaN)");
+    if (B == 0) return KBEST_OK;
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    auto refuse = [&](int b) {
+        memset(probs + probOff[b], 0, (size_t)nM[b] * ((size_t)nL[b] + 1) * 8);
+        method[b] = -1;
+        if (logPerm) logPerm[b] = nan;
+        if (nOpen) nOpen[b] = 0;
+        if (nBig) nBig[b] = 0;
+        if (nFrontier) nFrontier[b] = 0;
+        if (maxCluster) maxCluster[b] = 0;
+    };
+    auto round = [&](const QmapHostRound &q) -> int {
+        const std::vector<int> &idx = *q.idx;
+        const int n = q.n, maxMap = q.maxMap, maxKeep = q.maxKeep, maxCol = q.maxCol;
+        int32_t *d_method = q.d_method, *d_nOpen = q.d_nOpen, *d_nFrontier = q.d_nFrontier, *d_maxCluster = q.d_maxCluster;
+        double *d_logPerm = q.d_logPerm;
+        hipError_t e;
         KB_TRY(kbest_reserve_quadric_map_dev(ctx, n, maxMap, maxKeep, maxCol));
         const QmapLayout L = qmap_layout(n, maxMap, maxKeep, maxCol);
         DevBuf dRows, dCost, dCp;
         if ((e = dRows.alloc(ctx, (size_t)n * maxKeep * 4)) != hipSuccess || (e = dCost.alloc(ctx, (size_t)n * L.costStride * 8)) != hipSuccess ||
             (e = dCp.alloc(ctx, (size_t)n * L.cprobStride * 8)) != hipSuccess)
             return fail(ctx, KBEST_ERR_NOMEM, "kbest_quadric_map_probs_batch_f64: device buffers", e);
-        KB_TRY(kbest_quadric_map_probs_batch_f64_dev(ctx, n, maxMap, maxKeep, maxCol, d_mapMean, d_mapCov, d_landOff, d_nL, d_measMean,
-                                                     d_measCov, d_measOff, d_nM, gate, maxExact, maxWidth, d_nKeep, dRows.as<int32_t>(),
-                                                     dCost.as<double>(), dCp.as<double>(), nullptr, nullptr, d_logPerm, d_method, d_nOpen,
-                                                     d_nFrontier, d_maxCluster, nullptr));
-        HIP_TRY(ctx, hipStreamSynchronize(s));
+        KB_TRY(kbest_quadric_map_probs_batch_f64_dev(ctx, n, maxMap, maxKeep, maxCol, q.d_mapMean, q.d_mapCov, q.d_landOff, q.d_nL,
+                                                     q.d_measMean, q.d_measCov, q.d_measOff, q.d_nM, gate, maxExact, maxWidth, q.d_nKeep,
+                                                     dRows.as<int32_t>(), dCost.as<double>(), dCp.as<double>(), nullptr, nullptr, d_logPerm,
+                                                     d_method, d_nOpen, d_nFrontier, d_maxCluster, nullptr));
+        HIP_TRY(ctx, hipStreamSynchronize(q.s));
         std::vector<int32_t> rows((size_t)n * maxKeep), ints((size_t)n * 4);
         std::vector<double> cp((size_t)n * L.cprobStride), lp(n);
         HIP_TRY(ctx, hipMemcpy(rows.data(), dRows.p, rows.size() * 4, hipMemcpyDeviceToHost));
@@ -5022,8 +5060,9 @@ int kbest_quadric_map_probs_batch_f64(kbest_ctx *ctx, int B, int nMap, const dou
             if (nBig) nBig[b] = big[j];
             if (logPerm) logPerm[b] = lp[j];
         }
-    }
-    return KBEST_OK;
+        return KBEST_OK;
+    };
+    return qmap_host_rounds(ctx, who, B, nMap, mapMean, mapCov, landOff, nL, nM, measMean, measCov, gate, {probOff}, nKeep, refuse, round);
 }
 
 // ---- whole hypotheses for the frames of kbest_hybrid_frontier_probs_batch_f64(k = 0, maxBig = 0): the small clusters by the
@@ -5495,6 +5534,243 @@ int kbest_hybrid_frontier_sample_assoc_batch_f64_dev(kbest_ctx *ctx, int B, int 
     if (e == hipSuccess) e = kb::launch_hybrid_sample_join(sp, s);
     if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "hybrid sampling kernel launch", e);
     return KBEST_OK;
+}
+
+// ---- joint associations from quadrics against a map of any size: the gate and fill passes of kbest_quadric_map.hip, the one-stream
+//      sampler above on the compact blocks, and kbest_quadric_map_sample.hip, which turns compact rows back into landmark numbers ----
+// workgroups per frame of that last kernel: a grid-stride loop over the frame's nSample * nM draws, at most 1 024 of them a frame
+static int qmap_sample_tiles(int B, int maxCol, int nSample)
+{
+    long long t = ((long long)maxCol * nSample + kb::QMAP_TILE - 1) / kb::QMAP_TILE;
+    if (t > 1024) t = 1024;
+    while (t > 1 && t * B > 0x7fffffffLL) t >>= 1;
+    return (int)t;
+}
+
+static const char QMAP_SAMPLE_ARGS_TEXT[] = ": bad argument (maxExact 0 .. 16, maxWidth 0 .. 16, nSample >= 1, sampleBase + nSample <= 2^32, "
+                                            "gate not NaN)";
+
+int kbest_reserve_quadric_map_sample_dev(kbest_ctx *ctx, int B, int maxMap, int maxKeep, int maxCol, int nSample)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    KB_TRY(qmap_check(ctx, "kbest_reserve_quadric_map_sample_dev", B, maxMap, maxKeep, maxCol));
+    if (nSample < 1) return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_reserve_quadric_map_sample_dev: bad argument (nSample >= 1)");
+    if (B == 0) return KBEST_OK;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    KB_TRY(kbest_reserve_quadric_map_dev(ctx, B, maxMap, maxKeep, maxCol));
+    // the sampler's work space for the largest of each number so far, as the quadric map's: every legal call within them fits
+    return kbest_reserve_hybrid_sample_dev(ctx, ctx->qmapB, std::min(ctx->qmapKeep + ctx->qmapCol, (int)KBEST_MAX_DIM_WIDE), ctx->qmapCol,
+                                           nSample);
+}
+
+int kbest_quadric_map_sample_assoc_batch_f64_dev(kbest_ctx *ctx, int B, int maxMap, int maxKeep, int maxCol, const double *d_mapMean,
+                                                 const double *d_mapCov, const int64_t *d_landOff, const int32_t *d_nL,
+                                                 const double *d_measMean, const double *d_measCov, const int64_t *d_measOff,
+                                                 const int32_t *d_nM, double gate, int maxExact, int maxWidth, int nSample, uint64_t seed,
+                                                 uint32_t sampleBase, const uint64_t *d_frameKey, int32_t *d_nKeep, int32_t *d_rowIdx,
+                                                 double *d_ccost, int32_t *d_assign, const int64_t *d_asgOff, double *d_logProb,
+                                                 const int64_t *d_lpOff, double *d_logPerm, int32_t *d_method, int32_t *d_nOpen,
+                                                 int32_t *d_nFrontier, int32_t *d_maxCluster, void *stream)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    const std::string who = "kbest_quadric_map_sample_assoc_batch_f64_dev";
+    KB_TRY(qmap_check(ctx, who.c_str(), B, maxMap, maxKeep, maxCol));
+    if (maxExact < 0 || maxExact > KBEST_CLUSTER_MAX_SIZE || maxWidth < 0 || maxWidth > KBEST_FRONTIER_MAX_WIDTH || nSample < 1 ||
+        (uint64_t)sampleBase + (uint64_t)nSample > ((uint64_t)1 << 32) || gate != gate)
+        return fail(ctx, KBEST_ERR_BAD_ARG, (who + QMAP_SAMPLE_ARGS_TEXT).c_str());
+    if (B == 0) return KBEST_OK;
+    if (!d_mapMean || !d_mapCov || !d_landOff || !d_nL || !d_measMean || !d_measCov || !d_measOff || !d_nM || !d_nKeep || !d_rowIdx ||
+        !d_assign || !d_asgOff || !d_logProb || !d_lpOff || !d_method)
+        return fail(ctx, KBEST_ERR_BAD_ARG, (who + ": bad argument (a required pointer is NULL)").c_str());
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // everything is checked before anything is launched: this entry's work space, and what the sampler will ask for
+    const int maxRawRow = maxKeep + maxCol;
+    HybridDevPlan d;
+    KB_TRY(hybrid_dev_plan(ctx, who.c_str(), B, maxRawRow, maxCol, d));
+    if (!qmap_reserved(ctx, B, maxMap, maxKeep, maxCol) || !d.reserved || B > ctx->hybSampB || maxRawRow > ctx->hybSampRow ||
+        maxCol > ctx->hybSampCol || nSample > ctx->hybSampN ||
+        ctx->hybSampBuf.bytes < hybrid_sample_layout(B, maxRawRow, maxCol, nSample).total)
+        return fail(ctx, KBEST_ERR_NOT_RESERVED, (who + ": call kbest_reserve_quadric_map_sample_dev first").c_str());
+    const QmapLayout L = qmap_layout(B, maxMap, maxKeep, maxCol);
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    KB_TRY(order_behind_last(ctx, s));
+    const Launched mark{ctx, s};
+    hold_if_capturing(s, {&ctx->qmapBuf});  // (the sampler holds its own)
+    kb::QuadricMapParams p;
+    qmap_params(p, ctx, L, B, maxMap, maxKeep, maxCol, d_mapMean, d_mapCov, d_landOff, d_nL, d_measMean, d_measCov, d_measOff, d_nM, gate,
+                d_nKeep, d_rowIdx, d_ccost);
+    hipError_t e = kb::launch_quadric_map_gate(p, s);
+    if (e == hipSuccess) e = kb::launch_quadric_map_fill(p, s);
+    if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "quadric map kernel launch", e);
+    // the compact blocks are conditioned already: condition = 0, nL = the kept rows (-1: the frame is refused and not touched)
+    unsigned char *h8 = static_cast<unsigned char *>(ctx->qmapBuf.p);
+    KB_TRY(kbest_hybrid_frontier_sample_assoc_batch_f64_dev(ctx, B, maxRawRow, maxCol, p.nLh, d_nM, p.ccost,
+                                                            reinterpret_cast<const int64_t *>(p.costOff), 0, maxExact, maxWidth, nSample,
+                                                            seed, sampleBase, d_frameKey, reinterpret_cast<double *>(h8 + L.sub), d_assign,
+                                                            d_asgOff, d_logProb, d_lpOff, d_logPerm, d_method, d_nOpen, d_nFrontier,
+                                                            d_maxCluster, stream));
+    kb::QuadricMapSampleParams q;
+    q.landOff = p.landOff;
+    q.measOff = p.measOff;
+    q.nL = d_nL;
+    q.nM = d_nM;
+    q.B = B;
+    q.maxMap = maxMap;
+    q.maxKeep = maxKeep;
+    q.maxCol = maxCol;
+    q.nTiles = qmap_sample_tiles(B, maxCol, nSample);
+    q.nSample = nSample;
+    q.nKeep = d_nKeep;
+    q.rowIdx = d_rowIdx;
+    q.assign = d_assign;
+    q.asgOff = reinterpret_cast<const long long *>(d_asgOff);
+    q.logProb = d_logProb;
+    q.lpOff = reinterpret_cast<const long long *>(d_lpOff);
+    e = kb::launch_quadric_map_sample_rows(q, s);
+    if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "quadric map sampling kernel launch", e);
+    return KBEST_OK;
+}
+
+int kbest_quadric_map_sample_kernel_usage(int32_t *vgprs, int32_t *scratchBytes, int32_t *ldsBytes)
+{
+    int v = 0, sc = 0, l = 0;
+    if (!vgprs || !scratchBytes || !ldsBytes) return KBEST_ERR_BAD_ARG;
+    if (kb::quadric_map_sample_kernel_usage(&v, &sc, &l) != hipSuccess) return KBEST_ERR_HIP;
+    *vgprs = v;
+    *scratchBytes = sc;
+    *ldsBytes = l;
+    return KBEST_OK;
+}
+
+// The synchronous entry: qmap_host_rounds, and in a round the one-stream entry; with k >= 1 the frames that path refuses go on as
+// their compact blocks through kbest_hybrid_sample_assoc_batch_f64(condition = 0, k), under the frame's own key, and their rows
+// are mapped here as kbest_quadric_map_sample.hip maps the others.
+int kbest_quadric_map_sample_assoc_batch_f64(kbest_ctx *ctx, int B, int nMap, const double *mapMean, const double *mapCov,
+                                             const int64_t *landOff, const int32_t *nL, const int32_t *nM, const double *measMean,
+                                             const double *measCov, double gate, int k, int maxExact, int maxWidth, int nSample,
+                                             uint64_t seed, uint32_t sampleBase, const uint64_t *frameKey, int32_t *assign,
+                                             const int64_t *asgOff, double *logProb, const int64_t *lpOff, double *logPerm,
+                                             int32_t *method, int32_t *nKeep, int32_t *nOpen, int32_t *nFrontier, int32_t *nEnum,
+                                             int32_t *maxCluster)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    const char *who = "kbest_quadric_map_sample_assoc_batch_f64";
+    if (B < 0 || nMap < 0 || k < 0 || k > KBEST_TABLE_SAMPLE_MAX_K || maxExact < 0 || maxExact > KBEST_CLUSTER_MAX_SIZE || maxWidth < 0 ||
+        maxWidth > KBEST_FRONTIER_MAX_WIDTH || nSample < 1 || (uint64_t)sampleBase + (uint64_t)nSample > ((uint64_t)1 << 32) || gate != gate ||
+        (B > 0 && (!landOff || !nL || !nM || !measMean || !measCov || !assign || !asgOff || !logProb || !lpOff || !method || !nKeep)) ||
+        (nMap > 0 && (!mapMean || !mapCov)))
+        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_quadric_map_sample_assoc_batch_f64: bad argument (k 0 .. 4096, maxExact 0 .. 16, "
+                                            "maxWidth 0 .. 16, nSample >= 1, sampleBase + nSample <= 2^32, gate not NaN)");
+    if (B == 0) return KBEST_OK;
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    auto refuse = [&](int b) {
+        std::fill_n(assign + asgOff[b], (size_t)nSample * nM[b], -1);
+        std::fill_n(logProb + lpOff[b], (size_t)nSample, nan);
+        method[b] = -1;
+        if (logPerm) logPerm[b] = nan;
+        if (nOpen) nOpen[b] = 0;
+        if (nFrontier) nFrontier[b] = 0;
+        if (nEnum) nEnum[b] = 0;
+        if (maxCluster) maxCluster[b] = 0;
+    };
+    auto round = [&](const QmapHostRound &q) -> int {
+        const std::vector<int> &idx = *q.idx;
+        const int n = q.n, maxKeep = q.maxKeep, maxCol = q.maxCol;
+        hipError_t e;
+        KB_TRY(kbest_reserve_quadric_map_sample_dev(ctx, n, q.maxMap, maxKeep, maxCol, nSample));
+        const QmapLayout L = qmap_layout(n, q.maxMap, maxKeep, maxCol);
+        // the round's draws, frame after frame: asgOff[n] | lpOff[n] | keys[n]; a frame keeps its own key wherever it stands
+        std::vector<int64_t> off(3 * (size_t)n);
+        int64_t nAsg = 0;
+        for (int j = 0; j < n; j++) {
+            off[j] = nAsg;
+            off[n + j] = (int64_t)j * nSample;
+            off[2 * (size_t)n + j] = (int64_t)(frameKey ? frameKey[idx[j]] : (uint64_t)idx[j]);
+            nAsg += (int64_t)nSample * nM[idx[j]];
+        }
+        DevBuf dRows, dCost, dAsg, dLp, dOff;
+        if ((e = dRows.alloc(ctx, (size_t)n * maxKeep * 4)) != hipSuccess || (e = dCost.alloc(ctx, (size_t)n * L.costStride * 8)) != hipSuccess ||
+            (e = dAsg.alloc(ctx, (size_t)nAsg * 4)) != hipSuccess || (e = dLp.alloc(ctx, (size_t)n * nSample * 8)) != hipSuccess ||
+            (e = dOff.alloc(ctx, off.size() * 8)) != hipSuccess)
+            return fail(ctx, KBEST_ERR_NOMEM, "kbest_quadric_map_sample_assoc_batch_f64: device buffers", e);
+        HIP_TRY(ctx, hipMemcpy(dOff.p, off.data(), off.size() * 8, hipMemcpyHostToDevice));
+        const int64_t *d_off = dOff.as<int64_t>();
+        KB_TRY(kbest_quadric_map_sample_assoc_batch_f64_dev(
+            ctx, n, q.maxMap, maxKeep, maxCol, q.d_mapMean, q.d_mapCov, q.d_landOff, q.d_nL, q.d_measMean, q.d_measCov, q.d_measOff, q.d_nM,
+            gate, maxExact, maxWidth, nSample, seed, sampleBase, reinterpret_cast<const uint64_t *>(d_off + 2 * (size_t)n), q.d_nKeep,
+            dRows.as<int32_t>(), dCost.as<double>(), dAsg.as<int32_t>(), d_off, dLp.as<double>(), d_off + n, q.d_logPerm, q.d_method,
+            q.d_nOpen, q.d_nFrontier, q.d_maxCluster, nullptr));
+        HIP_TRY(ctx, hipStreamSynchronize(q.s));
+        std::vector<int32_t> rows((size_t)n * maxKeep), ints((size_t)n * 4), ha((size_t)nAsg), en(n, 0);
+        std::vector<double> hl((size_t)n * nSample), lp(n);
+        HIP_TRY(ctx, hipMemcpy(rows.data(), dRows.p, rows.size() * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(ha.data(), dAsg.p, ha.size() * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(hl.data(), dLp.p, hl.size() * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(lp.data(), q.d_logPerm, (size_t)n * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(ints.data(), q.d_method, (size_t)n * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(ints.data() + n, q.d_nOpen, (size_t)n * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(ints.data() + 2 * (size_t)n, q.d_nFrontier, (size_t)n * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(ints.data() + 3 * (size_t)n, q.d_maxCluster, (size_t)n * 4, hipMemcpyDeviceToHost));
+        // the frames with an open cluster the frontier sampler did not take, where the enumeration could: one copy of the compact blocks
+        std::vector<int> fwd;
+        for (int j = 0; j < n; j++)
+            if (ints[j] == -1 && k >= 1) fwd.push_back(j);
+        if (!fwd.empty()) {
+            std::vector<double> cc((size_t)n * L.costStride);
+            HIP_TRY(ctx, hipMemcpy(cc.data(), dCost.p, cc.size() * 8, hipMemcpyDeviceToHost));
+            dCost.release();
+            dAsg.release();
+            dLp.release();
+            dRows.release();
+            const size_t nf = fwd.size();
+            std::vector<int32_t> fL(nf), fM(nf), fi(5 * nf);
+            std::vector<int64_t> fco(nf), fao(nf), flo(nf);
+            std::vector<uint64_t> fkey(nf);
+            std::vector<double> flp(nf);
+            for (size_t i = 0; i < nf; i++) {
+                const int j = fwd[i];
+                fL[i] = nKeep[idx[j]];
+                fM[i] = nM[idx[j]];
+                fco[i] = (int64_t)j * L.costStride;
+                fao[i] = off[j];
+                flo[i] = off[n + j];
+                fkey[i] = (uint64_t)off[2 * (size_t)n + j];
+            }
+            KB_TRY(kbest_hybrid_sample_assoc_batch_f64(ctx, (int)nf, fL.data(), fM.data(), cc.data(), fco.data(), 0, k, maxExact, maxWidth,
+                                                       nSample, seed, sampleBase, fkey.data(), ha.data(), fao.data(), hl.data(), flo.data(),
+                                                       flp.data(), fi.data(), fi.data() + nf, fi.data() + 2 * nf, fi.data() + 3 * nf,
+                                                       fi.data() + 4 * nf));
+            for (size_t i = 0; i < nf; i++) {
+                const int j = fwd[i], b = idx[j], nk = nKeep[b];
+                ints[j] = fi[i];
+                ints[n + j] = fi[nf + i];
+                ints[2 * (size_t)n + j] = fi[2 * nf + i];
+                en[j] = fi[3 * nf + i];
+                ints[3 * (size_t)n + j] = fi[4 * nf + i];
+                lp[j] = flp[i];
+                // compact rows to the rows of the raw block, as qmap_sample_rows_kernel has done for the other frames
+                const int32_t *r = rows.data() + (size_t)j * maxKeep;
+                int32_t *a = ha.data() + off[j];
+                for (size_t t = 0; t < (size_t)nSample * nM[b]; t++)
+                    if (a[t] >= 0) a[t] = a[t] < nk ? r[a[t]] : nL[b] + (a[t] - nk);
+            }
+        }
+        for (int j = 0; j < n; j++) {
+            const int b = idx[j];
+            memcpy(assign + asgOff[b], ha.data() + off[j], (size_t)nSample * nM[b] * 4);
+            memcpy(logProb + lpOff[b], hl.data() + off[n + j], (size_t)nSample * 8);
+            method[b] = ints[j];
+            if (nOpen) nOpen[b] = ints[n + j];
+            if (nFrontier) nFrontier[b] = ints[2 * (size_t)n + j];
+            if (maxCluster) maxCluster[b] = ints[3 * (size_t)n + j];
+            if (nEnum) nEnum[b] = en[j];
+            if (logPerm) logPerm[b] = lp[j];
+        }
+        return KBEST_OK;
+    };
+    return qmap_host_rounds(ctx, who, B, nMap, mapMean, mapCov, landOff, nL, nM, measMean, measCov, gate, {asgOff, lpOff}, nKeep, refuse,
+                            round);
 }
 
 int kbest_bruteforce_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,

@@ -38,5 +38,23 @@ hipError_t launch_quadric_map_fill(const QuadricMapParams &p, hipStream_t stream
 hipError_t launch_quadric_map_expand(const QuadricMapParams &p, hipStream_t stream);  // probs
 hipError_t quadric_map_kernel_usage(int which, int *vgprs, int *scratchBytes, int *ldsBytes);
 
+// kbest_quadric_map_sample.hip: the draws of the sampler on the compact blocks, rewritten in place from compact rows to the rows of
+// the notional raw (nL + nM) x nM block (kbest_c.h, "Joint associations from quadrics").  Workgroup b * nTiles + tile.
+struct QuadricMapSampleParams {
+    const long long *landOff, *measOff; // [B] as QuadricMapParams': with nL and nM they say whether the launch takes the frame
+    const int *nL, *nM;                 // [B]
+    int B, maxMap, maxKeep, maxCol;
+    int nTiles;                         // workgroups per frame: a grid-stride loop over the frame's nSample * nM elements
+    int nSample;
+    const int *nKeep;                   // [B] the true count of kept rows; beyond maxKeep: -1s and NaNs
+    const int *rowIdx;                  // [B][maxKeep]
+    int *assign;                        // in and out: frame b's [nSample][nM] at asgOff[b]
+    const long long *asgOff;
+    double *logProb;                    // frame b's [nSample] at lpOff[b]: written only where nKeep > maxKeep
+    const long long *lpOff;
+};
+hipError_t launch_quadric_map_sample_rows(const QuadricMapSampleParams &p, hipStream_t stream);
+hipError_t quadric_map_sample_kernel_usage(int *vgprs, int *scratchBytes, int *ldsBytes);
+
 }  // namespace kb
 #endif

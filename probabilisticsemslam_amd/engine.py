@@ -72,6 +72,8 @@ C_ABI_SYMBOLS = (
     "kbest_bb_costs_f64",
     "kbest_reserve_quadric_map_dev", "kbest_quadric_map_probs_batch_f64_dev", "kbest_quadric_map_probs_batch_f64",
     "kbest_quadric_map_kernel_usage",
+    "kbest_reserve_quadric_map_sample_dev", "kbest_quadric_map_sample_assoc_batch_f64_dev", "kbest_quadric_map_sample_assoc_batch_f64",
+    "kbest_quadric_map_sample_kernel_usage",
 )
 KBEST_MULTI_STAMPS = 6
 KBEST_MULTI_BATCH, KBEST_MULTI_SUBTREE = 0, 1
@@ -249,6 +251,16 @@ def load_library():
         lib.kbest_quadric_map_probs_batch_f64.argtypes = [vp, C.c_int, C.c_int, dp, dp, i64p, i32p, i32p, dp, dp, C.c_double, C.c_int,
                                                           C.c_int, C.c_int, C.c_int, dp, i64p, dp, i32p, i32p, i32p, i32p, i32p, i32p]
         lib.kbest_quadric_map_kernel_usage.argtypes = [C.c_int, i32p, i32p, i32p]
+    if hasattr(lib, "kbest_quadric_map_sample_assoc_batch_f64_dev"):
+        lib.kbest_reserve_quadric_map_sample_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+        lib.kbest_quadric_map_sample_assoc_batch_f64_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, i64p, i32p, dp, dp,
+                                                                     i64p, i32p, C.c_double, C.c_int, C.c_int, C.c_int, C.c_uint64,
+                                                                     C.c_uint32, i64p, i32p, i32p, dp, i32p, i64p, dp, i64p, dp, i32p,
+                                                                     i32p, i32p, i32p, vp]
+        lib.kbest_quadric_map_sample_assoc_batch_f64.argtypes = [vp, C.c_int, C.c_int, dp, dp, i64p, i32p, i32p, dp, dp, C.c_double,
+                                                                 C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint32, i64p, i32p,
+                                                                 i64p, dp, i64p, dp, i32p, i32p, i32p, i32p, i32p, i32p]
+        lib.kbest_quadric_map_sample_kernel_usage.argtypes = [i32p, i32p, i32p]
     lib.kbest_register_host_buffer.argtypes = [vp, vp, C.c_size_t]
     lib.kbest_unregister_host_buffer.argtypes = [vp, vp]
     _lib = lib
@@ -868,6 +880,64 @@ class KBestEngine:
             _dptr(d_measMean), _dptr(d_measCov), _dptr(d_measOff), _dptr(d_nM), float(gate), int(max_exact), int(max_width),
             _dptr(d_nKeep), _dptr(d_rowIdx), _dptr(d_ccost), _dptr(d_cprobs), _dptr(d_probs), _dptr(d_probOff), _dptr(d_logPerm),
             _dptr(d_method), _dptr(d_nOpen), _dptr(d_nFrontier), _dptr(d_maxCluster), _stream(stream)))
+
+    def quadric_map_sample_assoc(self, map_mean, map_cov, frames, gate, n_sample, k=0, seed=0, frame_key=None, sample_base=0,
+                                 max_exact=16, max_width=16):
+        """kbest_quadric_map_sample_assoc_batch_f64: n_sample joint associations a frame, drawn from the exact posterior whose
+        marginals quadric_map_probs() returns -- map and frames as there.  The compact blocks go through the one-stream sampler, and
+        with k >= 1 what that refuses because of an open cluster through hybrid_sample_assoc(k, condition=False).  Returns (list of
+        int32 [n_sample, nM] arrays: the row of the notional raw (nL + nM) x nM block every measurement takes -- a landmark of the
+        frame's window, or nL + c for the miss of measurement c --, list of logProb [n_sample], logPerm[B], method[B]: 0 all exact,
+        1 / 2 enumerated, -1 refused, -2 infeasible (assign -1, logProb NaN), nKeep[B], nOpen[B], nFrontier[B], nEnum[B],
+        maxCluster[B])."""
+        B = len(frames)
+        mm = np.ascontiguousarray(np.asarray(map_mean, np.float64).reshape(-1, 3))
+        mc = np.ascontiguousarray(np.asarray(map_cov, np.float64).reshape(-1, 9))
+        if len(mm) != len(mc):
+            raise KBestError("quadric_map_sample_assoc: map_mean and map_cov differ in length")
+        landOff = np.array([f[0] for f in frames], np.int64)
+        nL = np.array([f[1] for f in frames], np.int32)
+        nM = np.array([len(f[2]) for f in frames], np.int32)
+        cat = lambda i, w: np.ascontiguousarray(np.concatenate([np.zeros((0, w))] + [np.asarray(f[i], np.float64).reshape(-1, w) for f in frames]))  # noqa: E731
+        zm, zc = cat(2, 3), cat(3, 9)
+        n_sample, asgOff, lpOff, assign, logp, key = _pack_draws(nM, B, n_sample, frame_key, "quadric_map_sample_assoc")
+        ints = np.zeros((6, max(B, 1)), np.int32)  # method | nKeep | nOpen | nFrontier | nEnum | maxCluster
+        logPerm = np.zeros(max(B, 1), np.float64)
+        self._check(self.lib.kbest_quadric_map_sample_assoc_batch_f64(
+            self.ctx, B, len(mm), _ptr(mm), _ptr(mc), _ptr(landOff), _ptr(nL), _ptr(nM), _ptr(zm), _ptr(zc), float(gate), int(k),
+            int(max_exact), int(max_width), n_sample, int(seed), int(sample_base), _ptr(key), _ptr(assign), _ptr(asgOff), _ptr(logp),
+            _ptr(lpOff), _ptr(logPerm), _ptr(ints[0]), _ptr(ints[1]), _ptr(ints[2]), _ptr(ints[3]), _ptr(ints[4]), _ptr(ints[5])))
+        return (*_split_draws(assign, asgOff, logp, lpOff, nM, n_sample), logPerm[:B].copy()) + tuple(ints[i, :B].copy() for i in range(6))
+
+    def reserve_quadric_map_sample_dev(self, B, maxMap, maxKeep, maxCol, n_sample):
+        """kbest_reserve_quadric_map_sample_dev: everything quadric_map_sample_assoc_dev needs besides the caller's buffers, sized
+        from the five numbers alone (a reservation never shrinks)."""
+        self._check(self.lib.kbest_reserve_quadric_map_sample_dev(self.ctx, int(B), int(maxMap), int(maxKeep), int(maxCol), int(n_sample)))
+
+    def quadric_map_sample_assoc_dev(self, B, maxMap, maxKeep, maxCol, d_mapMean, d_mapCov, d_landOff, d_nL, d_measMean, d_measCov,
+                                     d_measOff, d_nM, gate, n_sample, d_nKeep, d_rowIdx, d_assign, d_asgOff, d_logProb, d_lpOff, d_method,
+                                     d_ccost=None, d_logPerm=None, d_nOpen=None, d_nFrontier=None, d_maxCluster=None, seed=0,
+                                     sample_base=0, d_frameKey=None, max_exact=16, max_width=16, stream=None, reserve=True):
+        """kbest_quadric_map_sample_assoc_batch_f64_dev on torch CUDA tensors (or raw addresses), asynchronous on `stream` (a raw
+        hipStream_t integer): from quadrics against one resident map to n_sample joint associations a frame without a host read, a
+        synchronise or an allocation.  The map, frames, d_nKeep, d_rowIdx and d_ccost as in quadric_map_probs_dev; d_assign (int32)
+        at d_asgOff[b] [n_sample][nM]: rows of the notional raw block; d_logProb (float64) at d_lpOff[b] [n_sample]; d_frameKey int64
+        / uint64 [B] or None (frame b: b).  d_method int32 [B] is required.  reserve=False: the caller has called
+        reserve_quadric_map_sample_dev (timed loops, graph capture; the C entry never allocates)."""
+        if reserve:
+            self.reserve_quadric_map_sample_dev(B, maxMap, maxKeep, maxCol, n_sample)
+        self._check(self.lib.kbest_quadric_map_sample_assoc_batch_f64_dev(
+            self.ctx, int(B), int(maxMap), int(maxKeep), int(maxCol), _dptr(d_mapMean), _dptr(d_mapCov), _dptr(d_landOff), _dptr(d_nL),
+            _dptr(d_measMean), _dptr(d_measCov), _dptr(d_measOff), _dptr(d_nM), float(gate), int(max_exact), int(max_width),
+            int(n_sample), int(seed), int(sample_base), _dptr(d_frameKey), _dptr(d_nKeep), _dptr(d_rowIdx), _dptr(d_ccost),
+            _dptr(d_assign), _dptr(d_asgOff), _dptr(d_logProb), _dptr(d_lpOff), _dptr(d_logPerm), _dptr(d_method), _dptr(d_nOpen),
+            _dptr(d_nFrontier), _dptr(d_maxCluster), _stream(stream)))
+
+    def quadric_map_sample_kernel_usage(self):
+        """(registers, scratch bytes, static LDS bytes) of the kernel that maps compact rows to raw rows."""
+        v = np.zeros(3, np.int32)
+        self._check(self.lib.kbest_quadric_map_sample_kernel_usage(_ptr(v[0:1]), _ptr(v[1:2]), _ptr(v[2:3])))
+        return tuple(int(x) for x in v)
 
     @staticmethod
     def _pack_boxes(boxesL, boxesR):
