@@ -104,6 +104,23 @@ struct WeightParams {
     int kUse;                 // > 0: only the first kUse solutions of a problem are weighed (its table holds k >= kUse slots)
 };
 
+// Dynamic LDS of weights_kernel (launch_weights sets chunk, ldsAcc and accBytes from it): weights and row maps of one chunk of
+// solutions, and -- when it fits 96 KiB with them -- the [maxCol][solveRows] accumulator table
+struct WeightsLds { int chunk, ldsAcc; long long accBytes; size_t total; };
+inline WeightsLds weights_lds_plan(int maxCol, int solveRows)
+{
+    WeightsLds w;
+    int chunk = 8192 / (maxCol > 0 ? maxCol : 1);
+    chunk = chunk > 256 ? 256 : (chunk < 8 ? 8 : chunk);
+    const size_t base = (size_t)chunk * 8 + (size_t)chunk * maxCol * 4;
+    const size_t accWant = (size_t)maxCol * (size_t)(solveRows > 0 ? solveRows : 1) * 8;
+    w.chunk = chunk;
+    w.ldsAcc = (base + accWant <= 96 * 1024) ? 1 : 0;
+    w.accBytes = w.ldsAcc ? (long long)accWant : 0;
+    w.total = ((base + (w.ldsAcc ? accWant : 0)) + 15) & ~(size_t)15;
+    return w;
+}
+
 // Bytes of one saved hypothesis: u[D] v[D] (fp64), row4col[D] col4row[D] (u8),
 // forbidden-row mask, gain, activeCol.
 __host__ __device__ inline long long state_stride(int maxRow)
@@ -151,6 +168,39 @@ __host__ __device__ inline Lds lds_layout(int maxRow, int k, int spec, int nWave
     L.total = (o + 15) & ~15;
     return L;
 }
+
+// Sizes around a launch of the 64-row kernel, for the kernel's host build (tests/cpp/engine_host.cpp).  They restate, line for line,
+// what the entry computes (kbest_capi.cpp: states_need, p.statesPerProblem, SplitLayout, relay_plan's image, relay_reserve's words).
+// The entry keeps its own text for now: its compiled code is to stay the parent's while the GPU fault of NOTES sections 34, 35 and
+// 37 is unexplained; it should call these once that is settled.
+// State slots of one matrix: the lazy region (k + extraStates: the root and the candidates that are re-solved when selected) and
+// the eager region behind it (children kept in full when they are found).
+inline int engine_states_per_problem(int k, int extraStates, int eagerStates) { return k + extraStates + eagerStates; }
+// Bytes of the work space of a (B, maxRow, k) launch -- saved hypotheses, then the slot -> state table, then 256 spare bytes -- and
+// where the table starts in it.
+inline size_t engine_states_need(int B, int maxRow, int k, int extraStates, int eagerStates, size_t *slotOff)
+{
+    const size_t nStates = (size_t)B * (size_t)engine_states_per_problem(k, extraStates, eagerStates) * (size_t)state_stride(maxRow);
+    if (slotOff) *slotOff = (nStates + 127) & ~(size_t)127;
+    return nStates + (size_t)B * (size_t)slot_table_stride(k) * 2 + 256;
+}
+// per-share result tables [S][B][...] + one shared threshold per matrix of a split launch
+struct SplitLayout {
+    size_t offGain, offR4C, offNf, offT, bytes;
+    SplitLayout(int B, int S, int k, int maxCol)
+    {
+        auto up = [](size_t x) { return (x + 127) & ~(size_t)127; };
+        offGain = 0;
+        offR4C = up((size_t)S * B * k * 8);
+        offNf = offR4C + up((size_t)S * B * k * maxCol * 4);
+        offT = offNf + up((size_t)S * B * 4);
+        bytes = offT + up((size_t)B * 8);
+    }
+};
+// relay launches: bytes of one matrix' LDS image in HBM, and of the three arrays of words (pieces done, pieces claimed, workgroups
+// gone: quarters of one buffer)
+inline size_t relay_image_bytes(int ldsBytes) { return ((size_t)ldsBytes + 16 + 127) & ~(size_t)127; }
+inline size_t relay_words_bytes(int B) { return (size_t)B * 16; }
 
 // computeQuadricCostMatrix inputs: per frame nL landmark and nM measurement (mean[3], cov[3][3]) pairs
 struct QuadricParams {

@@ -49,6 +49,22 @@
 #include "kbest_wave.h"
 #include "kbest_lap.h"
 
+#ifndef KB_DYNAMIC_LDS  // (tests/cpp/engine_host.cpp runs these lines on the host, on a heap block of exactly the planned size)
+#define KB_DYNAMIC_LDS(name) extern __shared__ __attribute__((aligned(16))) unsigned char name[]
+#endif
+// The places written in assembly have a C++ restatement for the host build beside them (HIP_ON_HOST_H: tests/cpp/hip_on_host.h);
+// the empty register constraints have none.  KB_WAIT_VMCNT0: this wave's global stores have arrived.
+#ifndef HIP_ON_HOST_H
+#define KB_WAIT_VMCNT0() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+typedef double2 fresh2;
+#else
+#define KB_WAIT_VMCNT0() emu_waitcnt()
+// Two fresh gains per read in the merge.  lds_layout's offFreshG is a multiple of 8 but, where maxRow * (maxRow | 1) + spec * nodeStride / 8
+// is odd (8 x 8 with one hypothesis per round), not of 16: the device then reads the pairs off their natural alignment -- right
+// values, replayed reads (NOTES section 37) --, which the host's sanitizer would stop at.  The host reads them as two doubles.
+struct fresh2 { double x, y; };
+#endif
+
 namespace kb {
 
 
@@ -431,7 +447,7 @@ constexpr int min_waves_per_simd(int nw) { return nw <= 12 ? 6 : 4; }
 template <int NW, int EPT, bool RELAY>
 __global__ void __launch_bounds__(NW * 64, min_waves_per_simd(NW)) kbest_kernel(Params p)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    KB_DYNAMIC_LDS(smem);
     constexpr int NT = NW * 64;
     const double INF = d_inf();
     int tid = threadIdx.x;   // (not const: see the top of the round loop)
@@ -474,7 +490,7 @@ __global__ void __launch_bounds__(NW * 64, min_waves_per_simd(NW)) kbest_kernel(
     auto relay_depart = [&]() {
         if constexpr (RELAY) {
             if (threadIdx.x == 0) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (this lane's store to the progress word, if any, has arrived)
+                KB_WAIT_VMCNT0();  // (this lane's store to the progress word, if any, has arrived)
                 if (atomicAdd(p.relayGone + blk, 1u) == gridDim.y - 1u) {
                     __hip_atomic_store(p.relayFlag + blk, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     __hip_atomic_store(p.relayClaim + blk, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -580,7 +596,7 @@ __global__ void __launch_bounds__(NW * 64, min_waves_per_simd(NW)) kbest_kernel(
             }
             red[0] = __longlong_as_double((long long)f);
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            KB_WAIT_VMCNT0();
         }
         __syncthreads();
         const unsigned f = (unsigned)uni32((int)(unsigned)__double_as_longlong(red[0]));  // (uniform: the return below is a scalar branch)
@@ -1043,7 +1059,9 @@ __global__ void __launch_bounds__(NW * 64, min_waves_per_simd(NW)) kbest_kernel(
         // The compiler hoists every cheap expression of the lane number out of this loop (addresses, lane masks: two dozen of
         // them) and then has to spill them at 80 VGPRs: a scratch load per use instead of one or two vector instructions.
         // Making the lane number opaque once per round keeps those expressions where they are used.
+#ifndef HIP_ON_HOST_H
         asm volatile("" : "+v"(lane), "+v"(tid));
+#endif
         KB_T(tRound);
         KB_ACC(7, 1);  // [7] rounds
         if ((t0On && roundNo == 1) || (t1On && roundNo == 2)) {
@@ -1166,7 +1184,11 @@ __global__ void __launch_bounds__(NW * 64, min_waves_per_simd(NW)) kbest_kernel(
                     cv = Ccol[r];
                     const u32 lo = (u32)low | ((u32)(nallow >> r) & 1u);
                     mk = (low & 0xffffffff00000000ull) | lo;
+#ifndef HIP_ON_HOST_H
                     asm("s_bitset1_b64 %0, %1" : "+s"(low) : "s"(jj - a));
+#else
+                    low |= 1ull << (jj - a);
+#endif
                 };
                 auto apply = [&](double cv, double vr, u64 mk) {
                     const double rc = (cv - uc) - vr;  // ((0 + C) - u) - v, cpp:313 with delta = 0
@@ -1213,7 +1235,11 @@ __global__ void __launch_bounds__(NW * 64, min_waves_per_simd(NW)) kbest_kernel(
                         h = h < 0 ? 0 : h;  // -1e-17 from rounding: no information
                         h = sel32(mk, h, KEY_INF_HI);
                         inHi = h < inHi ? h : inHi;
+#ifndef HIP_ON_HOST_H
                         asm("s_bitset1_b64 %0, %1" : "+s"(mk) : "s"(jj - a));
+#else
+                        mk |= 1ull << (jj - a);
+#endif
                     };
                     for (; j2 + 4 <= jEnd; j2 += 4) {  // four independent pairs of LDS reads in flight
                         double cin[4], uj[4];
@@ -1233,6 +1259,9 @@ __global__ void __launch_bounds__(NW * 64, min_waves_per_simd(NW)) kbest_kernel(
         // all parts are in LDS once every part has bumped the node's counter (a wave's LDS operations execute in order).
         bool compactor = false;
         if (myNode >= 0) {
+#ifdef HIP_ON_HOST_H
+            wave_fence();  // (the device's lanes run in lock step: every lane's minima are out before lane 0 bumps the counter; threads do not)
+#endif
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             int old = 0;
             if (lane == 0) old = atomicAdd(&ctrl->partsDone[myNode], 1);
@@ -1260,7 +1289,9 @@ __global__ void __launch_bounds__(NW * 64, min_waves_per_simd(NW)) kbest_kernel(
                 // (the stride is made opaque here: the compiler would otherwise keep the reciprocal of this division in a register
                 //  across the whole round loop -- and spill it -- for a test that only the root of a sharded run ever makes)
                 int st = rcStride;
+#ifndef HIP_ON_HOST_H
                 asm volatile("" : "+s"(st));
+#endif
                 live = live && ((int)colOf[c & 63] % st) == rcOffset;
             }
             const u64 key = lbKey[myNode * 64 + lane];
@@ -1334,7 +1365,9 @@ __global__ void __launch_bounds__(NW * 64, min_waves_per_simd(NW)) kbest_kernel(
                 // ONE wait for the three loads, here: the stores below are predicated, and behind a store that may or may not have
                 // been issued the compiler can only wait for a loaded register by waiting for everything, the store's
                 // acknowledgement included
+#ifndef HIP_ON_HOST_H
                 asm volatile("" : "+v"(rv), "+v"(cv));
+#endif
                 if (lane < M) put_index(p.row4col, (outBase + sOut) * p.ldCol + colOf[lane], rv, tabI8);
                 if (c4rOn && lane < N)
                     put_index(p.col4row, (outBase + sOut) * p.ldRow + lane, (rect && cv == 255) ? -1 : (cv < M ? (int)colOf[cv] : cv), tabI8);  // unassigned row (cpp:134)
@@ -1566,10 +1599,10 @@ __global__ void __launch_bounds__(NW * 64, min_waves_per_simd(NW)) kbest_kernel(
                 const double g = PG[head + i];
                 int pos = i;
                 {   // four fresh gains per pair of 16-byte broadcast reads: the loop is latency, not arithmetic
-                    const double2 *f2 = reinterpret_cast<const double2 *>(freshG);
+                    const fresh2 *f2 = reinterpret_cast<const fresh2 *>(freshG);
                     int j = 0;
                     for (; j + 4 <= nFresh; j += 4) {
-                        const double2 a = f2[j >> 1], b = f2[(j >> 1) + 1];
+                        const fresh2 a = f2[j >> 1], b = f2[(j >> 1) + 1];
                         pos += ((a.x < g) ? 1 : 0) + ((a.y < g) ? 1 : 0) + ((b.x < g) ? 1 : 0) + ((b.y < g) ? 1 : 0);
                     }
                     for (; j < nFresh; j++) pos += (freshG[j] < g) ? 1 : 0;
@@ -1594,10 +1627,10 @@ __global__ void __launch_bounds__(NW * 64, min_waves_per_simd(NW)) kbest_kernel(
             }
             int pos = lo;
             {
-                const double2 *f2 = reinterpret_cast<const double2 *>(freshG);
+                const fresh2 *f2 = reinterpret_cast<const fresh2 *>(freshG);
                 int nEq = 0, j2 = 0;
                 for (; j2 + 4 <= nFresh; j2 += 4) {
-                    const double2 a = f2[j2 >> 1], b = f2[(j2 >> 1) + 1];
+                    const fresh2 a = f2[j2 >> 1], b = f2[(j2 >> 1) + 1];
                     pos += ((a.x < g) ? 1 : 0) + ((a.y < g) ? 1 : 0) + ((b.x < g) ? 1 : 0) + ((b.y < g) ? 1 : 0);
                     nEq += ((a.x == g) ? 1 : 0) + ((a.y == g) ? 1 : 0) + ((b.x == g) ? 1 : 0) + ((b.y == g) ? 1 : 0);
                 }
@@ -1868,11 +1901,11 @@ __global__ void __launch_bounds__(NW * 64, min_waves_per_simd(NW)) kbest_kernel(
         // (a workgroup barrier alone does not wait for them), then one lane writes the XCD's L2 back and, once THAT is done,
         // raises the flag (the wait is spelled in asm: the compiler drops its own behind a release fence when it believes the
         // wave has nothing outstanding)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        KB_WAIT_VMCNT0();
         __syncthreads();
         if (tid == 0) {
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            KB_WAIT_VMCNT0();
             __hip_atomic_store(p.relayFlag + blk, (unsigned)piece + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         relay_depart();
@@ -1978,7 +2011,7 @@ __global__ void __launch_bounds__(64) condition_kernel(CondParams p)
 // assignment.cpp:68-74): output row stride nLout[b] + 1.
 __global__ void __launch_bounds__(256) weights_kernel(WeightParams p)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char wsm[];
+    KB_DYNAMIC_LDS(wsm);
     constexpr int NT = 256;
     const int b = blockIdx.x, tid = threadIdx.x;
     const int nL = p.nL[b], nM = p.nM[b];
@@ -2111,15 +2144,12 @@ hipError_t launch_condition(const CondParams &p, int B, hipStream_t stream)
 hipError_t launch_weights(const WeightParams &p0, int B, hipStream_t stream)
 {
     WeightParams p = p0;
-    // LDS: weights and row maps of one chunk of solutions, and -- when it fits -- the accumulator table
-    int chunk = 8192 / (p.maxCol > 0 ? p.maxCol : 1);
-    chunk = chunk > 256 ? 256 : (chunk < 8 ? 8 : chunk);
-    const size_t base = (size_t)chunk * 8 + (size_t)chunk * p.maxCol * 4;
-    const size_t accWant = (size_t)p.maxCol * (size_t)(p.solveRows > 0 ? p.solveRows : 1) * 8;
-    p.chunk = chunk;
-    p.ldsAcc = (base + accWant <= 96 * 1024) ? 1 : 0;
-    p.accBytes = p.ldsAcc ? (long long)accWant : 0;
-    const size_t lds = ((base + (p.ldsAcc ? accWant : 0)) + 15) & ~(size_t)15;
+    // LDS: weights and row maps of one chunk of solutions, and -- when it fits -- the accumulator table (weights_lds_plan, kbest_engine.h)
+    const WeightsLds wl = weights_lds_plan(p.maxCol, p.solveRows);
+    p.chunk = wl.chunk;
+    p.ldsAcc = wl.ldsAcc;
+    p.accBytes = wl.accBytes;
+    const size_t lds = wl.total;
     static std::atomic<size_t> granted{0};
     if (lds > granted.load(std::memory_order_relaxed)) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(weights_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

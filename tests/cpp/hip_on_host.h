@@ -19,7 +19,8 @@
 #define __host__
 #define __forceinline__ inline
 #define __shared__ static
-#define __launch_bounds__(x)
+#define __constant__
+#define __launch_bounds__(...)
 typedef unsigned long long u64;
 typedef unsigned u32;
 struct dim3 { int x = 1, y = 1, z = 1; dim3(int a = 1, int b = 1, int c = 1) : x(a), y(b), z(c) {} };
@@ -102,12 +103,22 @@ inline int __shfl_down(int x, int d) { const int l = threadIdx.x & 63; return em
 inline int __shfl_up(int x, int d) { const int l = threadIdx.x & 63; return emu_xchg(x, l - d >= 0 ? l - d : l); }
 inline int __builtin_amdgcn_readlane(int x, int l) { return emu_xchg(x, l & 63); }
 inline int __builtin_amdgcn_readfirstlane(int x) { return emu_xchg(x, 0); }  // (every lane of the wave is active wherever the kernels call it)
-// DPP with a quad_perm control word (below 0x100: two bits per lane of the quad), every row and bank enabled
-inline int __builtin_amdgcn_update_dpp(int, int x, int ctrl, int rowMask, int bankMask, bool)
+// DPP, every bank enabled: a quad_perm control word (below 0x100: two bits per lane of the quad), row_shr:n (0x111 .. 0x11F),
+// row_bcast:15 (0x142) and row_bcast:31 (0x143).  A lane whose row is not in rowMask keeps `old`; a lane whose source lies outside
+// its row (row_shr) or does not exist (the broadcasts into rows 0 / 0 and 1) reads 0 with boundCtrl and keeps `old` without.
+inline int __builtin_amdgcn_update_dpp(int old, int x, int ctrl, int rowMask, int bankMask, bool boundCtrl)
 {
-    if (ctrl < 0 || ctrl >= 0x100 || rowMask != 0xF || bankMask != 0xF) abort();
-    const int l = threadIdx.x & 63;
-    return emu_xchg(x, (l & ~3) | ((ctrl >> (2 * (l & 3))) & 3));
+    if (bankMask != 0xF) abort();
+    const int l = threadIdx.x & 63, row = l >> 4;
+    int src = -1;
+    if (ctrl >= 0 && ctrl < 0x100) src = (l & ~3) | ((ctrl >> (2 * (l & 3))) & 3);
+    else if (ctrl >= 0x111 && ctrl <= 0x11F) src = (l & 15) >= (ctrl & 15) ? l - (ctrl & 15) : -1;
+    else if (ctrl == 0x142) src = row >= 1 ? row * 16 - 1 : -1;
+    else if (ctrl == 0x143) src = row >= 2 ? 31 : -1;
+    else abort();
+    const int got = emu_xchg(x, src >= 0 ? src : l);
+    if (!((rowMask >> row) & 1)) return old;
+    return src >= 0 ? got : (boundCtrl ? 0 : old);
 }
 inline u32 __builtin_amdgcn_mbcnt_lo(u32 mask, u32 base) { const int l = threadIdx.x & 63; return base + (u32)__builtin_popcount(l >= 32 ? mask : (mask & ((1u << l) - 1u))); }
 inline u32 __builtin_amdgcn_mbcnt_hi(u32 mask, u32 base) { const int l = threadIdx.x & 63; return base + (u32)__builtin_popcount(l <= 32 ? 0u : (mask & ((1u << (l - 32)) - 1u))); }
@@ -115,17 +126,32 @@ inline bool __builtin_amdgcn_inverse_ballot_w64(u64 mask) { return ((mask >> (th
 inline u64 __builtin_amdgcn_read_exec() { return ~0ull; }
 #define __builtin_amdgcn_fence(order, scope) __atomic_thread_fence(order)
 #define __HIP_MEMORY_SCOPE_AGENT 0
+#define __HIP_MEMORY_SCOPE_WORKGROUP 0
 #define __hip_atomic_load(ptr, order, scope) __atomic_load_n(ptr, order)
 #define __hip_atomic_store(ptr, value, order, scope) __atomic_store_n(ptr, value, order)
+#define __hip_atomic_fetch_add(ptr, value, order, scope) __atomic_fetch_add(ptr, value, order)
+inline void __builtin_amdgcn_s_sleep(int) { std::this_thread::yield(); }
+inline void emu_waitcnt() { __atomic_thread_fence(__ATOMIC_SEQ_CST); }  // s_waitcnt vmcnt(0): this thread's stores are out
 inline int atomicAdd(int *p, int v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
+inline unsigned atomicAdd(unsigned *p, unsigned v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
 inline int atomicSub(int *p, int v) { return __atomic_fetch_sub(p, v, __ATOMIC_RELAXED); }
 inline int atomicOr(int *p, int v) { return __atomic_fetch_or(p, v, __ATOMIC_RELAXED); }
+inline unsigned long long atomicOr(unsigned long long *p, unsigned long long v) { return __atomic_fetch_or(p, v, __ATOMIC_RELAXED); }
 inline int atomicMin(int *p, int v)
 {
     int old = __atomic_load_n(p, __ATOMIC_RELAXED);
     while (v < old && !__atomic_compare_exchange_n(p, &old, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) { }
     return old;
 }
+template <class T>
+inline T emu_atomic_min(T *p, T v)
+{
+    T old = __atomic_load_n(p, __ATOMIC_RELAXED);
+    while (v < old && !__atomic_compare_exchange_n(p, &old, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) { }
+    return old;
+}
+inline unsigned atomicMin(unsigned *p, unsigned v) { return emu_atomic_min(p, v); }
+inline unsigned long long atomicMin(unsigned long long *p, unsigned long long v) { return emu_atomic_min(p, v); }
 struct alignas(16) double2 { double x, y; };
 struct alignas(16) float4 { float x, y, z, w; };
 struct alignas(16) int4 { int x, y, z, w; };
@@ -136,6 +162,9 @@ inline int __double2hiint(double d) { u64 b; memcpy(&b, &d, 8); return (int)(u32
 inline int __double2loint(double d) { u64 b; memcpy(&b, &d, 8); return (int)(u32)b; }
 inline double __hiloint2double(int hi, int lo) { const u64 b = ((u64)(u32)hi << 32) | (u32)lo; double d; memcpy(&d, &b, 8); return d; }
 inline float __int_as_float(int i) { float f; memcpy(&f, &i, 4); return f; }
+inline long long __double_as_longlong(double d) { long long v; memcpy(&v, &d, 8); return v; }
+inline float __double2float_ru(double x) { float f = (float)x; return (double)f < x ? nextafterf(f, INFINITY) : f; }   // round up
+inline float __double2float_rd(double x) { float f = (float)x; return (double)f > x ? nextafterf(f, -INFINITY) : f; }  // round down
 namespace kb {
 constexpr int KEY_INF_HI = 0x7ff00000;  // kbest_wave.h's keys
 inline void to_key(double x, int &khi, u32 &klo)
@@ -214,8 +243,8 @@ inline double dpp_f64(double x)
 }
 }
 // block.x threads (whole waves) and block.x / 64 wave barriers, whatever the program launches; the workgroups of the launch one
-// after another on the same threads, each with a fresh block of dynamic LDS (the barriers around a workgroup: its static LDS and
-// hostLds are the next one's).  lds = 0 is the normal case: only sample_host and lane_host launch with dynamic LDS.
+// after another (a two-dimensional grid: x fastest) on the same threads, each with a fresh block of dynamic LDS (the barriers around a workgroup: its static LDS and
+// hostLds are the next one's).  lds = 0 is the normal case: only sample_host, lane_host and engine_host launch with dynamic LDS.
 template <class K, class... A>
 void emu_launch(K kernel, dim3 grid, dim3 block, int lds, A... args)
 {
@@ -233,17 +262,18 @@ void emu_launch(K kernel, dim3 grid, dim3 block, int lds, A... args)
             threadIdx = dim3(t);
             gridDim = grid;
             blockDim = block;
-            for (int b = 0; b < grid.x; b++) {
-                blockIdx = dim3(b);
-                if (t == 0) {
-                    hostLds = new unsigned char[lds];
-                    emu_fill_bytes(hostLds, (size_t)lds, emuLdsFill, emuLdsSeed + (unsigned long long)b);
+            for (int by = 0; by < grid.y; by++)      // (y outer, x inner: piece j of a relay launch finds piece j - 1 finished)
+                for (int b = 0; b < grid.x; b++) {
+                    blockIdx = dim3(b, by);
+                    if (t == 0) {
+                        hostLds = new unsigned char[lds];
+                        emu_fill_bytes(hostLds, (size_t)lds, emuLdsFill, emuLdsSeed + (unsigned long long)by * (unsigned long long)grid.x + (unsigned long long)b);
+                    }
+                    wgBar->arrive_and_wait();
+                    kernel(args...);
+                    wgBar->arrive_and_wait();
+                    if (t == 0) delete[] hostLds;
                 }
-                wgBar->arrive_and_wait();
-                kernel(args...);
-                wgBar->arrive_and_wait();
-                if (t == 0) delete[] hostLds;
-            }
         });
     for (auto &t : th) t.join();
 }
