@@ -41,6 +41,8 @@
  *        joint associations drawn from the exact posterior of such frames, one walk per cluster (not in the reference)
  *   kbest_quadric_map_sample_assoc_batch_f64 / kbest_quadric_map_sample_assoc_batch_f64_dev / kbest_reserve_quadric_map_sample_dev
  *        the same draws from quadrics against a map of any size, in the rows of the raw block (not in the reference)
+ *   kbest_assoc_factors_f64_dev / kbest_quadric_map_factors_batch_f64_dev / kbest_assoc_factors_batch_f64
+ *        the consumer loop (system.cpp:279-346): thresholded, ordered factor and new-landmark lists from the probabilities
  *
  * Conventions kept from the reference: cost matrices are column-major
  * C[row + col*numRow] with numRow >= numCol (shortestPathCPP.hpp:185-190);
@@ -1078,6 +1080,87 @@ int kbest_quadric_map_sample_assoc_batch_f64(kbest_ctx *ctx, int B, int nMap, co
 /* Diagnostic: registers, scratch bytes and static LDS bytes of the kernel that maps compact rows to raw rows, for
  * tools/bench_quadric_map_sample.py. */
 int kbest_quadric_map_sample_kernel_usage(int32_t *vgprs, int32_t *scratchBytes, int32_t *ldsBytes);
+/*
+ * Factor lists from association probabilities, on the stream (kbest_factors.hip): what the reference's consumer loop makes of a
+ * frame's probabilities (system.cpp:279-346; the window keeps per landmark whether a frame still constrains it,
+ * slidingWindow.cpp:351-460), as a stream compaction on the device instead of a copy of the dense slice and a scan on the host.
+ *
+ *   for m, for q < nL:  if (probs[m][q] < NEW_FACTOR_PROB_THRESH) continue;   two factors, noise BOX_SD / probs[m][q]
+ *   for m:              if (probs[m][nL] > NEW_LANDMARK_THRESH)               a new landmark, noise BOX_SD / probs[m][nL]
+ *   (constsUtils.h:57-59 for the noise, :75-78 for the defaults BOX_SD 3, NEW_LANDMARK_THRESH 0.33, NEW_FACTOR_PROB_THRESH 0.05)
+ *
+ * kbest_assoc_factors_f64_dev takes the output of ANY probability entry.  Frame b has probabilities row-major
+ * [d_nM[b]][d_nSlot[b] + 1] at d_probOff[b] in d_probs.  Slot nSlot is the miss / new-landmark column; slot l < nSlot is the
+ * landmark d_rowIdx[b * rowStride + l] (compact form: d_cprobs, d_rowIdx and d_nKeep of the quadric-map entries) or, with
+ * d_rowIdx NULL, the landmark l (dense form, nSlot = nL).  The map index of a landmark is d_landOff[b] + landmark (d_landOff NULL: 0).
+ *   Factor list:  every (b, m, l) with !(p < factorThresh), in the order b ascending, then m ascending, then l ascending.  rowIdx is
+ *                 ascending, so this is the reference's q order, and the compact and the dense form of a frame give the same list.
+ *                 A struct of arrays: d_fFrame, d_fMeas, d_fLand (int32, the frame-local landmark), d_fMap (int64, may be NULL),
+ *                 d_fProb (the bits of p), d_fSigma = boxSd / p (one IEEE division: the bits of C's BOX_SD / prob; +inf for p = 0).
+ *   New-landmark list:  every (b, m) with P_b[m][nSlot] > newThresh, strictly, in the order b, then m: d_nFrame, d_nMeas, d_nProb,
+ *                 d_nSigma.  The two comparisons are the reference's: p equal to factorThresh is kept, p equal to newThresh is not new.
+ *   Counts:       d_nFactor[b], d_nNew[b] (int32) the TRUE counts; d_factorOff[b], d_newOff[b] (int64) the exclusive prefix sums of
+ *                 the true counts; d_total[2] (int64) the true totals.
+ *   Capacity:     an entry whose position is >= maxFactor (>= maxNew) is not written, and nothing else changes: the caller sees
+ *                 total > capacity and calls again.  Capacity 0 with NULL arrays is a legal counting call.
+ *   Support:      d_support[nSupport] (int32, may be NULL) is zeroed on the stream, then 1 is added per factor at its map index;
+ *                 indices outside [0, nSupport) are not counted.  The value does not depend on the capacities.
+ *   Frames that emit nothing (counts 0):  d_method given and d_method[b] < 0; nM < 1, nM > maxCol, nSlot < 0, nSlot > maxSlot, a
+ *                 negative offset.  A refused frame's slice was never written, and a NaN would pass !(p < t).
+ * The position of every entry is computed (a count pass, an integer prefix pass, an emit pass that recomputes the predicates), so a
+ * frame's entries are the same alone and in any batch; only fFrame and the offsets differ.  No floating-point atomics (the support
+ * is an integer sum, which does not depend on the order), no workgroup waits for another, no host read, synchronise or allocation;
+ * every index into a buffer is 64-bit.
+ * Limits: B >= 0, 1 <= maxCol <= 128, 0 <= maxSlot <= KBEST_QUADRIC_MAP_MAX, B * maxCol < 2^31, thresholds and boxSd not NaN,
+ * capacities and nSupport >= 0, rowStride >= maxSlot where d_rowIdx is given -- else KBEST_ERR_BAD_ARG.
+ * kbest_reserve_assoc_factors_dev(ctx, B, maxCol) reserves the per-(frame, measurement) counts and scan partials (all integer); it
+ * never shrinks.  A call beyond it: KBEST_ERR_NOT_RESERVED, nothing launched.  B = 0: KBEST_OK, the totals 0 and the support
+ * zeroed.  Asynchronous on `stream` (NULL: the context's); two calls on one stream need no synchronise between them.
+ */
+/* (a work space a captured launch holds does not grow: "WORK SPACES UNDER A CAPTURED LAUNCH" at kbest_reserve) */
+int kbest_reserve_assoc_factors_dev(kbest_ctx *ctx, int B, int maxCol);
+int kbest_assoc_factors_f64_dev(kbest_ctx *ctx, int B, int maxSlot, int maxCol, const double *d_probs, const int64_t *d_probOff,
+                                const int32_t *d_nSlot, const int32_t *d_nM, const int32_t *d_rowIdx, int64_t rowStride,
+                                const int64_t *d_landOff, const int32_t *d_method, double factorThresh, double newThresh, double boxSd,
+                                int64_t maxFactor, int32_t *d_fFrame, int32_t *d_fMeas, int32_t *d_fLand, int64_t *d_fMap,
+                                double *d_fProb, double *d_fSigma, int64_t maxNew, int32_t *d_nFrame, int32_t *d_nMeas, double *d_nProb,
+                                double *d_nSigma, int32_t *d_nFactor, int64_t *d_factorOff, int32_t *d_nNew, int64_t *d_newOff,
+                                int64_t *d_total, int32_t *d_support, int64_t nSupport, void *stream);
+/*
+ * The same fused behind kbest_quadric_map_probs_batch_f64_dev, on one stream: the arguments of that entry (its body is unchanged,
+ * d_probs may be NULL, every output has its bits), then the factor arguments.  The factor passes run in compact form on d_cprobs,
+ * d_rowIdx and d_nKeep with d_method, maxSlot = maxKeep, and d_landOff gives the map index.  A frame with nKeep > maxKeep or
+ * method -1 emits nothing.  kbest_reserve_quadric_map_factors_dev calls kbest_reserve_quadric_map_dev and
+ * kbest_reserve_assoc_factors_dev; without either, KBEST_ERR_NOT_RESERVED and nothing is launched.
+ */
+int kbest_reserve_quadric_map_factors_dev(kbest_ctx *ctx, int B, int maxMap, int maxKeep, int maxCol);
+int kbest_quadric_map_factors_batch_f64_dev(kbest_ctx *ctx, int B, int maxMap, int maxKeep, int maxCol, const double *d_mapMean,
+                                            const double *d_mapCov, const int64_t *d_landOff, const int32_t *d_nL,
+                                            const double *d_measMean, const double *d_measCov, const int64_t *d_measOff,
+                                            const int32_t *d_nM, double gate, int maxExact, int maxWidth, int32_t *d_nKeep,
+                                            int32_t *d_rowIdx, double *d_ccost, double *d_cprobs, double *d_probs,
+                                            const int64_t *d_probOff, double *d_logPerm, int32_t *d_method, int32_t *d_nOpen,
+                                            int32_t *d_nFrontier, int32_t *d_maxCluster, double factorThresh, double newThresh,
+                                            double boxSd, int64_t maxFactor, int32_t *d_fFrame, int32_t *d_fMeas, int32_t *d_fLand,
+                                            int64_t *d_fMap, double *d_fProb, double *d_fSigma, int64_t maxNew, int32_t *d_nFrame,
+                                            int32_t *d_nMeas, double *d_nProb, double *d_nSigma, int32_t *d_nFactor,
+                                            int64_t *d_factorOff, int32_t *d_nNew, int64_t *d_newOff, int64_t *d_total,
+                                            int32_t *d_support, int64_t nSupport, void *stream);
+/*
+ * The same from host buffers, synchronous: the dense [nM][nL + 1] slices at probOff[b] that every host probability entry returns
+ * (landOff and method may be NULL) are staged, the device entry runs in dense form, and the lists -- their first
+ * min(total, capacity) entries -- the counts, offsets and support are copied back.  total[2] holds the true totals.  A frame with
+ * nM < 1, nL < 0, a negative offset or method < 0 emits nothing; nM > 128 or nL > KBEST_QUADRIC_MAP_MAX: KBEST_ERR_UNSUPPORTED.
+ */
+int kbest_assoc_factors_batch_f64(kbest_ctx *ctx, int B, const double *probs, const int64_t *probOff, const int32_t *nL,
+                                  const int32_t *nM, const int64_t *landOff, const int32_t *method, double factorThresh,
+                                  double newThresh, double boxSd, int64_t maxFactor, int32_t *fFrame, int32_t *fMeas, int32_t *fLand,
+                                  int64_t *fMap, double *fProb, double *fSigma, int64_t maxNew, int32_t *nFrame, int32_t *nMeas,
+                                  double *nProb, double *nSigma, int32_t *nFactor, int64_t *factorOff, int32_t *nNew, int64_t *newOff,
+                                  int64_t *total, int32_t *support, int64_t nSupport);
+/* Diagnostic: registers, scratch bytes and static LDS bytes of the factor passes (which = 0: count, 1: scan inside a frame, 2: scan
+ * over the frames, 3: emit), for tools/bench_factors.py. */
+int kbest_factors_kernel_usage(int which, int32_t *vgprs, int32_t *scratchBytes, int32_t *ldsBytes);
 /* on = 1: the HOST-buffer association entries of this context (kbest_weights / assoc_probs / bruteforce / quadric_assoc) enumerate
  * their k best in the REFERENCE's own order of operations (the reference-order kernel, as KBEST_FLAG_REFERENCE_ORDER does for
  * kbest_batch_f64): where exactly equal gains straddle slot k the assignments that are weighed are the ones the reference's

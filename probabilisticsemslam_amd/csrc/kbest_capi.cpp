@@ -22,6 +22,7 @@
 #include "kbest_engine.h"
 #include "kbest_table_sample.h"
 #include "kbest_quadric_map.h"
+#include "kbest_factors.h"
 
 namespace kb {
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -235,6 +236,8 @@ struct kbest_ctx {
     DevBufRaw qmapBuf{"quadric map"};  // kbest_quadric_map_probs_batch_f64_dev: tile minima, column minima, ballots, counts, offsets, the
                               // hybrid entry's d_sub and the compact blocks (kbest_reserve_quadric_map_dev; QmapLayout)
     int qmapB = 0, qmapMap = 0, qmapKeep = 0, qmapCol = 0;  // ... the largest of each number reserved so far: what it is sized for
+    DevBufRaw factBuf{"factor list"};  // kbest_assoc_factors_f64_dev: the per-(frame, measurement) counts and scan partials
+    int factB = 0, factCol = 0;        // ... the largest of each number reserved so far (kbest_reserve_assoc_factors_dev)
 };
 
 namespace {
@@ -857,6 +860,7 @@ int kbest_destroy(kbest_ctx *ctx)
     if (ctx->frPlan.p) (void)hipFree(ctx->frPlan.p);
     if (ctx->hybBuf.p) (void)hipFree(ctx->hybBuf.p);
     if (ctx->qmapBuf.p) (void)hipFree(ctx->qmapBuf.p);
+    if (ctx->factBuf.p) (void)hipFree(ctx->factBuf.p);
     if (ctx->hybSampBuf.p) (void)hipFree(ctx->hybSampBuf.p);
     if (ctx->relayFlags.p) (void)hipFree(ctx->relayFlags.p);
     if (ctx->lastEvent) (void)hipEventDestroy(ctx->lastEvent);
@@ -5771,6 +5775,277 @@ int kbest_quadric_map_sample_assoc_batch_f64(kbest_ctx *ctx, int B, int nMap, co
     };
     return qmap_host_rounds(ctx, who, B, nMap, mapMean, mapCov, landOff, nL, nM, measMean, measCov, gate, {asgOff, lpOff}, nKeep, refuse,
                             round);
+}
+
+// ---- factor lists from association probabilities (kbest_factors.hip): the reference's consumer loop (system.cpp:279-346) as a
+//      stream compaction behind any probability entry, and fused behind kbest_quadric_map_probs_batch_f64_dev ----
+// What the caller hands over besides the probabilities: thresholds, capacities, lists, counts, support.
+struct FactorOut {
+    double factorThresh, newThresh, boxSd;
+    int64_t maxFactor;
+    int32_t *fFrame, *fMeas, *fLand;
+    int64_t *fMap;
+    double *fProb, *fSigma;
+    int64_t maxNew;
+    int32_t *nFrame, *nMeas;
+    double *nProb, *nSigma;
+    int32_t *nFactor;
+    int64_t *factorOff;
+    int32_t *nNew;
+    int64_t *newOff, *total;
+    int32_t *support;
+    int64_t nSupport;
+};
+
+static const char FACTOR_ARGS_TEXT[] = ": bad argument (B >= 0, 1 <= maxCol <= 128, 0 <= maxSlot <= KBEST_QUADRIC_MAP_MAX, B * maxCol < 2^31, "
+                                       "thresholds and boxSd not NaN, capacities and nSupport >= 0, rowStride >= maxSlot, a required "
+                                       "pointer is NULL)";
+static int factors_check(kbest_ctx *ctx, const char *who, int B, int maxSlot, int maxCol, bool haveRows, int64_t rowStride, const FactorOut &o)
+{
+    bool bad = B < 0 || maxCol < 1 || maxCol > kb::FACTOR_MAX_COLS || maxSlot < 0 || maxSlot > KBEST_QUADRIC_MAP_MAX ||
+               (long long)B * maxCol > 0x7fffffffLL || o.factorThresh != o.factorThresh || o.newThresh != o.newThresh ||
+               o.boxSd != o.boxSd || o.maxFactor < 0 || o.maxNew < 0 || o.nSupport < 0 || (haveRows && rowStride < maxSlot) || !o.total;
+    bad = bad || (o.maxFactor > 0 && (!o.fFrame || !o.fMeas || !o.fLand || !o.fProb || !o.fSigma));
+    bad = bad || (o.maxNew > 0 && (!o.nFrame || !o.nMeas || !o.nProb || !o.nSigma));
+    bad = bad || (B > 0 && (!o.nFactor || !o.factorOff || !o.nNew || !o.newOff));
+    if (bad) return fail(ctx, KBEST_ERR_BAD_ARG, (std::string(who) + FACTOR_ARGS_TEXT).c_str());
+    return KBEST_OK;
+}
+
+static bool factors_reserved(const kbest_ctx *ctx, int B, int maxCol)
+{
+    return B == 0 || (ctx->factBuf.p && B <= ctx->factB && maxCol <= ctx->factCol);
+}
+
+// bytes of one of the two int32 arrays [B][maxCol] of the work space, 16-byte aligned
+static size_t factors_part(int B, int maxCol) { return ((size_t)B * (size_t)maxCol * 4 + 15) & ~(size_t)15; }
+
+int kbest_reserve_assoc_factors_dev(kbest_ctx *ctx, int B, int maxCol)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    if (B < 0 || maxCol < 1 || maxCol > kb::FACTOR_MAX_COLS || (long long)B * maxCol > 0x7fffffffLL)
+        return fail(ctx, KBEST_ERR_BAD_ARG, "kbest_reserve_assoc_factors_dev: bad argument (B >= 0, 1 <= maxCol <= 128, B * maxCol < 2^31)");
+    if (B == 0) return KBEST_OK;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int nb = std::max(B, ctx->factB), nc = std::max(maxCol, ctx->factCol);  // never shrinks
+    KB_TRY(raw_reserve(ctx, ctx->factBuf, 2 * factors_part(nb, nc)));
+    ctx->factB = nb;
+    ctx->factCol = nc;
+    return KBEST_OK;
+}
+
+// Everything is checked by the caller; the launches alone.
+static int factors_launch(kbest_ctx *ctx, int B, int maxSlot, int maxCol, const double *d_probs, const int64_t *d_probOff,
+                          const int32_t *d_nSlot, const int32_t *d_nM, const int32_t *d_rowIdx, int64_t rowStride,
+                          const int64_t *d_landOff, const int32_t *d_method, const FactorOut &o, hipStream_t s)
+{
+    hold_if_capturing(s, {&ctx->factBuf});
+    kb::FactorParams p;
+    p.probs = d_probs;
+    p.probOff = reinterpret_cast<const long long *>(d_probOff);
+    p.nSlot = d_nSlot;
+    p.nM = d_nM;
+    p.rowIdx = d_rowIdx;
+    p.rowStride = rowStride;
+    p.landOff = reinterpret_cast<const long long *>(d_landOff);
+    p.method = d_method;
+    p.factorThresh = o.factorThresh;
+    p.newThresh = o.newThresh;
+    p.boxSd = o.boxSd;
+    p.B = B;
+    p.maxSlot = maxSlot;
+    p.maxCol = maxCol;
+    p.maxFactor = o.maxFactor;
+    p.maxNew = o.maxNew;
+    p.fFrame = o.fFrame;
+    p.fMeas = o.fMeas;
+    p.fLand = o.fLand;
+    p.fMap = reinterpret_cast<long long *>(o.fMap);
+    p.fProb = o.fProb;
+    p.fSigma = o.fSigma;
+    p.nFrame = o.nFrame;
+    p.nMeas = o.nMeas;
+    p.nProb = o.nProb;
+    p.nSigma = o.nSigma;
+    p.nFactor = o.nFactor;
+    p.nNew = o.nNew;
+    p.factorOff = reinterpret_cast<long long *>(o.factorOff);
+    p.newOff = reinterpret_cast<long long *>(o.newOff);
+    p.total = reinterpret_cast<long long *>(o.total);
+    p.support = o.support;
+    p.nSupport = o.nSupport;
+    unsigned char *h8 = static_cast<unsigned char *>(ctx->factBuf.p);
+    p.rowCnt = reinterpret_cast<int *>(h8);
+    p.rowNew = B > 0 ? reinterpret_cast<int *>(h8 + factors_part(B, maxCol)) : nullptr;
+    const hipError_t e = kb::launch_assoc_factors(p, s);
+    if (e != hipSuccess) return fail(ctx, KBEST_ERR_HIP, "factor list kernel launch", e);
+    return KBEST_OK;
+}
+
+int kbest_assoc_factors_f64_dev(kbest_ctx *ctx, int B, int maxSlot, int maxCol, const double *d_probs, const int64_t *d_probOff,
+                                const int32_t *d_nSlot, const int32_t *d_nM, const int32_t *d_rowIdx, int64_t rowStride,
+                                const int64_t *d_landOff, const int32_t *d_method, double factorThresh, double newThresh, double boxSd,
+                                int64_t maxFactor, int32_t *d_fFrame, int32_t *d_fMeas, int32_t *d_fLand, int64_t *d_fMap,
+                                double *d_fProb, double *d_fSigma, int64_t maxNew, int32_t *d_nFrame, int32_t *d_nMeas, double *d_nProb,
+                                double *d_nSigma, int32_t *d_nFactor, int64_t *d_factorOff, int32_t *d_nNew, int64_t *d_newOff,
+                                int64_t *d_total, int32_t *d_support, int64_t nSupport, void *stream)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    const char *who = "kbest_assoc_factors_f64_dev";
+    const FactorOut o{factorThresh, newThresh, boxSd, maxFactor, d_fFrame, d_fMeas, d_fLand, d_fMap, d_fProb, d_fSigma, maxNew,
+                      d_nFrame, d_nMeas, d_nProb, d_nSigma, d_nFactor, d_factorOff, d_nNew, d_newOff, d_total, d_support, nSupport};
+    KB_TRY(factors_check(ctx, who, B, maxSlot, maxCol, d_rowIdx != nullptr, rowStride, o));
+    if (B > 0 && (!d_probs || !d_probOff || !d_nSlot || !d_nM)) return fail(ctx, KBEST_ERR_BAD_ARG, (std::string(who) + FACTOR_ARGS_TEXT).c_str());
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!factors_reserved(ctx, B, maxCol))
+        return fail(ctx, KBEST_ERR_NOT_RESERVED, "kbest_assoc_factors_f64_dev: call kbest_reserve_assoc_factors_dev first");
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    KB_TRY(order_behind_last(ctx, s));
+    const Launched mark{ctx, s};
+    return factors_launch(ctx, B, maxSlot, maxCol, d_probs, d_probOff, d_nSlot, d_nM, d_rowIdx, rowStride, d_landOff, d_method, o, s);
+}
+
+int kbest_reserve_quadric_map_factors_dev(kbest_ctx *ctx, int B, int maxMap, int maxKeep, int maxCol)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    KB_TRY(kbest_reserve_quadric_map_dev(ctx, B, maxMap, maxKeep, maxCol));
+    return kbest_reserve_assoc_factors_dev(ctx, B, maxCol);
+}
+
+int kbest_quadric_map_factors_batch_f64_dev(kbest_ctx *ctx, int B, int maxMap, int maxKeep, int maxCol, const double *d_mapMean,
+                                            const double *d_mapCov, const int64_t *d_landOff, const int32_t *d_nL,
+                                            const double *d_measMean, const double *d_measCov, const int64_t *d_measOff,
+                                            const int32_t *d_nM, double gate, int maxExact, int maxWidth, int32_t *d_nKeep,
+                                            int32_t *d_rowIdx, double *d_ccost, double *d_cprobs, double *d_probs,
+                                            const int64_t *d_probOff, double *d_logPerm, int32_t *d_method, int32_t *d_nOpen,
+                                            int32_t *d_nFrontier, int32_t *d_maxCluster, double factorThresh, double newThresh,
+                                            double boxSd, int64_t maxFactor, int32_t *d_fFrame, int32_t *d_fMeas, int32_t *d_fLand,
+                                            int64_t *d_fMap, double *d_fProb, double *d_fSigma, int64_t maxNew, int32_t *d_nFrame,
+                                            int32_t *d_nMeas, double *d_nProb, double *d_nSigma, int32_t *d_nFactor,
+                                            int64_t *d_factorOff, int32_t *d_nNew, int64_t *d_newOff, int64_t *d_total,
+                                            int32_t *d_support, int64_t nSupport, void *stream)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    const char *who = "kbest_quadric_map_factors_batch_f64_dev";
+    KB_TRY(qmap_check(ctx, who, B, maxMap, maxKeep, maxCol));
+    const FactorOut o{factorThresh, newThresh, boxSd, maxFactor, d_fFrame, d_fMeas, d_fLand, d_fMap, d_fProb, d_fSigma, maxNew,
+                      d_nFrame, d_nMeas, d_nProb, d_nSigma, d_nFactor, d_factorOff, d_nNew, d_newOff, d_total, d_support, nSupport};
+    KB_TRY(factors_check(ctx, who, B, maxKeep, maxCol, true, maxKeep, o));
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // both reservations are checked before anything is launched: this one here, the other by the probability entry itself
+    if (!factors_reserved(ctx, B, maxCol))
+        return fail(ctx, KBEST_ERR_NOT_RESERVED, "kbest_quadric_map_factors_batch_f64_dev: call kbest_reserve_quadric_map_factors_dev first");
+    KB_TRY(kbest_quadric_map_probs_batch_f64_dev(ctx, B, maxMap, maxKeep, maxCol, d_mapMean, d_mapCov, d_landOff, d_nL, d_measMean, d_measCov,
+                                                 d_measOff, d_nM, gate, maxExact, maxWidth, d_nKeep, d_rowIdx, d_ccost, d_cprobs, d_probs,
+                                                 d_probOff, d_logPerm, d_method, d_nOpen, d_nFrontier, d_maxCluster, stream));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    KB_TRY(order_behind_last(ctx, s));
+    const Launched mark{ctx, s};
+    // the compact probabilities where the probability entry left them: frame b's [nM][nKeep + 1] at b maxCol (maxKeep + 1), the
+    // offsets in the quadric-map work space (written for every frame); nKeep > maxKeep is beyond maxSlot, and such a frame has method -1
+    const int64_t *d_cprobOff = nullptr;
+    if (B > 0) {
+        hold_if_capturing(s, {&ctx->qmapBuf});
+        d_cprobOff = reinterpret_cast<const int64_t *>(static_cast<unsigned char *>(ctx->qmapBuf.p) + qmap_layout(B, maxMap, maxKeep, maxCol).cprobOff);
+    }
+    return factors_launch(ctx, B, maxKeep, maxCol, d_cprobs, d_cprobOff, d_nKeep, d_nM, d_rowIdx, maxKeep, d_landOff, d_method, o, s);
+}
+
+int kbest_factors_kernel_usage(int which, int32_t *vgprs, int32_t *scratchBytes, int32_t *ldsBytes)
+{
+    int v = 0, sc = 0, l = 0;
+    if (which < 0 || which > 3 || !vgprs || !scratchBytes || !ldsBytes) return KBEST_ERR_BAD_ARG;
+    if (kb::factors_kernel_usage(which, &v, &sc, &l) != hipSuccess) return KBEST_ERR_HIP;
+    *vgprs = v;
+    *scratchBytes = sc;
+    *ldsBytes = l;
+    return KBEST_OK;
+}
+
+// The synchronous entry on host buffers: the dense [nM][nL + 1] slices every host probability entry returns are staged, the device
+// entry runs in dense form, the lists (up to the capacities) and the counts come back.
+int kbest_assoc_factors_batch_f64(kbest_ctx *ctx, int B, const double *probs, const int64_t *probOff, const int32_t *nL,
+                                  const int32_t *nM, const int64_t *landOff, const int32_t *method, double factorThresh,
+                                  double newThresh, double boxSd, int64_t maxFactor, int32_t *fFrame, int32_t *fMeas, int32_t *fLand,
+                                  int64_t *fMap, double *fProb, double *fSigma, int64_t maxNew, int32_t *nFrame, int32_t *nMeas,
+                                  double *nProb, double *nSigma, int32_t *nFactor, int64_t *factorOff, int32_t *nNew, int64_t *newOff,
+                                  int64_t *total, int32_t *support, int64_t nSupport)
+{
+    if (!ctx) return KBEST_ERR_BAD_ARG;
+    const char *who = "kbest_assoc_factors_batch_f64";
+    int maxSlot = 0, maxCol = 1;
+    int64_t nProbs = 0;  // doubles to stage: up to the end of the last slice of a frame that may emit
+    if (B < 0 || !total || (B > 0 && (!probs || !probOff || !nL || !nM))) return fail(ctx, KBEST_ERR_BAD_ARG, (std::string(who) + FACTOR_ARGS_TEXT).c_str());
+    for (int b = 0; b < B; b++) {
+        if (nM[b] < 1 || nL[b] < 0 || probOff[b] < 0 || (method && method[b] < 0) || (landOff && landOff[b] < 0)) continue;  // emits nothing
+        if (nM[b] > kb::FACTOR_MAX_COLS) return fail(ctx, KBEST_ERR_UNSUPPORTED, (std::string(who) + CLUSTER_COLS_TEXT).c_str());
+        if (nL[b] > KBEST_QUADRIC_MAP_MAX) return fail(ctx, KBEST_ERR_UNSUPPORTED, (std::string(who) + ": more than KBEST_QUADRIC_MAP_MAX landmarks in a frame").c_str());
+        maxSlot = std::max(maxSlot, nL[b]);
+        maxCol = std::max(maxCol, nM[b]);
+        nProbs = std::max(nProbs, probOff[b] + (int64_t)nM[b] * ((int64_t)nL[b] + 1));
+    }
+    const FactorOut h{factorThresh, newThresh, boxSd, maxFactor, fFrame, fMeas, fLand, fMap, fProb, fSigma, maxNew,
+                      nFrame, nMeas, nProb, nSigma, nFactor, factorOff, nNew, newOff, total, support, nSupport};
+    KB_TRY(factors_check(ctx, who, B, maxSlot, maxCol, false, 0, h));
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    KB_TRY(kbest_reserve_assoc_factors_dev(ctx, B, maxCol));
+    // one block each: doubles (probs | fProb | fSigma | nProb | nSigma), int64 (probOff | landOff | factorOff | newOff | total | fMap),
+    // int32 (nL | nM | method | nFactor | nNew | fFrame | fMeas | fLand | nFrame | nMeas | support)
+    const size_t b = (size_t)B, cf = (size_t)maxFactor, cn = (size_t)maxNew, ns = support ? (size_t)nSupport : 0;
+    DevBuf dD, dL, dI;
+    hipError_t e;
+    if ((e = dD.alloc(ctx, ((size_t)nProbs + 2 * cf + 2 * cn) * 8)) != hipSuccess || (e = dL.alloc(ctx, (4 * b + 2 + cf) * 8)) != hipSuccess ||
+        (e = dI.alloc(ctx, (5 * b + 3 * cf + 2 * cn + ns) * 4)) != hipSuccess)
+        return fail(ctx, KBEST_ERR_NOMEM, (std::string(who) + ": device buffers").c_str(), e);
+    double *d_probs = dD.as<double>(), *d_fProb = d_probs + nProbs, *d_fSigma = d_fProb + cf, *d_nProb = d_fSigma + cf, *d_nSigma = d_nProb + cn;
+    int64_t *d_probOff = dL.as<int64_t>(), *d_landOff = d_probOff + b, *d_factorOff = d_landOff + b, *d_newOff = d_factorOff + b,
+            *d_total = d_newOff + b, *d_fMap = d_total + 2;
+    int32_t *d_nL = dI.as<int32_t>(), *d_nM = d_nL + b, *d_method = d_nM + b, *d_nFactor = d_method + b, *d_nNew = d_nFactor + b,
+            *d_fFrame = d_nNew + b, *d_fMeas = d_fFrame + cf, *d_fLand = d_fMeas + cf, *d_nFrame = d_fLand + cf, *d_nMeas = d_nFrame + cn,
+            *d_support = d_nMeas + cn;
+    if (nProbs > 0) HIP_TRY(ctx, hipMemcpy(d_probs, probs, (size_t)nProbs * 8, hipMemcpyHostToDevice));
+    if (B > 0) {
+        HIP_TRY(ctx, hipMemcpy(d_probOff, probOff, b * 8, hipMemcpyHostToDevice));
+        if (landOff) HIP_TRY(ctx, hipMemcpy(d_landOff, landOff, b * 8, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(d_nL, nL, b * 4, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(d_nM, nM, b * 4, hipMemcpyHostToDevice));
+        if (method) HIP_TRY(ctx, hipMemcpy(d_method, method, b * 4, hipMemcpyHostToDevice));
+    }
+    KB_TRY(kbest_assoc_factors_f64_dev(ctx, B, maxSlot, maxCol, d_probs, d_probOff, d_nL, d_nM, nullptr, 0, landOff ? d_landOff : nullptr,
+                                       method ? d_method : nullptr, factorThresh, newThresh, boxSd, maxFactor, cf ? d_fFrame : nullptr,
+                                       cf ? d_fMeas : nullptr, cf ? d_fLand : nullptr, cf && fMap ? d_fMap : nullptr, cf ? d_fProb : nullptr,
+                                       cf ? d_fSigma : nullptr, maxNew, cn ? d_nFrame : nullptr, cn ? d_nMeas : nullptr,
+                                       cn ? d_nProb : nullptr, cn ? d_nSigma : nullptr, d_nFactor, d_factorOff, d_nNew, d_newOff, d_total,
+                                       support ? d_support : nullptr, nSupport, nullptr));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpy(total, d_total, 16, hipMemcpyDeviceToHost));
+    if (B > 0) {
+        HIP_TRY(ctx, hipMemcpy(nFactor, d_nFactor, b * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(nNew, d_nNew, b * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(factorOff, d_factorOff, b * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(newOff, d_newOff, b * 8, hipMemcpyDeviceToHost));
+    }
+    const size_t gf = (size_t)std::min<int64_t>(total[0], maxFactor), gn = (size_t)std::min<int64_t>(total[1], maxNew);
+    if (gf) {
+        HIP_TRY(ctx, hipMemcpy(fFrame, d_fFrame, gf * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(fMeas, d_fMeas, gf * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(fLand, d_fLand, gf * 4, hipMemcpyDeviceToHost));
+        if (fMap) HIP_TRY(ctx, hipMemcpy(fMap, d_fMap, gf * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(fProb, d_fProb, gf * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(fSigma, d_fSigma, gf * 8, hipMemcpyDeviceToHost));
+    }
+    if (gn) {
+        HIP_TRY(ctx, hipMemcpy(nFrame, d_nFrame, gn * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(nMeas, d_nMeas, gn * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(nProb, d_nProb, gn * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(nSigma, d_nSigma, gn * 8, hipMemcpyDeviceToHost));
+    }
+    if (ns) HIP_TRY(ctx, hipMemcpy(support, d_support, ns * 4, hipMemcpyDeviceToHost));
+    return KBEST_OK;
 }
 
 int kbest_bruteforce_probs_batch_f64(kbest_ctx *ctx, int B, const int32_t *nL, const int32_t *nM, const double *cost,

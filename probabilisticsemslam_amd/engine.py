@@ -74,6 +74,8 @@ C_ABI_SYMBOLS = (
     "kbest_quadric_map_kernel_usage",
     "kbest_reserve_quadric_map_sample_dev", "kbest_quadric_map_sample_assoc_batch_f64_dev", "kbest_quadric_map_sample_assoc_batch_f64",
     "kbest_quadric_map_sample_kernel_usage",
+    "kbest_reserve_assoc_factors_dev", "kbest_assoc_factors_f64_dev", "kbest_reserve_quadric_map_factors_dev",
+    "kbest_quadric_map_factors_batch_f64_dev", "kbest_assoc_factors_batch_f64", "kbest_factors_kernel_usage",
 )
 KBEST_MULTI_STAMPS = 6
 KBEST_MULTI_BATCH, KBEST_MULTI_SUBTREE = 0, 1
@@ -261,6 +263,17 @@ def load_library():
                                                                  C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint32, i64p, i32p,
                                                                  i64p, dp, i64p, dp, i32p, i32p, i32p, i32p, i32p, i32p]
         lib.kbest_quadric_map_sample_kernel_usage.argtypes = [i32p, i32p, i32p]
+    if hasattr(lib, "kbest_assoc_factors_f64_dev"):
+        i64 = C.c_int64
+        # thresholds, capacities, lists, counts, support: the factor arguments every entry ends with (before the stream)
+        fargs = [C.c_double, C.c_double, C.c_double, i64, i32p, i32p, i32p, i64p, dp, dp, i64, i32p, i32p, dp, dp, i32p, i64p, i32p,
+                 i64p, i64p, i32p, i64]
+        lib.kbest_reserve_assoc_factors_dev.argtypes = [vp, C.c_int, C.c_int]
+        lib.kbest_assoc_factors_f64_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, i64p, i32p, i32p, i32p, i64, i64p, i32p] + fargs + [vp]
+        lib.kbest_reserve_quadric_map_factors_dev.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
+        lib.kbest_quadric_map_factors_batch_f64_dev.argtypes = lib.kbest_quadric_map_probs_batch_f64_dev.argtypes[:-1] + fargs + [vp]
+        lib.kbest_assoc_factors_batch_f64.argtypes = [vp, C.c_int, dp, i64p, i32p, i32p, i64p, i32p] + fargs
+        lib.kbest_factors_kernel_usage.argtypes = [C.c_int, i32p, i32p, i32p]
     lib.kbest_register_host_buffer.argtypes = [vp, vp, C.c_size_t]
     lib.kbest_unregister_host_buffer.argtypes = [vp, vp]
     _lib = lib
@@ -932,6 +945,132 @@ class KBestEngine:
             int(n_sample), int(seed), int(sample_base), _dptr(d_frameKey), _dptr(d_nKeep), _dptr(d_rowIdx), _dptr(d_ccost),
             _dptr(d_assign), _dptr(d_asgOff), _dptr(d_logProb), _dptr(d_lpOff), _dptr(d_logPerm), _dptr(d_method), _dptr(d_nOpen),
             _dptr(d_nFrontier), _dptr(d_maxCluster), _stream(stream)))
+
+    # ---- factor lists from association probabilities (kbest_factors.hip; the reference's consumer loop, system.cpp:279-346) ----
+    @staticmethod
+    def _factor_args(ptr, factor_thresh, new_thresh, box_sd, max_factor, factors, max_new, news, counts, total, support, n_support):
+        """The factor arguments every C entry ends with.  factors: (fFrame, fMeas, fLand, fMap or None, fProb, fSigma) or None with
+        capacity 0; news: (nFrame, nMeas, nProb, nSigma) or None with capacity 0; counts: (nFactor, factorOff, nNew, newOff)."""
+        f = tuple(factors) if factors is not None else (None,) * 6
+        n = tuple(news) if news is not None else (None,) * 4
+        c = tuple(counts) if counts is not None else (None,) * 4
+        if len(f) != 6 or len(n) != 4 or len(c) != 4:
+            raise KBestError("factor lists: 6 factor arrays, 4 new-landmark arrays, 4 count arrays")
+        return (float(factor_thresh), float(new_thresh), float(box_sd), int(max_factor)) + tuple(ptr(x) for x in f) + (int(max_new),) + \
+            tuple(ptr(x) for x in n) + tuple(ptr(x) for x in c) + (ptr(total), ptr(support), int(n_support))
+
+    def reserve_assoc_factors_dev(self, B, maxCol):
+        """kbest_reserve_assoc_factors_dev: the per-(frame, measurement) counts and scan partials of assoc_factors_dev (never shrinks)."""
+        self._check(self.lib.kbest_reserve_assoc_factors_dev(self.ctx, int(B), int(maxCol)))
+
+    def assoc_factors_dev(self, B, maxSlot, maxCol, d_probs, d_probOff, d_nSlot, d_nM, max_factor, d_factors, max_new, d_news, d_counts,
+                          d_total, d_rowIdx=None, row_stride=0, d_landOff=None, d_method=None, d_support=None, n_support=0,
+                          factor_thresh=0.05, new_thresh=0.33, box_sd=3.0, stream=None, reserve=True):
+        """kbest_assoc_factors_f64_dev on torch CUDA tensors (or raw addresses), asynchronous on `stream`: the thresholded, ordered
+        factor and new-landmark lists of the probabilities of any entry, without a host read, a synchronise or an allocation.  Frame
+        b: [nM][nSlot + 1] at d_probOff[b]; d_rowIdx (None: dense form) int32 [B][row_stride]; d_factors = (fFrame, fMeas, fLand int32,
+        fMap int64 or None, fProb, fSigma float64) or None with max_factor 0; d_news = (nFrame, nMeas int32, nProb, nSigma float64) or
+        None with max_new 0; d_counts = (nFactor int32, factorOff int64, nNew int32, newOff int64), each [B]; d_total int64 [2];
+        d_support int32 [n_support] or None.  reserve=False: the caller has called reserve_assoc_factors_dev."""
+        if reserve:
+            self.reserve_assoc_factors_dev(B, maxCol)
+        self._check(self.lib.kbest_assoc_factors_f64_dev(
+            self.ctx, int(B), int(maxSlot), int(maxCol), _dptr(d_probs), _dptr(d_probOff), _dptr(d_nSlot), _dptr(d_nM), _dptr(d_rowIdx),
+            int(row_stride), _dptr(d_landOff), _dptr(d_method),
+            *self._factor_args(_dptr, factor_thresh, new_thresh, box_sd, max_factor, d_factors, max_new, d_news, d_counts, d_total,
+                               d_support, n_support), _stream(stream)))
+
+    def reserve_quadric_map_factors_dev(self, B, maxMap, maxKeep, maxCol):
+        """kbest_reserve_quadric_map_factors_dev: reserve_quadric_map_dev and reserve_assoc_factors_dev."""
+        self._check(self.lib.kbest_reserve_quadric_map_factors_dev(self.ctx, int(B), int(maxMap), int(maxKeep), int(maxCol)))
+
+    def quadric_map_factors_dev(self, B, maxMap, maxKeep, maxCol, d_mapMean, d_mapCov, d_landOff, d_nL, d_measMean, d_measCov, d_measOff,
+                                d_nM, gate, d_nKeep, d_rowIdx, d_cprobs, d_method, max_factor, d_factors, max_new, d_news, d_counts,
+                                d_total, d_ccost=None, d_probs=None, d_probOff=None, d_logPerm=None, d_nOpen=None, d_nFrontier=None,
+                                d_maxCluster=None, d_support=None, n_support=0, factor_thresh=0.05, new_thresh=0.33, box_sd=3.0,
+                                max_exact=16, max_width=16, stream=None, reserve=True):
+        """kbest_quadric_map_factors_batch_f64_dev: quadric_map_probs_dev (same arguments, same bits, d_probs may stay None), then
+        the factor passes of assoc_factors_dev in compact form on d_cprobs, d_rowIdx and d_nKeep with d_method, all on `stream`.
+        reserve=False: the caller has called reserve_quadric_map_factors_dev (timed loops, graph capture)."""
+        if reserve:
+            self.reserve_quadric_map_factors_dev(B, maxMap, maxKeep, maxCol)
+        self._check(self.lib.kbest_quadric_map_factors_batch_f64_dev(
+            self.ctx, int(B), int(maxMap), int(maxKeep), int(maxCol), _dptr(d_mapMean), _dptr(d_mapCov), _dptr(d_landOff), _dptr(d_nL),
+            _dptr(d_measMean), _dptr(d_measCov), _dptr(d_measOff), _dptr(d_nM), float(gate), int(max_exact), int(max_width),
+            _dptr(d_nKeep), _dptr(d_rowIdx), _dptr(d_ccost), _dptr(d_cprobs), _dptr(d_probs), _dptr(d_probOff), _dptr(d_logPerm),
+            _dptr(d_method), _dptr(d_nOpen), _dptr(d_nFrontier), _dptr(d_maxCluster),
+            *self._factor_args(_dptr, factor_thresh, new_thresh, box_sd, max_factor, d_factors, max_new, d_news, d_counts, d_total,
+                               d_support, n_support), _stream(stream)))
+
+    def assoc_factors(self, probs_list, land_off=None, method=None, factor_thresh=0.05, new_thresh=0.33, box_sd=3.0, max_factor=None,
+                      max_new=None, n_support=0):
+        """kbest_assoc_factors_batch_f64 on the dense [nM, nL + 1] arrays every host probability entry returns.  land_off[B] (None:
+        0) gives the map index of a frame's landmark 0, method[B] (None: every frame emits) the method of the probability entry: a
+        frame with method < 0 emits nothing.  max_factor / max_new None: a counting call first, then the exact capacities.  Returns
+        a dict: factors (per frame a dict meas, land, map, prob, sigma), new (per frame a dict meas, prob, sigma), flat (the lists
+        as they are: fFrame, fMeas, fLand, fMap, fProb, fSigma, nFrame, nMeas, nProb, nSigma, cut at min(total, capacity)), nFactor,
+        factorOff, nNew, newOff, total (the true totals) and support (int32 [n_support], None with n_support 0)."""
+        B = len(probs_list)
+        arrs = [np.ascontiguousarray(p, dtype=np.float64) for p in probs_list]
+        if any(a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1 for a in arrs):
+            raise KBestError("assoc_factors: every frame is an [nM, nL + 1] array with nM >= 1")
+        nM = np.array([a.shape[0] for a in arrs], np.int32)
+        nL = np.array([a.shape[1] - 1 for a in arrs], np.int32)
+        sizes = np.array([a.size for a in arrs], np.int64)
+        probOff = np.zeros(B, np.int64)
+        probOff[1:] = np.cumsum(sizes)[:-1]
+        flat = np.concatenate([np.zeros(0)] + [a.reshape(-1) for a in arrs])
+        lo = None if land_off is None else np.ascontiguousarray(land_off, dtype=np.int64)
+        me = None if method is None else np.ascontiguousarray(method, dtype=np.int32)
+        if (lo is not None and lo.shape != (B,)) or (me is not None and me.shape != (B,)):
+            raise KBestError("assoc_factors: land_off and method hold one number per frame")
+        counts = (np.zeros(max(B, 1), np.int32), np.zeros(max(B, 1), np.int64), np.zeros(max(B, 1), np.int32), np.zeros(max(B, 1), np.int64))
+        total = np.zeros(2, np.int64)
+        support = np.zeros(int(n_support), np.int32) if n_support else None
+
+        def call(cf, cn):
+            f = (np.zeros(cf, np.int32), np.zeros(cf, np.int32), np.zeros(cf, np.int32), np.zeros(cf, np.int64), np.zeros(cf), np.zeros(cf))
+            n = (np.zeros(cn, np.int32), np.zeros(cn, np.int32), np.zeros(cn), np.zeros(cn))
+            self._check(self.lib.kbest_assoc_factors_batch_f64(
+                self.ctx, B, _ptr(flat), _ptr(probOff), _ptr(nL), _ptr(nM), _ptr(lo), _ptr(me),
+                *self._factor_args(_ptr, factor_thresh, new_thresh, box_sd, cf, f if cf else None, cn, n if cn else None, counts, total,
+                                   support, n_support)))
+            return f, n
+
+        if max_factor is None or max_new is None:
+            call(0, 0)
+            max_factor = int(total[0]) if max_factor is None else int(max_factor)
+            max_new = int(total[1]) if max_new is None else int(max_new)
+        f, n = call(int(max_factor), int(max_new))
+        gf, gn = min(int(total[0]), int(max_factor)), min(int(total[1]), int(max_new))
+        f, n = tuple(a[:gf] for a in f), tuple(a[:gn] for a in n)
+        nFactor, factorOff, nNew, newOff = (c[:B].copy() for c in counts)
+        cutf = lambda a, b: a[min(int(factorOff[b]), gf): min(int(factorOff[b]) + int(nFactor[b]), gf)]  # noqa: E731
+        cutn = lambda a, b: a[min(int(newOff[b]), gn): min(int(newOff[b]) + int(nNew[b]), gn)]  # noqa: E731
+        return dict(
+            factors=[dict(meas=cutf(f[1], b), land=cutf(f[2], b), map=cutf(f[3], b), prob=cutf(f[4], b), sigma=cutf(f[5], b)) for b in range(B)],
+            new=[dict(meas=cutn(n[1], b), prob=cutn(n[2], b), sigma=cutn(n[3], b)) for b in range(B)],
+            flat=dict(zip(("fFrame", "fMeas", "fLand", "fMap", "fProb", "fSigma", "nFrame", "nMeas", "nProb", "nSigma"), f + n)),
+            nFactor=nFactor, factorOff=factorOff, nNew=nNew, newOff=newOff, total=total.copy(), support=support)
+
+    def quadric_map_factors(self, map_mean, map_cov, frames, gate, factor_thresh=0.05, new_thresh=0.33, box_sd=3.0, k=0, max_exact=16,
+                            max_big=20, max_width=16, support=True):
+        """From quadrics against one map to the factor lists: quadric_map_probs(map_mean, map_cov, frames, gate, k, ...) and
+        assoc_factors on its dense slices with the frames' landOff and method -- the defaults are the reference's
+        NEW_FACTOR_PROB_THRESH, NEW_LANDMARK_THRESH and BOX_SD (constsUtils.h:75-78).  Returns the dict of assoc_factors (support
+        over the whole map, None with support=False) with method, nKeep and logPerm of the probability entry added."""
+        out = self.quadric_map_probs(map_mean, map_cov, frames, gate, k=k, max_exact=max_exact, max_big=max_big, max_width=max_width)
+        n_map = len(np.asarray(map_mean, np.float64).reshape(-1, 3))
+        r = self.assoc_factors(out[0], land_off=[f[0] for f in frames], method=out[1], factor_thresh=factor_thresh, new_thresh=new_thresh,
+                               box_sd=box_sd, n_support=n_map if support else 0)
+        r.update(method=out[1], nKeep=out[2], logPerm=out[7])
+        return r
+
+    def factors_kernel_usage(self, which):
+        """(registers, scratch bytes, static LDS bytes) of a factor pass: 0 count, 1 scan inside a frame, 2 scan over the frames, 3 emit."""
+        v = np.zeros(3, np.int32)
+        self._check(self.lib.kbest_factors_kernel_usage(int(which), _ptr(v[0:1]), _ptr(v[1:2]), _ptr(v[2:3])))
+        return tuple(int(x) for x in v)
 
     def quadric_map_sample_kernel_usage(self):
         """(registers, scratch bytes, static LDS bytes) of the kernel that maps compact rows to raw rows."""
